@@ -7,10 +7,17 @@ written back to HBM).  A "step" is one pass of the batched JT kernel over the 10
 --gpus N (torchrun, one process per GPU) every rank processes its own 100k-case shard (seed +
 rank, no data-path collective) -> weak scaling; `value` = all cases / max-over-ranks time.
 
-Also reported (rank 0, N = 1): PC-stable CI-tests / s on alarm_s5000.txt (BASELINE config 3,
+A plain run sets up, warms up, times the --steps steps and prints the line (`ms_per_step` = wall
+time of the timed region / steps; the headline kernel's roofline from the committed counter
+summaries under profiles/).  --dump-outputs DIR writes the last timed step's labels and marginals
+as DIR/*.npy (`dump_outputs`); the inputs are seeded, so two builds can be compared output for output.
+
+With --full, also (rank 0, N = 1): the oracle and full-batch checks of the last step's outputs,
+PC-stable CI-tests / s on alarm_s5000.txt (BASELINE config 3,
 reference-equivalent test count), the dominant kernel's HBM roofline (algorithmic bytes per case =
 16*(sum clique + separator entries) + 8*sum dom + V = 22,877 B) and the CPU baseline
-(the unmodified reference's per-case loop, oracle/_ref, timed on this host on a bounded sample).
+(the unmodified reference's per-case loop, oracle/_ref, timed on this host on a bounded sample);
+at N > 1 the Munin-like and PC-stable legs over the ranks.
 """
 import argparse
 import json
@@ -29,6 +36,9 @@ ALARM = os.path.join(REPO, "tests", "golden", "alarm")
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md)
 CASES_PER_GPU = 100_000
 EVIDENCE_PER_CASE = 7
+MAX_LABEL_SLICES = 4096  # per-step label buffers of a one-GPU run (1.6 GB at 100k cases)
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: marginal rows written (float64), labels beside them
+DUMP_SEED = 20250131
 
 
 def log(*a):
@@ -652,6 +662,30 @@ def oracle_sample(n, head, spread):
     return np.unique(np.concatenate([np.arange(min(head, n)), np.linspace(0, n - 1, spread).astype(np.int64)]))
 
 
+def dump_outputs(dirname, d_lab, d_marg, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: what the last timed step left in its output buffers, as the caller of
+    fbn_jt_run_device reads them -- labels.npy (float32 [cases], every case) and marginals.npy
+    (float64 [rows][sum_dom], case-major rows whatever the device layout).  All cases' marginals
+    where they fit `budget` bytes; else a seeded sample of the cases (ascending, the same for the
+    same case count, row size and seed), whose indices go to marginal_cases.npy (float64, exact)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n, width = d_marg.shape
+    rows = min(n, max(1, budget // (8 * width)))
+    if rows < n:
+        pick = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=rows, replace=False))
+    else:
+        pick = np.arange(n)
+    marg = d_marg[torch.from_numpy(pick).to(d_marg.device)].cpu().numpy().astype(np.float64, copy=False)
+    files = {"labels": d_lab.cpu().numpy().astype(np.float32), "marginals": np.ascontiguousarray(marg),
+             "marginal_cases": pick.astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": {k: list(a.shape) for k, a in files.items()},
+            "bytes": int(sum(a.nbytes for a in files.values())),
+            "marginal_rows": "all" if rows == n else f"{rows} of {n} cases (PCG64 seed {seed}, ascending)"}
+
+
 def bench_munin(steps, warmup, cases=125_000, rank=0, world=1, device=0, with_baseline=False, exact=None):
     """the seeded Munin-like 1041-variable network at 20 % evidence (208
     variables per case), 125k cases per GPU -- on 8 GPUs the 1M-case job sharded by rank (seed
@@ -901,6 +935,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--cases", type=int, default=CASES_PER_GPU)
     ap.add_argument("--waves-per-cu", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the oracle / full-batch checks of the last step, the PCIe-inclusive "
+                         "rate, PC-stable, Munin-like JT, loaders and the CPU baselines (minutes); --no-* trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's labels and marginals to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--no-pc", action="store_true")
     ap.add_argument("--no-munin", action="store_true")
@@ -910,6 +949,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     # --gpus N is the number of rank processes.  Under a launcher (torchrun sets WORLD_SIZE) the two
     # must agree; without one, N > 1 starts the ranks here, before anything touches the GPU.
@@ -988,7 +1029,10 @@ def main():
     # step at world size 1 even asynchronous: the collective's call overhead.)
     # (FBN_BENCH_FORCE_GATHER=1: the gather at world size 1 too -- a test of the RCCL path)
     gathering = world > 1 or (os.environ.get("FBN_BENCH_FORCE_GATHER") == "1" and dist.is_initialized())
-    step_labs = torch.empty((max(1, args.steps), args.cases), dtype=torch.int32, device=dev)
+    # (without the gather nothing reads the older slices: at most MAX_LABEL_SLICES, reused in turn, so
+    # a long --steps run does not grow with its step count)
+    slices = args.steps if gathering else min(args.steps, MAX_LABEL_SLICES)
+    step_labs = torch.empty((slices, args.cases), dtype=torch.int32, device=dev)
     all_labs = torch.empty(world * step_labs.numel(), dtype=torch.int32, device=dev) if gathering else None
 
     def step(i=0):
@@ -1033,25 +1077,32 @@ def main():
     if gathering:  # the gathered labels hold every rank's labels of every step, in rank order
         n1 = step_labs.numel()
         assert torch.equal(all_labs[rank * n1:(rank + 1) * n1], step_labs.view(-1)), "label all-gather"
-    # sanity: labels of the last step agree with a CPU recomputation on a few cases (not timed)
-    if rank == 0:
-        sys.path.insert(0, os.path.join(REPO, "oracle"))
-        import oracle as O
-        pick = oracle_sample(args.cases, 256, 1792)
-        olab, omarg = O.OracleJT(os.path.join(ALARM, "alarm.xml")).infer(ev[pick])
-        # default (fast) arithmetic order: labels equal, marginals within 1e-12 relative
-        ip = torch.from_numpy(pick).to(dev)
-        gm = d_marg[ip].cpu().numpy()
-        alarm_rel = float(np.max(np.abs(gm - omarg) / np.maximum(np.abs(omarg), 1e-300)))
-        ok = (d_lab[ip].cpu().numpy() == olab).all() and alarm_rel <= 1e-12
-        if not ok:
-            log("ERROR: GPU results differ from the oracle")
+    dumped = dump_outputs(args.dump_outputs, d_lab, d_marg) if (args.dump_outputs and rank == 0) else None
+    checks = {}
+    if args.full:
+        # sanity: labels of the last step agree with a CPU recomputation on a few cases (not timed)
+        if rank == 0:
+            sys.path.insert(0, os.path.join(REPO, "oracle"))
+            import oracle as O
+            pick = oracle_sample(args.cases, 256, 1792)
+            olab, omarg = O.OracleJT(os.path.join(ALARM, "alarm.xml")).infer(ev[pick])
+            # default (fast) arithmetic order: labels equal, marginals within 1e-12 relative
+            ip = torch.from_numpy(pick).to(dev)
+            gm = d_marg[ip].cpu().numpy()
+            alarm_rel = float(np.max(np.abs(gm - omarg) / np.maximum(np.abs(omarg), 1e-300)))
+            ok = (d_lab[ip].cpu().numpy() == olab).all() and alarm_rel <= 1e-12
+            if not ok:
+                log("ERROR: GPU results differ from the oracle")
+                sys.exit(1)
+        # every case of the last step: size-independent properties (each rank its own shard)
+        alarm_props = jt_full_batch_properties(d_ev, d_lab, d_marg, alarm_net.dims)
+        if not alarm_props["ok"]:
+            log(f"ERROR: full-batch properties violated: {alarm_props}")
             sys.exit(1)
-    # every case of the last step: size-independent properties (each rank its own shard)
-    alarm_props = jt_full_batch_properties(d_ev, d_lab, d_marg, alarm_net.dims)
-    if not alarm_props["ok"]:
-        log(f"ERROR: full-batch properties violated: {alarm_props}")
-        sys.exit(1)
+        checks = {"parity_vs_oracle": {"cases": int(len(pick)) if rank == 0 else None,
+                                       "sample": "first 256 + 1792 spread over the batch", "labels_equal": True,
+                                       "max_rel_err": alarm_rel if rank == 0 else None},
+                  "full_batch_properties": alarm_props}
 
     total_cases = args.cases * args.steps * world
     value = total_cases / elapsed
@@ -1066,6 +1117,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": 1e3 * elapsed / args.steps,
+        "full": args.full,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1080,19 +1132,19 @@ def main():
                                                               if world > 1 else "")},
         "roofline": {**roof, "kernel_variant": jt.refresh_info()["variant"],
                      "arithmetic_order": "fast (normalizations cancel; labels equal, marginals within 1e-12)",
-                     "parity_vs_oracle": {"cases": int(len(pick)) if rank == 0 else None,
-                                          "sample": "first 256 + 1792 spread over the batch", "labels_equal": True,
-                                          "max_rel_err": alarm_rel if rank == 0 else None},
-                     "full_batch_properties": alarm_props},
+                     **checks},
     }
-    if world > 1 and not args.no_munin:
+    if dumped:
+        out["dumped_outputs"] = dumped
+    # everything below is beside the headline: --full only
+    if args.full and world > 1 and not args.no_munin:
         # BASELINE config 4 at its real scale: 125k Munin-like cases per rank (1M on 8 GPUs)
         out["munin_like"] = bench_munin(3, 1, rank=rank, world=world, device=local)
-    if world > 1 and not args.no_pc:
+    if args.full and world > 1 and not args.no_pc:
         # BASELINE configs 3 and 5 on N GPUs: edge ranges per level, one all-gather per level
         out["pc_stable"] = bench_pc_alarm_dist(10, rank, world, local)
         out["pc_synthetic"] = bench_pc_synth_dist(5, rank, world, local)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # PCIe-inclusive rate (host evidence in, host labels + marginals out through fbn_jt_run):
         # reported beside the metric, never as `value`
         log("bench: PCIe-inclusive JT rate")

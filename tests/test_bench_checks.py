@@ -59,6 +59,30 @@ def test_oracle_sample_indices():
     assert list(bench.oracle_sample(5, 16, 48)) == [0, 1, 2, 3, 4]
 
 
+def test_dump_outputs_all_rows_or_fixed_sample(tmp_path):
+    """--dump-outputs: float32 labels of every case; every marginal row where the budget holds them,
+    else the same seeded ascending sample on every call, rows read through a transposed
+    (variable-major) view included."""
+    import torch
+    ev, lab, marg, dims = _batch(n=64)
+    n, w = marg.shape
+    a = bench.dump_outputs(str(tmp_path / "a"), lab, marg)
+    assert a["marginal_rows"] == "all" and a["files"]["marginals"] == [n, w]
+    la, ma = np.load(tmp_path / "a" / "labels.npy"), np.load(tmp_path / "a" / "marginals.npy")
+    assert la.dtype == np.float32 and ma.dtype == np.float64
+    assert np.array_equal(la, lab.numpy()) and np.array_equal(ma, marg.numpy())
+    vm = marg.t().contiguous().t()  # the benchmark's view of a [sum_dom][cases] buffer
+    budget = 10 * 8 * w
+    for d in ("b", "c"):
+        r = bench.dump_outputs(str(tmp_path / d), lab, vm, budget=budget)
+        assert r["files"]["marginals"] == [10, w] and r["bytes"] <= budget + 4 * n + 8 * 10
+    pick = np.load(tmp_path / "b" / "marginal_cases.npy")
+    assert np.array_equal(pick, np.load(tmp_path / "c" / "marginal_cases.npy"))
+    assert len(pick) == 10 and (np.diff(pick) > 0).all() and 0 <= pick[0] and pick[-1] < n
+    assert np.array_equal(np.load(tmp_path / "b" / "marginals.npy"), marg.numpy()[pick.astype(np.int64)])
+    assert torch.equal(vm, marg)
+
+
 def _bench(args, env_extra=None):
     import json
     import subprocess

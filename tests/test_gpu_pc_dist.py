@@ -226,7 +226,7 @@ def test_bench_gpus_2_rehearsal_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["FBN_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-munin", "--no-loaders", "--no-baseline"], capture_output=True, text=True, env=env,
+                        "--full", "--no-munin", "--no-loaders", "--no-baseline"], capture_output=True, text=True, env=env,
                        timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -246,8 +246,8 @@ def test_bench_rccl_final_gather_at_world1():
     repo = os.path.dirname(GOLD.rstrip("/").rsplit("/", 1)[0])
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["FBN_BENCH_FORCE_GATHER"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1", "--no-munin",
-                        "--no-pc", "--no-loaders", "--no-baseline"], capture_output=True, text=True, env=env,
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                        "--no-munin", "--no-pc", "--no-loaders", "--no-baseline"], capture_output=True, text=True, env=env,
                        timeout=200)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

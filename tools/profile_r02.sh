@@ -8,7 +8,7 @@ set -o pipefail
 out=$1
 mkdir -p $out
 export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python -u bench.py --steps 10 --no-baseline --no-loaders > $out/stats_bench.json 2> $out/stats.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python -u bench.py --full --steps 10 --no-baseline --no-loaders > $out/stats_bench.json 2> $out/stats.err || exit 1
 VALU="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES"
 for c in FETCH_SIZE WRITE_SIZE VALU; do
   cc=$c; [ $c = VALU ] && cc="$VALU"

@@ -6,8 +6,8 @@ set -e
 out=$1
 mkdir -p $out
 export TMPDIR=/tmp
-timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python -u bench.py --steps 10 --no-baseline > $out/stats_bench.json 2> $out/stats.err
+timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python -u bench.py --full --steps 10 --no-baseline > $out/stats_bench.json 2> $out/stats.err
 cp $out/stats/run_kernel_stats.csv $out/kernel_stats.csv 2>/dev/null || find $out/stats -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
 bash tools/pmc_traffic.sh $out/traffic
 for c in FETCH_SIZE WRITE_SIZE; do
