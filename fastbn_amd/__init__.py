@@ -10,6 +10,8 @@ reference's names and argument meaning:
   -- include/PCStable.h:23-59
 * ``IndependenceTest(dataset, alpha).IndependenceResult(x, y, z)``
   -- include/IndependenceTest.h:30-56
+* ``ParameterLearning(source).LearnParamsKnowStructCompData(parents)``
+  -- src/ParameterLearning.cpp:11-64 (``pdag_to_dag`` turns PC-stable's CPDAG into its input)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -21,6 +23,9 @@ from .api import (  # noqa: F401
     IndependenceTest,
     PCStable,
     PCResult,
+    ParameterLearning,
+    family_sizes,
+    pdag_to_dag,
     orient_skeleton,
     shd_bif,
     lib,
@@ -31,5 +36,6 @@ from .api import (  # noqa: F401
     kernel_options,
 )
 
-__all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "orient_skeleton", "shd_bif",
+__all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
+           "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -102,6 +102,11 @@ _SIGS = {
     "fbn_pc_dist_apply": [_vp, _vp, _vp],
     "fbn_pc_dist_result": [_vp, _pp],
     "fbn_pc_dist_destroy": [_vp],
+    "fbn_param_family_sizes": [C.c_int, _vp, _vp, _vp, _vp, _vp],
+    "fbn_param_counts": [_vp, _vp, _vp, _vp, _i64, _vp],
+    "fbn_param_learn": [_vp, _vp, _vp, _vp, _pp],
+    "fbn_param_set_tuning": [_vp, _i64, _i64],
+    "fbn_pdag_to_dag": [C.c_int, _vp, C.c_int, _vp, _vp],
 }
 
 
@@ -144,7 +149,9 @@ class _Lib:
         def call(*args):
             rc = f(*args)
             if rc != 0:
-                raise FastBNError(f"{name}: {h.fbn_last_error().decode()} (code {rc})")
+                err = FastBNError(f"{name}: {h.fbn_last_error().decode()} (code {rc})")
+                err.code = rc  # the fbn_err_t value (include/fastbn.h)
+                raise err
             return rc
 
         return call
@@ -715,11 +722,13 @@ class PCStable:
     def __init__(self, alpha=0.05, depth=1000, device=0):
         self.alpha, self.depth, self.device = alpha, depth, device
         self.result = None
+        self.ci = None
 
     def StructLearnCompData(self, dataset, group_size=1, num_threads=1, print_struct=False, verbose=False):
         """`dataset`: a Dataset (uploaded for this call) or an IndependenceTest whose column store is
         already resident on the device (reused across calls)."""
         ci = dataset if isinstance(dataset, IndependenceTest) else IndependenceTest(dataset, self.alpha, self.device)
+        self.ci = ci  # the context of the run: ParameterLearning(pc.ci) learns from the same upload
         r = C.c_void_p()
         lib.fbn_pc_stable(ci._h, self.alpha, self.depth, group_size, C.byref(r))
         self.result = res = PCResult(r)
@@ -736,3 +745,87 @@ class PCStable:
 
     def GetSHD(self, bif_path):
         return self.result.GetSHD(bif_path)
+
+
+def _csr_parents(parents, nvars):
+    """List of parent lists -> (parent_off int32 [nvars+1], parents int32) for the C-ABI."""
+    if len(parents) != nvars:
+        raise FastBNError(f"{len(parents)} parent lists for {nvars} variables")
+    off = np.zeros(nvars + 1, np.int32)
+    for v in range(nvars):
+        off[v + 1] = off[v] + len(parents[v])
+    par = np.ascontiguousarray([int(q) for ps in parents for q in ps] or [0], np.int32)
+    return off, par
+
+
+def family_sizes(dims, parents):
+    """fbn_param_family_sizes: (family_off int64 [n+1], total cells) of the tables counts[v] =
+    [dims[v]][parent configurations]; raises FastBNError for a bad parent list (code -1) or a graph
+    past the cell cap (code -6).  Host only."""
+    d = np.ascontiguousarray(dims, np.int32)
+    off, par = _csr_parents(parents, len(d))
+    foff = np.zeros(len(d) + 1, np.int64)
+    total = C.c_int64()
+    lib.fbn_param_family_sizes(len(d), _p(d), _p(off), _p(par), _p(foff), C.byref(total))
+    return foff, total.value
+
+
+def pdag_to_dag(nvars, oriented):
+    """fbn_pdag_to_dag: a consistent DAG extension (Dor & Tarsi) of a PDAG given as PCResult.oriented
+    gives it -- (from, to, 1) arcs and (a, b, 0) undirected edges -- as a list of ascending parent
+    lists.  Deterministic; raises FastBNError if no extension exists.  Host only."""
+    n = len(oriented)
+    t = np.ascontiguousarray(np.asarray(oriented if n else [(0, 0, 0)], np.int32).reshape(-1, 3))
+    off = np.zeros(int(nvars) + 1, np.int32)
+    par = np.zeros(max(n, 1), np.int32)
+    lib.fbn_pdag_to_dag(int(nvars), _p(t), n, _p(off), _p(par))
+    return [[int(q) for q in par[off[v]:off[v + 1]]] for v in range(int(nvars))]
+
+
+class ParameterLearning:
+    """Maximum-likelihood counts of a known structure from complete data on the device
+    (ParameterLearning::LearnParamsKnowStructCompData).  `source`: a Dataset (uploaded here) or an
+    IndependenceTest, whose context -- and column store -- is shared, so PC-stable and learning use
+    one upload (PCStable.ci after a run)."""
+
+    def __init__(self, source, device=0):
+        self.ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=device)
+        self.dims = np.ascontiguousarray(self.ci.dims, np.int32)
+
+    def counts(self, parents):
+        """Family counts of every node: a list of int64 [dims[v]][parent configurations] arrays
+        (configurations over the parents in ascending index order, last fastest), the shape
+        Network.node_counts returns."""
+        n = len(self.dims)
+        off, par = _csr_parents(parents, n)
+        total = C.c_int64()
+        lib.fbn_param_counts(self.ci._h, _p(off), _p(par), None, 0, C.byref(total))
+        buf = np.zeros(max(total.value, 1), np.int64)
+        lib.fbn_param_counts(self.ci._h, _p(off), _p(par), _p(buf), total.value, C.byref(total))
+        out, o = [], 0
+        for v in range(n):
+            cells = int(self.dims[v]) * int(np.prod(self.dims[list(parents[v])], dtype=np.int64))
+            out.append(buf[o:o + cells].reshape(int(self.dims[v]), -1))
+            o += cells
+        return out
+
+    def LearnParamsKnowStructCompData(self, parents, names=None):
+        """The learned Network (fbn_param_learn): parents[v] in the node's own order."""
+        n = len(self.dims)
+        off, par = _csr_parents(parents, n)
+        nm = None
+        if names is not None:
+            enc = [os.fsencode(x) for x in names]
+            nm = (C.c_char_p * n)(*enc)
+        h = C.c_void_p()
+        lib.fbn_param_learn(self.ci._h, _p(off), _p(par), C.cast(nm, C.c_void_p) if nm is not None else None,
+                            C.byref(h))
+        return Network(_handle=h)
+
+    def set_tuning(self, samples_per_slice=0, lds_cells_max=0):
+        """fbn_param_set_tuning: samples per (family, slice) work item and the largest table counted
+        in LDS; 0 = default."""
+        lib.fbn_param_set_tuning(self.ci._h, int(samples_per_slice), int(lds_cells_max))
+
+    def last_kernel_ms(self):
+        return self.ci.last_kernel_ms()

@@ -18,6 +18,7 @@
 #include "pc_internal.h"
 #include "ci_chisq.h"
 #include "pc_small.h"
+#include "param_counts.h"
 
 extern "C" hipError_t fbn_jt_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
                                     const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
@@ -341,6 +342,10 @@ struct fbn_ci_ctx {
     std::vector<hipStream_t> streams_used;  // caller streams of fbn_ci_run (drained by fbn_ci_ctx_destroy)
     float last_ms = 0.f;
     bool timing = true;  // HIP events around every CI kernel (fbn_ci_set_kernel_timing)
+    // parameter learning (param_counts.hip): family descriptors, their columns / key strides, the
+    // 32-bit family tables (zeroed by every fbn_param_counts), fbn_param_set_tuning (0 = default)
+    DevBuf par_fam, par_col, par_str, par_tab;
+    int64_t par_slice = 0, par_lds = 0;
     ~fbn_ci_ctx();
     void destroy_() {
         if (h_open) (void)hipHostFree(h_open);
@@ -1321,7 +1326,9 @@ static int CiCreate(const uint8_t *cols, bool cols_on_device, int nvars, int64_t
     c->nvars = nvars;
     c->N = nsamples;
     c->dims.assign(dims, dims + nvars);
-    if ((rc = c->cols.ensure((size_t)nvars * nsamples))) return rc;
+    // 32 readable bytes past the last column: param_counts.hip reads a misaligned column as aligned
+    // dwords, up to 19 bytes past the column's last sample
+    if ((rc = c->cols.ensure((size_t)nvars * nsamples + 32))) return rc;
     if ((rc = c->ddims.ensure((size_t)nvars * 4))) return rc;
     if ((rc = c->stats.ensure(16))) return rc;
     FBN_HIP(hipMemcpy(c->cols.p, cols, (size_t)nvars * nsamples,
@@ -2059,6 +2066,115 @@ int fbn_ci_ctx_destroy(fbn_ci_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (hipStream_t s : c->streams_used) (void)hipStreamSynchronize(s);
     delete c;
+    return FBN_OK;
+}
+
+// ------------------------------------------------------------------ parameter learning
+int fbn_param_family_sizes(int nvars, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                           int64_t *family_off, int64_t *ncounts) {
+    return fbn::ParamFamilySizes(nvars, dims, parent_off, parents, family_off, ncounts);
+}
+
+int fbn_pdag_to_dag(int nvars, const int32_t *triples, int n, int32_t *parent_off, int32_t *parents) {
+    return fbn::PdagToDag(nvars, triples, n, parent_off, parents);
+}
+
+int fbn_param_set_tuning(fbn_ci_ctx *c, int64_t samples_per_slice, int64_t lds_cells_max) {
+    if (!c) return SetError(FBN_ERR_ARG, "null pointer");
+    if (samples_per_slice < 0) return SetError(FBN_ERR_ARG, "samples_per_slice = %lld is negative", (long long)samples_per_slice);
+    c->par_slice = samples_per_slice;
+    c->par_lds = lds_cells_max;
+    return FBN_OK;
+}
+
+int fbn_param_counts(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *parents, int64_t *counts, int64_t cap,
+                     int64_t *ncounts) {
+    if (!c || !parent_off) return SetError(FBN_ERR_ARG, "null pointer");
+    const int V = c->nvars;
+    // everything that can be refused is refused here, on the host, before any launch
+    std::vector<int64_t> foff((size_t)V + 1);
+    int64_t total = 0;
+    int rc = fbn::ParamFamilySizes(V, c->dims.data(), parent_off, parents, foff.data(), &total);
+    if (rc) return rc;
+    if (ncounts) *ncounts = total;
+    if (!counts) return FBN_OK;
+    if (cap < total) return SetError(FBN_ERR_ARG, "counts holds %lld cells, %lld needed", (long long)cap, (long long)total);
+    if (c->N >= (1ll << 31)) return SetError(FBN_ERR_LIMIT, "%lld samples: the device accumulators are 32-bit", (long long)c->N);
+    // slices: by default enough (family, slice) items for every CU to hold several workgroups, each
+    // slice at least 1024 samples (4 steps of the workgroup's 256 threads), a multiple of the 16
+    // samples a thread takes per step
+    int64_t slice = c->par_slice;
+    if (slice <= 0) {
+        const int64_t want = (16ll * c->num_cu + V - 1) / V;  // slices per family to aim for
+        const int64_t ns = std::max<int64_t>(1, std::min<int64_t>(want, c->N / 1024));
+        slice = ((c->N + ns - 1) / ns + kParamUnit - 1) / kParamUnit * kParamUnit;
+    }
+    const int64_t nslices = (c->N + slice - 1) / slice;
+    if ((int64_t)V * nslices > 0x7fffffffll)
+        return SetError(FBN_ERR_LIMIT, "%d families x %lld slices exceed one launch", V, (long long)nslices);
+    const int lds_max = c->par_lds == 0 ? kParamLdsCellsMax : (int)std::max<int64_t>(0, std::min<int64_t>(c->par_lds, kParamLdsCellsMax));
+    // family descriptors: the node's column first (stride = parent configurations), then its parents
+    // ascending, the last one fastest
+    std::vector<FbnParamFamily> fam((size_t)V);
+    std::vector<int32_t> fcol((size_t)parent_off[V] + V), fstr(fcol.size());
+    size_t lds_ints = 1;
+    for (int v = 0, o = 0; v < V; ++v) {
+        std::vector<int32_t> ps(parents + parent_off[v], parents + parent_off[v + 1]);
+        std::sort(ps.begin(), ps.end());
+        const int k = (int)ps.size();
+        const int64_t cells = foff[v + 1] - foff[v];
+        fam[v] = FbnParamFamily{(long long)foff[v], o, k + 1, (int32_t)cells, 0};
+        int64_t str = 1;
+        for (int j = k - 1; j >= 0; --j) {
+            fcol[o + 1 + j] = ps[j];
+            fstr[o + 1 + j] = (int32_t)str;
+            str *= c->dims[ps[j]];
+        }
+        fcol[o] = v;
+        fstr[o] = (int32_t)str;  // = cells / dims[v]
+        o += k + 1;
+        if (cells <= lds_max) lds_ints = std::max(lds_ints, fbn_param_lds_ints((int)cells));
+    }
+    FBN_HIP(hipSetDevice(c->device));
+    if ((rc = c->par_fam.ensure(fam.size() * sizeof(FbnParamFamily))) || (rc = c->par_col.ensure(fcol.size() * 4)) ||
+        (rc = c->par_str.ensure(fstr.size() * 4)) || (rc = c->par_tab.ensure((size_t)total * 4)))
+        return rc;
+    hipStream_t s = c->stream;
+    CiSlot &S = c->slot[0];
+    FBN_HIP(hipMemcpyAsync(c->par_fam.p, fam.data(), fam.size() * sizeof(FbnParamFamily), hipMemcpyHostToDevice, s));
+    FBN_HIP(hipMemcpyAsync(c->par_col.p, fcol.data(), fcol.size() * 4, hipMemcpyHostToDevice, s));
+    FBN_HIP(hipMemcpyAsync(c->par_str.p, fstr.data(), fstr.size() * 4, hipMemcpyHostToDevice, s));
+    if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
+    FBN_HIP(hipMemsetAsync(c->par_tab.p, 0, (size_t)total * 4, s));  // every call: no earlier call's counts
+    hipError_t e = fbn_param_launch(c->cols.as<uint8_t>(), c->N, c->par_fam.as<FbnParamFamily>(), V, c->par_col.as<int32_t>(),
+                                    c->par_str.as<int32_t>(), c->par_tab.as<uint32_t>(), slice, nslices, lds_max,
+                                    lds_ints * 4, s);
+    if (e != hipSuccess) return SetError(FBN_ERR_HIP, "param counts launch: %s", hipGetErrorString(e));
+    if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
+    std::vector<uint32_t> h((size_t)total);
+    FBN_HIP(hipMemcpyAsync(h.data(), c->par_tab.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+    FBN_HIP(hipStreamSynchronize(s));
+    c->last_ms = 0.f;
+    if (c->timing) FBN_HIP(hipEventElapsedTime(&c->last_ms, S.ev0, S.ev1));
+    for (int64_t i = 0; i < total; ++i) counts[i] = (int64_t)h[i];
+    return FBN_OK;
+}
+
+int fbn_param_learn(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *parents, const char *const *names,
+                    fbn_network **out) {
+    if (!c || !parent_off || !out) return SetError(FBN_ERR_ARG, "null pointer");
+    int64_t total = 0;
+    int rc = fbn_param_counts(c, parent_off, parents, nullptr, 0, &total);
+    if (rc) return rc;
+    // BuildNetwork's own limits first (1..127 states), so a graph it would refuse costs no launch
+    for (int v = 0; v < c->nvars; ++v)
+        if (c->dims[v] > 127) return SetError(FBN_ERR_LIMIT, "node %d has %d states (supported 1..127)", v, c->dims[v]);
+    std::vector<int64_t> counts((size_t)total);
+    if ((rc = fbn_param_counts(c, parent_off, parents, counts.data(), total, &total))) return rc;
+    auto h = std::unique_ptr<fbn_network>(new (std::nothrow) fbn_network());
+    if (!h) return SetError(FBN_ERR_NOMEM, "out of memory");
+    if ((rc = fbn::BuildNetwork(c->nvars, c->dims.data(), parent_off, parents, counts.data(), names, h->net))) return rc;
+    *out = h.release();
     return FBN_OK;
 }
 

@@ -33,6 +33,12 @@ int BuildNetwork(int n, const int32_t *dims, const int32_t *parent_off, const in
                  const char *const *names, Network &net);
 int NodeCounts(const Network &net, int v, int32_t *parents_asc, int64_t *counts, int *nparents, int64_t *ncounts);
 
+// parameter learning, host side (param_learn.cpp): family sizing / validation and the PDAG -> DAG
+// extension behind fbn_param_family_sizes / fbn_pdag_to_dag (no device, no other part of the library)
+int ParamFamilySizes(int nvars, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                     int64_t *family_off, int64_t *ncounts);
+int PdagToDag(int nvars, const int32_t *triples, int n, int32_t *parent_off, int32_t *parents);
+
 struct Dataset {
     int nvars = 0;
     int64_t nsamples = 0;

@@ -369,6 +369,57 @@ int fbn_pc_dist_destroy(fbn_pc_dist *s);
 int fbn_pc_device_bytes(const fbn_pc_result *r, int64_t *bytes);
 int fbn_pc_result_destroy(fbn_pc_result *r);
 
+/* ------------------------------------------------------------------ parameter learning
+ * The step between structure learning and inference: the count maps of every node of a DAG from
+ * the column store a context already holds.  Replaces ParameterLearning::LearnParamsKnowStructCompData
+ * (src/ParameterLearning.cpp:11-64), which calls DiscreteNode::AddInstanceOfVarVal / AddCount
+ * (src/DiscreteNode.cpp:100-145) once per node per sample.  A graph is given as CSR parent lists:
+ * node v's parents are parents[parent_off[v] .. parent_off[v+1]) in any order; node v's family table
+ * is int64 counts[value of v][parent configuration], configurations over the parents in ASCENDING
+ * index order, last fastest -- fbn_network_create's layout -- family after family in one array.
+ *
+ * Cap: one call counts at most FBN_PARAM_MAX_CELLS = 2^26 cells in all (256 MiB of 32-bit device
+ * accumulators, 512 MiB of int64 on the host); a family's cell count, or the sum, beyond that (or
+ * overflowing on the way there) is FBN_ERR_LIMIT, never a wrapped number. */
+#define FBN_PARAM_MAX_CELLS ((int64_t)1 << 26)
+
+/* Host-only sizing and validation of the families (the table shapes DiscreteNode::InitializeCPT
+ * enumerates, src/DiscreteNode.cpp:114-130): family_off[v] = first cell of node v's table,
+ * family_off[nvars] = *ncounts = total cells.  FBN_ERR_ARG for a parent out of range, a self parent
+ * or a repeated parent (and dims outside 1..256); FBN_ERR_LIMIT past the cap above. */
+int fbn_param_family_sizes(int nvars, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                           int64_t *family_off /* [nvars+1] or NULL */, int64_t *ncounts);
+/* Family counts of every node from the column store resident in c (AddCount over all samples,
+ * src/DiscreteNode.cpp:132-145; the sample loop of src/ParameterLearning.cpp:40-58): one launch for
+ * all families.  counts [cap] int64 on the host in the layout above; *ncounts = cells written.
+ * counts == NULL: sizes only.  cap < *ncounts: FBN_ERR_ARG.  The graph is validated on the host
+ * before anything is launched (errors as fbn_param_family_sizes); acyclicity is not required and
+ * any state count the context accepts is counted.  FBN_ERR_LIMIT for >= 2^31 samples (32-bit device
+ * accumulators).  Synchronous on the context's own stream; the device table is the context's and is
+ * zeroed by every call.  Kernel time (table zeroing + counting): fbn_ci_last_kernel_ms. */
+int fbn_param_counts(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *parents,
+                     int64_t *counts, int64_t cap, int64_t *ncounts);
+/* fbn_param_counts + fbn_network_create's BuildNetwork: the learned network (GetProbability's
+ * (count + 1) / (total + dims[v]), src/DiscreteNode.cpp:152-164, as every network here).  parents in
+ * the node's own order.  Inherits fbn_network_create's limits (1..127 states, the parent lists form
+ * a DAG) and error codes.  Replaces LearnParamsKnowStructCompData (src/ParameterLearning.cpp:11-64). */
+int fbn_param_learn(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *parents,
+                    const char *const *names, fbn_network **out);
+/* 0 = default.  Sample-slice length and the largest table counted in LDS (at most 8192 cells; larger
+ * values are clamped, a negative one sends every family to the global path): an explicit
+ * tuning/testing API (not an environment variable), so tests reach both paths and multi-slice
+ * merging at small N.  Replaces no reference interface. */
+int fbn_param_set_tuning(fbn_ci_ctx *c, int64_t samples_per_slice, int64_t lds_cells_max);
+/* Host-only: a consistent DAG extension of a PDAG (Dor & Tarsi 1992) -- the reference has no such
+ * step: its StructLearnCompData leaves the CPDAG of src/PCStable.cpp:576-843 and its parameter
+ * learner is only ever given a network file's DAG.  triples [n][3] as fbn_pc_oriented_edges writes
+ * them: (from, to, 1) arcs, (a, b, 0) undirected edges.  Repeatedly the lowest-index remaining node
+ * with no arc to a remaining node and whose undirected neighbours are each adjacent to all its other
+ * remaining neighbours takes its undirected edges as incoming and is removed (deterministic).
+ * parent_off [nvars+1], parents [n] ascending per node.  FBN_ERR_ARG naming the remaining nodes when
+ * none qualifies (no extension, or a directed cycle), and for a duplicate / contradictory edge. */
+int fbn_pdag_to_dag(int nvars, const int32_t *triples, int n, int32_t *parent_off, int32_t *parents /* cap n */);
+
 #ifdef __cplusplus
 }
 #endif
