@@ -12,6 +12,9 @@ reference's names and argument meaning:
   -- include/IndependenceTest.h:30-56
 * ``ParameterLearning(source).LearnParamsKnowStructCompData(parents)``
   -- src/ParameterLearning.cpp:11-64 (``pdag_to_dag`` turns PC-stable's CPDAG into its input)
+* ``LikelihoodWeighting(network, num_samples, seed, method="lw" | "pls").infer(evidence)``
+  -- the reference's ``-a 5`` / ``-a 4`` stubs (src/main.cpp:97-121); ``Sampler(network).forward_sample(n, seed)``
+  generates datasets on the device
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -24,6 +27,9 @@ from .api import (  # noqa: F401
     PCStable,
     PCResult,
     ParameterLearning,
+    Sampler,
+    LikelihoodWeighting,
+    score_marginals,
     family_sizes,
     pdag_to_dag,
     orient_skeleton,
@@ -37,5 +43,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
+           "Sampler", "LikelihoodWeighting", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

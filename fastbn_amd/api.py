@@ -107,6 +107,15 @@ _SIGS = {
     "fbn_param_learn": [_vp, _vp, _vp, _vp, _pp],
     "fbn_param_set_tuning": [_vp, _i64, _i64],
     "fbn_pdag_to_dag": [C.c_int, _vp, C.c_int, _vp, _vp],
+    "fbn_sampler_create": [_vp, C.c_int, _pp],
+    "fbn_sampler_destroy": [_vp],
+    "fbn_sample_forward": [_vp, _i64, C.c_uint64, _vp],
+    "fbn_sample_forward_device": [_vp, _i64, C.c_uint64, _vp, _vp],
+    "fbn_lw_run": [_vp, C.c_int, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp],
+    "fbn_lw_run_device": [_vp, C.c_int, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp, _vp],
+    "fbn_lw_debug_samples": [_vp, C.c_int, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp],
+    "fbn_sampler_last_kernel_ms": [_vp, _vp],
+    "fbn_score_marginals": [_vp, _vp, _vp, _i64, _vp, _vp],
 }
 
 
@@ -165,8 +174,8 @@ lib = _Lib()
 # Destroy order: results and sessions, then plans and contexts (they drain their device work),
 # then host-only handles.
 _LIVE = weakref.WeakSet()
-_CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "IndependenceTest": 3, "Dataset": 4,
-                "Network": 5}
+_CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
+                "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
 def _register(obj):
@@ -829,3 +838,103 @@ class ParameterLearning:
 
     def last_kernel_ms(self):
         return self.ci.last_kernel_ms()
+
+
+def score_marginals(network, marginals, golden):
+    """fbn_score_marginals: (mse_sum, hd_sum) of marginals [n][sum_dom] against a golden table, as
+    JunctionTree.score computes them, from the network alone (no plan)."""
+    m = np.ascontiguousarray(marginals, np.float64)
+    g = np.ascontiguousarray(golden, np.float64)
+    mse, hd = C.c_double(), C.c_double()
+    lib.fbn_score_marginals(network._h, _p(m), _p(g), m.shape[0], C.byref(mse), C.byref(hd))
+    return mse.value, hd.value
+
+
+class Sampler(_Handle):
+    """The sampling engine of one network on one device (fbn_sampler).  device < 0: the host path,
+    the same algorithm on CPU threads (bit-identical results)."""
+
+    _destroy = "fbn_sampler_destroy"
+
+    def __init__(self, network, device=0):
+        self.network = network
+        h = C.c_void_p()
+        lib.fbn_sampler_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def forward_sample(self, n, seed):
+        """n complete cases, uint8 [V][n]; = Network.forward_sample(n, seed) = synth.forward_sample."""
+        cols = np.empty((self.network.num_nodes, int(n)), np.uint8)
+        lib.fbn_sample_forward(self._h, int(n), int(seed), _p(cols))
+        return cols
+
+    def forward_sample_device(self, d_cols_ptr, n, seed, stream_ptr=None):
+        """The same into a device buffer uint8 [V][n] (e.g. IndependenceTest.from_device's input);
+        asynchronous on the stream."""
+        lib.fbn_sample_forward_device(self._h, int(n), int(seed), C.c_void_p(d_cols_ptr), stream_ptr)
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_sampler_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+
+class LikelihoodWeighting(Sampler):
+    """Sampling inference, mirroring JunctionTree: likelihood weighting (method="lw", the reference's
+    -a 5) or probabilistic logic sampling ("pls", -a 4) with num_samples samples per case (-q).
+    Works on any DAG, a disconnected learned network included."""
+
+    _METHODS = {"lw": 0, "pls": 1}
+
+    def __init__(self, network, num_samples=10000, seed=0, device=0, method="lw"):
+        if method not in self._METHODS:
+            raise FastBNError(f"method {method!r}: 'lw' or 'pls'")
+        super().__init__(network, device)
+        self.num_samples, self.seed, self.method = int(num_samples), int(seed), self._METHODS[method]
+        self.sum_dom = int(np.sum(network.dims))
+        self.stats = None
+
+    def infer(self, evidence, marginals=True, case_offset=0):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
+        self.stats = (log_evidence, ess) per case.  case_offset: the global index of the first case
+        (a batch split over calls gives the bits of the whole batch)."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        labels = np.zeros(n, np.int32)
+        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
+        st = np.zeros((n, 2), np.float64)
+        lib.fbn_lw_run(self._h, self.method, _p(ev), n, self.num_samples, self.seed, int(case_offset), _p(labels),
+                       _p(marg), _p(st))
+        self.stats = (st[:, 0].copy(), st[:, 1].copy())
+        return labels, marg
+
+    def run_device(self, d_evidence_ptr, ncases, d_labels_ptr, d_marg_ptr, d_stats_ptr=None, case_offset=0,
+                   stream_ptr=None):
+        """Device-resident run (asynchronous on the stream after the evidence check)."""
+        lib.fbn_lw_run_device(self._h, self.method, C.c_void_p(d_evidence_ptr), int(ncases), self.num_samples,
+                              self.seed, int(case_offset), C.c_void_p(d_labels_ptr),
+                              C.c_void_p(d_marg_ptr) if d_marg_ptr else None,
+                              C.c_void_p(d_stats_ptr) if d_stats_ptr else None, stream_ptr)
+
+    def debug_samples(self, evidence, case_offset=0):
+        """The samples behind infer(evidence): (values uint8 [V][ncases * S], mantissas fp64,
+        exponents int32 [ncases * S]); sample s of case c at c * S + s."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        tot = n * self.num_samples
+        vals = np.zeros((self.network.num_nodes, tot), np.uint8)
+        m = np.zeros(tot, np.float64)
+        e = np.zeros(tot, np.int32)
+        lib.fbn_lw_debug_samples(self._h, self.method, _p(ev), n, self.num_samples, self.seed, int(case_offset),
+                                 _p(vals), _p(m), _p(e))
+        return vals, m, e
+
+    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
+        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
+        labels, marg = self.infer(evidence)
+        acc = float(np.mean(labels == np.asarray(ground_truths)))
+        if golden is None:
+            return acc
+        mse, hd = score_marginals(self.network, marg, golden)
+        return acc, mse / len(labels), hd / len(labels)

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "fbn_internal.h"
+#include "sample_model.h"
 #include "pc_internal.h"
 #include "ci_chisq.h"
 #include "pc_small.h"
@@ -1228,38 +1229,7 @@ int fbn_jt_run(fbn_jt_plan *p, const int8_t *evidence, int64_t ncases, int32_t *
 int fbn_jt_score(const fbn_jt_plan *p, const double *marginals, const double *golden, int64_t ncases, double *mse_sum,
                  double *hd_sum) {
     if (!p || !marginals || !golden || !mse_sum || !hd_sum) return SetError(FBN_ERR_ARG, "null pointer");
-    const auto &dom = p->host.dom;
-    const int SD = p->prog.sum_dom;
-    auto round7 = [](double number) {  // Round(x, 7), src/Inference.cpp:195-206
-        long long integerpart = (long long)number;
-        number -= integerpart;
-        for (int i = 0; i < 7; ++i) number *= 10;
-        number = (double)(long long)(number + 0.5);
-        for (int i = 0; i < 7; ++i) number /= 10;
-        return integerpart + number;
-    };
-    double mse = 0.0, hd = 0.0;
-    for (int64_t c = 0; c < ncases; ++c) {  // CalculateMSE / CalculateHellingerDistance (:153-193)
-        const double *a = marginals + c * SD, *x = golden + c * SD;
-        int num = 0, off = 0;
-        double e1 = 0.0, e2 = 0.0;
-        for (size_t v = 0; v < dom.size(); ++v) {
-            if (x[off] > 0) {
-                num += dom[v];
-                for (int j = 0; j < dom[v]; ++j) {
-                    double r = round7(a[off + j]);
-                    e1 += pow(r - x[off + j], 2);
-                    e2 += pow(sqrt(r) - sqrt(x[off + j]), 2);
-                }
-            }
-            off += dom[v];
-        }
-        mse += sqrt(e1 / num);
-        hd += sqrt(e2 / num);
-    }
-    *mse_sum = mse;
-    *hd_sum = hd;
-    return FBN_OK;
+    return fbn::ScoreMarginals(p->host.dom, marginals, golden, ncases, mse_sum, hd_sum);  // sample_host.cpp
 }
 
 int fbn_jt_set_output_layout(fbn_jt_plan *p, int layout) {

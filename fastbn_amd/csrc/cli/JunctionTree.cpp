@@ -42,13 +42,12 @@ JunctionTree::JunctionTree(fbn_network *net, TestSet *tester, int device, int gp
 
 JunctionTree::~JunctionTree() { fbn_jt_plan_destroy(plan_); }
 
-double JunctionTree::EvaluateAccuracy(const std::string &pt_path, int /*num_threads*/) {
-    const int64_t n = tester_->num_instances();
-    const int V = info_.num_nodes, SD = info_.sum_dom;
-    std::vector<int32_t> dims(V);
-    fbn_network_dims(net_, dims.data());
-    // LoadGroundTruthProbabilityTable (src/Inference.cpp:108-146): one line per (case, node),
-    // empty line = evidence node (first entry marked -1)
+// LoadGroundTruthProbabilityTable (src/Inference.cpp:108-146): one line per (case, node),
+// empty line = evidence node (first entry marked -1)
+std::vector<double> LoadGroundTruth(const std::string &pt_path, const std::vector<int32_t> &dims, int64_t n) {
+    const int V = (int)dims.size();
+    int SD = 0;
+    for (int d : dims) SD += d;
     std::vector<double> golden((size_t)n * SD, 0.0);
     std::ifstream in(pt_path);
     if (!in.is_open()) {
@@ -77,6 +76,15 @@ double JunctionTree::EvaluateAccuracy(const std::string &pt_path, int /*num_thre
             off += dims[v];
         }
     }
+    return golden;
+}
+
+double JunctionTree::EvaluateAccuracy(const std::string &pt_path, int /*num_threads*/) {
+    const int64_t n = tester_->num_instances();
+    const int V = info_.num_nodes, SD = info_.sum_dom;
+    std::vector<int32_t> dims(V);
+    fbn_network_dims(net_, dims.data());
+    std::vector<double> golden = LoadGroundTruth(pt_path, dims, n);
     std::cout << "==================================================" << '\n'
               << "Begin testing the trained network." << std::endl;
     auto t0 = std::chrono::steady_clock::now();

@@ -17,6 +17,10 @@ struct TestSet {  // what Dataset::LoadLIBSVMDataKnownNetwork + Inference ctor e
     int Load(const std::string &path, int num_nodes);
 };
 
+// LoadGroundTruthProbabilityTable (src/Inference.cpp:108-146) -> golden [n][sum_dom], the first entry of an
+// evidence node marked -1; exits as the reference does when the file cannot be opened
+std::vector<double> LoadGroundTruth(const std::string &pt_path, const std::vector<int32_t> &dims, int64_t n);
+
 class JunctionTree {
 public:
     // gpus > 1: the cases are sharded over devices device .. device + gpus - 1 (RCCL, MultiGpu.h)

@@ -1,12 +1,14 @@
-// main.cpp -- drop-in for `./BayesianNetwork -a 0|2 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
-// same flags, defaults and "../dataset/" path prefix; -a 0 (PC-stable) and -a 2 (junction tree)
-// run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL: MultiGpu.h),
-// --depth D (PC-stable max depth, reference default 1000).
+// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
+// same flags, defaults and "../dataset/" path prefix; -a 0 (PC-stable), -a 2 (junction tree), -a 4
+// (probabilistic logic sampling) and -a 5 (likelihood weighting; -q samples per case, the reference's
+// default 10000) run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL:
+// MultiGpu.h), --depth D (PC-stable max depth, reference default 1000), --seed N (sampling seed, 0).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "JunctionTree.h"
 #include "PCStable.h"
@@ -14,6 +16,8 @@
 
 int main(int argc, char **argv) {
     int algorithm = 2, num_threads = 1, group_size = 1, device = 0, depth = 1000, gpus = 1;
+    long long num_samples = 10000;
+    unsigned long long seed = 0;
     std::string net_file = "alarm/alarm.xml", ref_net_file = "alarm/alarm.bif",
                 train_set_file = "alarm/alarm_s5000.txt", test_set_file = "alarm/testing_alarm_1k_p20",
                 pt_file = "alarm/alarm_1k_pt", prefix = "../dataset/";
@@ -24,15 +28,18 @@ int main(int argc, char **argv) {
         if (a == "--gpus" && i + 1 < argc) { gpus = atoi(argv[++i]); continue; }
         if (a == "--depth" && i + 1 < argc) { depth = atoi(argv[++i]); continue; }
         if (a == "--prefix" && i + 1 < argc) { prefix = argv[++i]; continue; }
+        if (a == "--seed" && i + 1 < argc) { seed = strtoull(argv[++i], nullptr, 10); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2] [-t threads] [-g group] [-f0 net] [-f1 refnet] "
-                         "[-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--prefix DIR]" << std::endl;
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5] [-t threads] [-g group] [-q samples] [-f0 net] [-f1 refnet] "
+                         "[-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] [--prefix DIR]"
+                      << std::endl;
             return 0;
         case 'a': algorithm = atoi(argv[++i]); break;
         case 't': num_threads = atoi(argv[++i]); break;
         case 'g': group_size = atoi(argv[++i]); break;
-        case 'q': case 'm': case 'l': case 'd': ++i; break;  // sampling-algorithm flags: accepted
+        case 'q': num_samples = atoll(argv[++i]); break;
+        case 'm': case 'l': case 'd': ++i; break;  // flags of the other sampling algorithms: accepted
         case 'f':
             switch (argv[i][2]) {
             case '0': net_file = argv[++i]; break;
@@ -95,8 +102,59 @@ int main(int argc, char **argv) {
         }
         std::cout << "accuracy = " << accuracy << std::endl;
         fbn_network_destroy(net);
+    } else if (algorithm == 4 || algorithm == 5) {
+        // the reference's PLS / LW stubs (src/main.cpp:97-121): its header lines, then -a 2's result lines
+        std::cout << "===============================" << std::endl
+                  << (algorithm == 4 ? "Algorithm: probabilistic logic sampling (PLS) for approximate inference, #threads = "
+                                     : "Algorithm: likelihood weighting (LW) for approximate inference, #threads = ")
+                  << num_threads << std::endl
+                  << "#samples = " << num_samples << std::endl
+                  << "\tBN: " << net_file << std::endl
+                  << "\ttesting set: " << test_set_file << std::endl
+                  << "\treference potential table: " << pt_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        fbn_network *net = nullptr;
+        if (fbn_network_load_xmlbif(net_file.c_str(), &net)) return die();
+        int n = 0;
+        fbn_network_num_nodes(net, &n);
+        TestSet tester;
+        if (tester.Load(test_set_file, n)) return die();
+        const int64_t nc = tester.num_instances();
+        std::vector<int32_t> dims(n);
+        fbn_network_dims(net, dims.data());
+        int sum_dom = 0;
+        for (int d : dims) sum_dom += d;
+        std::vector<double> golden = LoadGroundTruth(pt_file, dims, nc);
+        std::cout << "==================================================" << '\n'
+                  << "Begin testing the trained network." << std::endl;
+        fbn_sampler *smp = nullptr;
+        if (fbn_sampler_create(net, device, &smp)) return die();
+        std::vector<int32_t> predictions((size_t)nc);
+        std::vector<double> marginals((size_t)nc * sum_dom);
+        if (fbn_lw_run(smp, algorithm == 4 ? 1 : 0, tester.evidence.data(), nc, num_samples, seed, 0, predictions.data(),
+                       marginals.data(), nullptr))
+            return die();
+        float kms = 0.f;
+        const bool timed = fbn_sampler_last_kernel_ms(smp, &kms) == 0;  // not on the host path (--device -1)
+        double mse = 0, hd = 0;
+        if (fbn_score_marginals(net, marginals.data(), golden.data(), nc, &mse, &hd)) return die();
+        int64_t correct = 0;
+        for (int64_t c = 0; c < nc; ++c) correct += predictions[c] == tester.ground_truths[c];
+        std::cout << "average MSE = " << mse / nc << std::endl;
+        std::cout << "average HD = " << hd / nc << std::endl;
+        std::cout << "==================================================" << std::endl;
+        if (timed)
+            std::cout << (algorithm == 4 ? "pls: " : "lw: ") << "device kernel " << kms * 1e-3 << " s, "
+                      << (double)nc * (double)num_samples / (kms * 1e-3) << " samples/s" << std::endl;
+        std::cout << "accuracy = " << correct / (double)nc << std::endl;
+        fbn_sampler_destroy(smp);
+        fbn_network_destroy(net);
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0 and -a 2)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4 and 5)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

@@ -57,6 +57,11 @@ int EvidenceCases(const Network &net, int64_t n, int k, uint64_t seed, int query
 int WriteCsv(const std::string &path, const uint8_t *cols, int nvars, int64_t n, const std::vector<std::string> &names,
              const std::vector<std::vector<std::string>> &values);
 int WriteLibsvm(const std::string &path, const int8_t *ev, int64_t n, int V, const int32_t *labels);
+// the pieces of those generators the sampling engine (sample_host.cpp, sample.hip) is held to: the
+// topological order (Kahn, LIFO stack, children ascending; shorter than n() for a cyclic graph) and
+// numpy's PCG64(seed) after seeding, state and increment as (hi, lo) 64-bit halves
+std::vector<int> TopoOrder(const Network &net);
+void Pcg64Seed(uint64_t seed, uint64_t state[2], uint64_t inc[2]);
 
 // ---------------------------------------------------------------------------------------------
 // junction-tree static plan (host), container order as in JunctionTreeStructure

@@ -103,6 +103,15 @@ struct Pcg64 {
     double random() { return (double)(next64() >> 11) * (1.0 / 9007199254740992.0); }
 };
 
+}  // namespace
+
+// the seeded generator's state after PCG64(seed)'s constructor, as (hi, lo) halves (sample_host.cpp)
+void Pcg64Seed(uint64_t seed, uint64_t state[2], uint64_t inc[2]) {
+    const Pcg64 g(seed);
+    state[0] = (uint64_t)(g.state >> 64), state[1] = (uint64_t)g.state;
+    inc[0] = (uint64_t)(g.inc >> 64), inc[1] = (uint64_t)g.inc;
+}
+
 // synth.py _topo: Kahn's algorithm with a LIFO stack, children in ascending order
 std::vector<int> TopoOrder(const Network &net) {
     const int n = net.n();
@@ -127,6 +136,8 @@ std::vector<int> TopoOrder(const Network &net) {
     }
     return order;
 }
+
+namespace {
 
 int GenThreads() {
     const unsigned hc = std::thread::hardware_concurrency();

@@ -420,6 +420,76 @@ int fbn_param_set_tuning(fbn_ci_ctx *c, int64_t samples_per_slice, int64_t lds_c
  * none qualifies (no extension, or a directed cycle), and for a duplicate / contradictory edge. */
 int fbn_pdag_to_dag(int nvars, const int32_t *triples, int n, int32_t *parent_off, int32_t *parents /* cap n */);
 
+/* ------------------------------------------------------------------ sampling engine
+ * Forward (ancestral) sampling and the two sampling inference algorithms the reference's CLI
+ * advertises but only answers "under development" for: probabilistic logic sampling (-a 4) and
+ * likelihood weighting (-a 5), -q samples per case (src/main.cpp:97-121, include/Parameter.h:16-17,30).
+ * A sampler needs only a topological order and the CPTs, so it runs where fbn_jt_plan_create refuses
+ * (a disconnected moral graph, e.g. the network PC-stable learns from ALARM-5000).
+ *
+ * Random stream: numpy's PCG64(seed); the draw of the k-th variable in topological order (Kahn, LIFO
+ * stack, children ascending -- fbn_synth_forward_sample's order) for sample i sits at stream position
+ *   k * n + i                                  forward sampling (n = the call's sample count),
+ *   i * V + k,  i = (case_offset + c) * S + s  inference (case c of the call, sample s of S, V variables),
+ * every variable consuming its position whether or not its draw is used.  Under the inference map a
+ * case's result depends on (seed, case_offset + c, S) only: a batch split over calls or devices with
+ * case_offset gives the same bits.  Values by fbn_synth_forward_sample's rule (x = u * cdf[d - 1],
+ * value = min(#{q : x >= cdf[q]}, d - 1)) on fp64 cdf rows of the parent configuration.
+ *
+ * Limits: at most 2048 variables (one wave keeps its 64 samples' values as bytes [V][64] in LDS)
+ * and FBN_PARAM_MAX_CELLS table cells in all, else FBN_ERR_LIMIT; a cyclic network is FBN_ERR_ARG. */
+typedef struct fbn_sampler fbn_sampler;
+/* Flatten the network (order, parent lists in GIVEN order, fp64 probability and cdf tables built
+ * with the (count + 1) / (total + |dom|) convention) and upload it to `device` once.  device < 0: a
+ * host-only sampler that runs the same algorithm, chunk for chunk, on CPU threads (bit-identical
+ * values, weights and sums); its *_device entries return FBN_ERR_NODEV. */
+int fbn_sampler_create(const fbn_network *net, int device, fbn_sampler **out);
+int fbn_sampler_destroy(fbn_sampler *s);
+/* n complete cases, cols [V][n] uint8 (the column store layout), bit-identical to
+ * fbn_synth_forward_sample(net, n, seed, cols).  Replaces the reference's wall-clock seeded
+ * SampleSetGenerator (src/SampleSetGenerator.cpp) as the workload generator; the _device form writes
+ * a device buffer (e.g. the input of fbn_ci_dataset_from_device) and is asynchronous on hip_stream. */
+int fbn_sample_forward(fbn_sampler *s, int64_t n, uint64_t seed, uint8_t *cols);
+int fbn_sample_forward_device(fbn_sampler *s, int64_t n, uint64_t seed, uint8_t *d_cols, void *hip_stream);
+/* Sampling inference of ncases evidence cases with S >= 1 samples each (the reference's -q).
+ * evidence [ncases][V] int8, -1 = unobserved, every code -1 or < the node's state count (checked
+ * before anything indexes with it: FBN_ERR_ARG naming the first bad case / node).
+ * method 0, likelihood weighting (-a 5): in topological order an observed variable takes its evidence
+ *   value and multiplies P(v = ev | parents) into the sample's weight, kept as a scaled pair (m, e)
+ *   from (1.0, 0): (m, de) = frexp(m * P), e += de -- exact power-of-two scaling, so hundreds of
+ *   observed variables do not underflow and (m, e) is reproducible bit for bit.
+ * method 1, probabilistic logic sampling (-a 4): every variable is sampled; m becomes 0 when an
+ *   observed variable's sample differs from its evidence, e stays 0.
+ * Per case, with emax = max_s e_s, w_s = ldexp(m_s, e_s - emax) and sumw = sum_s w_s:
+ *   marginals [ncases][sum_dom] fp64 (or NULL) = sum_s w_s [x_v = q] / sumw, zeros for an observed
+ *     variable (fbn_jt_run's convention);
+ *   labels [ncases] = arg-max of variable 0's row (strict '>' from state 0, as fbn_jt_run);
+ *   stats [ncases][2] fp64 (or NULL) = log_evidence = log(sumw / S) + emax ln 2, and the effective
+ *     sample size sumw^2 / sum_s w_s^2.
+ * A case no sample of which is accepted (sumw == 0, method 1 only) gets a row of zeros, label -1,
+ * log_evidence -inf and ess 0, never a NaN.  All sums are taken in one fixed order (64-sample
+ * chunks of one wave, no floating-point atomics): two runs, and any split by case_offset, agree
+ * bitwise.  Replaces the PLS / LW stubs of src/main.cpp:97-121.  Host arrays, synchronous. */
+int fbn_lw_run(fbn_sampler *s, int method, const int8_t *evidence, int64_t ncases, int64_t S, uint64_t seed,
+               int64_t case_offset, int32_t *labels, double *marginals, double *stats);
+/* The same with device-resident buffers; asynchronous on hip_stream after the evidence check (one
+ * stream sync, as fbn_jt_run_device's).  d_marginals == NULL: labels (and stats) only. */
+int fbn_lw_run_device(fbn_sampler *s, int method, const int8_t *d_evidence, int64_t ncases, int64_t S, uint64_t seed,
+                      int64_t case_offset, int32_t *d_labels, double *d_marginals, double *d_stats, void *hip_stream);
+/* Testing interface (an explicit API, not an environment variable): the samples behind fbn_lw_run
+ * for a small batch (ncases * S <= 2^22): values [V][ncases * S] uint8, mantissas fp64 and
+ * exponents int32 [ncases * S], sample s of case c at index c * S + s.  Host arrays.  Replaces no
+ * reference interface. */
+int fbn_lw_debug_samples(fbn_sampler *s, int method, const int8_t *evidence, int64_t ncases, int64_t S, uint64_t seed,
+                         int64_t case_offset, uint8_t *values, double *mantissas, int32_t *exponents);
+/* Device kernel time (ms, hipEvent) of the sampler's last launch. */
+int fbn_sampler_last_kernel_ms(const fbn_sampler *s, float *ms);
+/* fbn_jt_score's sums (CalculateMSE / CalculateHellingerDistance with Round(., 7),
+ * src/Inference.cpp:153-206) from the network's state counts alone: no plan needed, so marginals of
+ * a network no junction tree can be built for are scored the same way, bit for bit. */
+int fbn_score_marginals(const fbn_network *net, const double *marginals, const double *golden, int64_t ncases,
+                        double *mse_sum, double *hd_sum);
+
 #ifdef __cplusplus
 }
 #endif
