@@ -55,6 +55,7 @@ _SIGS = {
     "fbn_jt_kernel_cache_path": [_vp, C.c_char_p, C.c_int64],
     "fbn_jt_kernel_options": [C.c_char_p, C.c_int64],
     "fbn_jt_kernel_build": [_vp],
+    "fbn_jt_kernel_placement": [_vp, _vp],
     "fbn_jt_debug_force_fixup": [_vp, C.c_int],
     "fbn_jt_debug_flagged_blocks": [_vp, _vp],
     "fbn_jt_set_exact": [_vp, C.c_int],
@@ -453,6 +454,13 @@ class JunctionTree(_Handle):
         info = _PlanInfo()
         lib.fbn_jt_plan_info_get(self._h, C.byref(info))
         self.info = {k: getattr(info, k) for k, _ in _PlanInfo._fields_}
+        if self.info["specialized_eligible"]:
+            # where the specialized kernel of the current order / layout keeps its message rows
+            rows = np.zeros(8, np.int64)
+            lib.fbn_jt_kernel_placement(self._h, _p(rows))
+            names = ("global_collect", "global_distribute", "lds_collect", "lds_distribute", "reg_collect",
+                     "reg_distribute", "workspace", "lds_pool")
+            self.info.update({"place_rows_" + k: int(v) for k, v in zip(names, rows)})
         return self.info
 
     def set_variant(self, v):

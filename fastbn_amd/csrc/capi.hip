@@ -876,6 +876,21 @@ int fbn_jt_kernel_cache_path(const fbn_jt_plan *p, char *buf, int64_t cap) {
     return FBN_OK;
 }
 
+int fbn_jt_kernel_placement(const fbn_jt_plan *p, int64_t *rows) {
+    if (!p || !rows) return SetError(FBN_ERR_ARG, "null pointer");
+    if (!p->gen_eligible) return SetError(FBN_ERR_ARG, "plan not eligible for codegen");
+    std::string src;
+    std::vector<double> iv;
+    int64_t we = 0;
+    fbn::JTPlacement pl;
+    int rc = fbn::GenerateJTKernel(p->host, src, &we, iv, nullptr, JtFast(p), p->out_layout == 1, &pl);
+    if (rc) return rc;
+    const int64_t r[8] = {pl.global[0], pl.global[1], pl.lds[0], pl.lds[1],
+                          pl.reg[0], pl.reg[1], pl.workspace_rows, pl.lds_pool_rows};
+    std::copy(r, r + 8, rows);
+    return FBN_OK;
+}
+
 int fbn_jt_set_exact(fbn_jt_plan *p, int exact) {
     if (!p || exact < -1 || exact > 1) return SetError(FBN_ERR_ARG, "exact must be -1 (auto), 0 (fast) or 1 (exact)");
     p->exact = exact;

@@ -155,8 +155,15 @@ bool JTCodegenEligible(const JTPlanHost &plan, int64_t *entry_ops);
 // fast: the fast arithmetic order (normalizations that cancel are left out; results within 1e-12 of
 // the exact order, which repeats the reference's every multiply + Normalize); var_major: marginals
 // stored variable-major [sum_dom][ncases] instead of case-major [ncases][sum_dom]
+// message rows (64 lanes x fp64 each) of the generated kernel per place, [0] Collect, [1] Distribute
+struct JTPlacement {
+    int64_t global[2] = {0, 0}, lds[2] = {0, 0}, reg[2] = {0, 0};
+    int64_t workspace_rows = 0;  // global rows per wave (a separator's two messages share theirs)
+    int64_t lds_pool_rows = 0;   // LDS pool rows per wave (the most in use at one time)
+};
 int GenerateJTKernel(const JTPlanHost &plan, std::string &src, int64_t *wave_entries, std::vector<double> &initv,
-                     int64_t *lds_bytes = nullptr, bool fast = false, bool var_major = false);
+                     int64_t *lds_bytes = nullptr, bool fast = false, bool var_major = false,
+                     JTPlacement *placement = nullptr);
 
 }  // namespace fbn
 

@@ -13,7 +13,8 @@
 // parent's -- so any children-first / parent-first traversal gives the same bits):
 //  * Collect in DFS post-order: the last child's message stays in registers for its parent; other
 //    messages are stored (they are needed again anyway as the "old" separator of Distribute) --
-//    in LDS pool rows when their live interval fits, else in the per-wave rows in global memory.
+//    in registers the small cliques leave unused (fast order), in LDS pool rows when their live
+//    interval fits, else in the per-wave rows in global memory (PlaceMessages).
 //  * Distribute in DFS pre-order: a clique's Collect table is not parked and reloaded but
 //    recomputed from its initial potential and its children's stored messages (which Distribute
 //    loads anyway) -- ALU is cheap here, HBM round trips are not.  The message to the first child
@@ -76,6 +77,7 @@ class JTGen {
     int Run(std::string &src, int64_t *wave_entries, std::vector<double> &initv);
     int64_t lds_rows = 0;  // LDS rows (64 lanes x fp64) per wave: the clique tail
     int64_t pool_rows = 0;  // + LDS rows of the message pool (after the tail, before the initial potentials)
+    JTPlacement place;  // message rows per place (PlaceMessages)
     // initial potentials: scalar loads from the constant buffer (round 5 default; 1 = an LDS copy per
     // wave, which takes LDS from the message pool: ALARM 0.163 vs 0.141 ms)
     bool iv_lds = false;
@@ -148,7 +150,21 @@ class JTGen {
         }
         o << "        }\n";
     }
-    void PlaceMessages(const std::vector<int> &post, const std::vector<int> &pre, int64_t budget);
+    void PlaceMessages(const std::vector<int> &post, const std::vector<int> &pre, int64_t budget, int64_t reg_cap,
+                       bool quiet);
+    // register pool: fp64 values per lane of one wave per SIMD (512 registers), the part left to
+    // the compiler's temporaries, and the default cap on parked rows (FBN_JT_REG_POOL; 0 = off;
+    // kRegFile = bounded only by what the ops leave free).  ALARM, 100k cases, variable-major:
+    // slack 16 parks 123 rows, 231 -> 128 message rows in global memory, no spill, 0.1166 ->
+    // 0.1027 ms; slack 0 / 32 (42 / 2 spilled registers) 0.111 / 0.110 ms, caps 32 / 64 0.111 /
+    // 0.1026 ms.  The case-major kernel (64-bit output addresses: more registers of its own) spills
+    // at slack 16 (0.1218 -> 0.1272 ms); slack 28 / 32 / 36 / 48: 0.1179 / 0.1167 / 0.1176 / 0.1188 ms,
+    // but every one of them spills 42-44 SGPRs against 34 without the pool, so there the pool is
+    // opt-in
+    static constexpr int64_t kRegFile = 256, kRegSlackVM = 16, kRegSlackCM = 32, kDefaultRegPool = kRegFile;
+    int64_t peak_need = 0;  // the largest register need of an op itself, over the schedule
+    std::vector<int64_t> reg_extra;  // parked rows live at time t beyond what op t holds itself
+    std::vector<std::string> reg_names;  // the parked entries' registers (declared per block)
     std::string B(int k) const {
         return profile ? "        FBN_OP_BOUNDARY(); FBN_STAMP(" + std::to_string(k) + ");\n" : "        FBN_OP_BOUNDARY();\n";
     }
@@ -602,8 +618,11 @@ void JTGen::ChooseMarginalSources(const std::vector<int> &pre) {
 // get pool rows by interval: shortest intervals first while the pool has room at every time of
 // the interval, rows then assigned in start order (an interval graph: the room suffices).  The
 // rest keep global rows (Collect and Distribute message of a separator in the same rows, as
-// before).  FBN_JT_LDS_POOL=n caps the pool at n rows (0: off).
-void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &pre, int64_t budget) {
+// before).  FBN_JT_LDS_POOL=n caps the pool at n rows (0: off).  Before the LDS pool, the fast order
+// parks message entries in registers the small cliques leave unused (reg_cap rows at most, 0: off);
+// a message may be split: its leading entries in registers, the others in one of the two memories.
+void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &pre, int64_t budget, int64_t reg_cap,
+                          bool quiet) {
     const int nc = (int)plan.cliques.size(), ns = (int)plan.seps.size();
     auto tsize = [&](int c) { return plan.cliques[c].size(); };
     std::vector<int> pi(nc), qi(nc);
@@ -641,26 +660,120 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
         else if (col_store[s]) items.push_back({s, false, qi[c], qi[p], plan.seps[s].size()});
         if (!md_reg[s]) items.push_back({s, true, nc + pi[p], nc + pi[c], plan.seps[s].size()});
     }
+    std::vector<int> order(items.size());
+    for (size_t i = 0; i < items.size(); ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+        return items[x].b - items[x].a < items[y].b - items[y].a;
+    });
+    // Register pool (fast order, FBN_JT_REG_POOL): the leading nreg[i] entries of message i stay in
+    // named registers for its whole interval.  An op needs its table (the register-resident part)
+    // and the messages it loads, prefetches or keeps (need[t], the same rules Run emits by); what
+    // is left of the 256 fp64 values per lane, less a slack for temporaries, may hold parked rows
+    // at that time.  A message is checked at its producer (which would otherwise store each entry
+    // as it is formed) and at every op before its consumer; an op that loads it on the way anyway
+    // (the parent's Collect of a message parked until the parent's Distribute, a prefetch) pays
+    // nothing extra for it.
+    std::vector<int64_t> nreg(items.size(), 0);
+    reg_extra.assign(2 * nc + 1, 0);
+    if (reg_cap > 0) {
+        auto kids_rows = [&](int c) {
+            int64_t r = 0;
+            for (int s : plan.clique_down[c]) r += plan.seps[s].size();
+            return r;
+        };
+        auto early_lb = [&](int c) {
+            const int64_t held = (c != plan.root) ? plan.seps[plan.clique_up[c]].size() : 0;
+            return tsize(c) + kids_rows(c) + held <= budget;
+        };
+        std::vector<int64_t> need(2 * nc + 1, 0);
+        std::vector<std::vector<int>> touch(2 * nc + 1);  // messages op t holds anyway: 2 * s + dist
+        for (int k = 0; k < nc; ++k) {  // Collect
+            const int c = post[k];
+            need[k] = std::min<int64_t>(tsize(c), kRegEntries) + kids_rows(c);
+            int64_t mine = 0;
+            for (int s : plan.clique_down[c]) {
+                touch[k].push_back(2 * s);
+                if (!(k > 0 && child(s) == post[k - 1])) mine += plan.seps[s].size();
+            }
+            if (k + 1 < nc) {
+                const int nx = post[k + 1];
+                int64_t next = 0;
+                for (int s : plan.clique_down[nx])
+                    if (child(s) != c) next += plan.seps[s].size();
+                if (tsize(c) + mine + next <= budget) {
+                    need[k] += next;
+                    for (int s : plan.clique_down[nx])
+                        if (child(s) != c) touch[k].push_back(2 * s);
+                }
+            }
+        }
+        for (int k = 0; k < nc; ++k) {  // Distribute
+            const int c = pre[k], up = plan.clique_up[c], t = nc + k;
+            const bool early = early_lb(c);
+            int64_t kmax = 0, pend = early ? kids_rows(c) : 0;
+            for (int s : plan.clique_down[c]) {
+                kmax = std::max<int64_t>(kmax, plan.seps[s].size());
+                touch[t].push_back(2 * s);
+                if (md_reg[s]) need[t] += plan.seps[s].size();
+            }
+            need[t] += std::min<int64_t>(tsize(c), kRegEntries) + (early ? kids_rows(c) : kmax);
+            if (c != plan.root) {
+                need[t] += plan.seps[up].size();
+                touch[t].push_back(2 * up + 1);
+                if (md_reg[up]) pend += plan.seps[up].size();
+            }
+            if (k + 1 < nc) {
+                const int nx = pre[k + 1], nup = plan.clique_up[nx];
+                const bool ld_next = !md_reg[nup] && plan.sep_up[nup] != c;
+                const int64_t nrows = (early_lb(nx) ? kids_rows(nx) : 0) + (ld_next ? plan.seps[nup].size() : 0);
+                if (tsize(c) + pend + nrows <= budget) {
+                    need[t] += nrows;
+                    if (early_lb(nx))
+                        for (int s : plan.clique_down[nx]) touch[t].push_back(2 * s);
+                    if (ld_next) touch[t].push_back(2 * nup + 1);
+                }
+            }
+        }
+        peak_need = *std::max_element(need.begin(), need.end());
+        const int64_t slack = vmajor ? kRegSlackVM : kRegSlackCM;
+        std::vector<int64_t> live(2 * nc + 1, 0);  // parked rows by time (the cap)
+        for (int i : order) {
+            const Item &it = items[i];
+            const int id = 2 * it.s + (it.dist ? 1 : 0);
+            int64_t room = it.n;
+            for (int t = it.a; t <= it.b; ++t) room = std::min(room, reg_cap - live[t]);
+            std::vector<int> pay;  // the times this message costs registers of its own
+            for (int t = it.a; t < it.b; ++t)
+                if (t == it.a || std::find(touch[t].begin(), touch[t].end(), id) == touch[t].end()) pay.push_back(t);
+            for (int t : pay) room = std::min(room, kRegFile - slack - need[t] - reg_extra[t]);
+            if (room <= 0) continue;
+            nreg[i] = room;
+            for (int t = it.a; t <= it.b; ++t) live[t] += room;
+            for (int t : pay) reg_extra[t] += room;
+        }
+        if (!quiet && getenv("FBN_JT_PLACE_DEBUG")) {
+            std::string u;
+            for (int t = 0; t < 2 * nc; ++t)
+                u += std::to_string(need[t]) + "+" + std::to_string(reg_extra[t]) + (t == nc - 1 ? " | " : " ");
+            fprintf(stderr, "register rows by time, the op's own + parked (Collect | Distribute): %s\n", u.c_str());
+        }
+    }
     // room: the LDS of four waves per CU (160 KB) less the clique tail and the initial potentials
     const int64_t per_wave = 160 * 1024 / 4 / 8;  // fp64 values
     int64_t ivn = 0;
     for (const auto &t : plan.cliques) ivn += t.size();
     int64_t cap = std::max<int64_t>(0, (per_wave - lds_rows * 64 - (iv_lds ? ivn : 0)) / 64);
     if (const char *e = getenv("FBN_JT_LDS_POOL")) cap = std::min<int64_t>(cap, std::max(0, atoi(e)));
-    std::vector<int> order(items.size());
-    for (size_t i = 0; i < items.size(); ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-        return items[x].b - items[x].a < items[y].b - items[y].a;
-    });
     std::vector<int64_t> use(2 * nc + 1, 0);
     std::vector<bool> in_lds(items.size(), false);
     for (int i : order) {
         const Item &it = items[i];
-        if (it.n > cap) continue;
+        const int64_t n = it.n - nreg[i];  // (the rows not in registers)
+        if (n == 0 || n > cap) continue;
         int64_t mx = 0;
         for (int t = it.a; t <= it.b; ++t) mx = std::max(mx, use[t]);
-        if (mx + it.n > cap) continue;
-        for (int t = it.a; t <= it.b; ++t) use[t] += it.n;
+        if (mx + n > cap) continue;
+        for (int t = it.a; t <= it.b; ++t) use[t] += n;
         in_lds[i] = true;
     }
     // concrete pool rows, in start order
@@ -684,7 +797,7 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
                 ++k;
             }
         }
-        for (int64_t j = 0; j < it.n; ++j) {
+        for (int64_t j = nreg[i]; j < it.n; ++j) {
             rows_of[i].push_back(free_rows.back());
             pool_rows = std::max<int64_t>(pool_rows, free_rows.back() + 1);
             free_rows.pop_back();
@@ -694,33 +807,52 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
     col_loc.assign(ns, {});
     dis_loc.assign(ns, {});
     sep_row.assign(ns, -1);
+    reg_names.clear();
+    // global rows of a separator: shared by both its messages, entry j in row sep_row + j - sep_skip
+    // (sep_skip: leading entries neither message keeps there)
+    std::vector<int64_t> sep_skip(ns, 0);
+    for (int s = 0; s < ns; ++s) sep_skip[s] = plan.seps[s].size();
+    for (size_t i = 0; i < items.size(); ++i)
+        if (!in_lds[i]) sep_skip[items[i].s] = std::min(sep_skip[items[i].s], nreg[i]);
     int64_t grow = 0;
+    place = JTPlacement();
     for (size_t i = 0; i < items.size(); ++i) {
         const Item &it = items[i];
         auto &loc = it.dist ? dis_loc[it.s] : col_loc[it.s];
         loc.assign(it.n, std::string());
+        for (int64_t j = 0; j < nreg[i]; ++j) {
+            loc[j] = (it.dist ? "rd" : "rc") + std::to_string(it.s) + "_" + std::to_string(j);
+            reg_names.push_back(loc[j]);
+        }
+        place.reg[it.dist] += nreg[i];
         if (in_lds[i]) {
-            for (int64_t j = 0; j < it.n; ++j) loc[j] = "LP(" + std::to_string(rows_of[i][j]) + ")";
+            for (int64_t j = nreg[i]; j < it.n; ++j) loc[j] = "LP(" + std::to_string(rows_of[i][j - nreg[i]]) + ")";
+            place.lds[it.dist] += it.n - nreg[i];
             continue;
         }
-        if (sep_row[it.s] < 0) sep_row[it.s] = grow, grow += it.n;  // (shared by both messages)
-        for (int64_t j = 0; j < it.n; ++j) loc[j] = "W(" + std::to_string(sep_row[it.s] + j) + "LL)";
+        if (nreg[i] == it.n) continue;
+        if (sep_row[it.s] < 0) sep_row[it.s] = grow, grow += it.n - sep_skip[it.s];  // (shared by both messages)
+        for (int64_t j = nreg[i]; j < it.n; ++j) loc[j] = "W(" + std::to_string(sep_row[it.s] + j - sep_skip[it.s]) + "LL)";
+        place.global[it.dist] += it.n - nreg[i];
     }
+    place.workspace_rows = grow;
+    place.lds_pool_rows = pool_rows;
     for (int s = 0; s < ns; ++s) {
         if (sep_row[s] < 0) sep_row[s] = 0;
         if (dis_loc[s].empty()) dis_loc[s].assign(plan.seps[s].size(), "0.0");  // (in registers: never read)
         if (col_loc[s].empty()) col_loc[s].assign(plan.seps[s].size(), "0.0");  // (recomputed: never read)
     }
-    if (getenv("FBN_JT_PLACE_DEBUG")) {  // diagnostic: the placement's summary
-        int64_t lc = 0, ld = 0, gc = 0, gd = 0, leaf = 0;
-        for (size_t i = 0; i < items.size(); ++i)
-            (items[i].dist ? (in_lds[i] ? ld : gd) : (in_lds[i] ? lc : gc)) += items[i].n;
+    if (!quiet && getenv("FBN_JT_PLACE_DEBUG")) {  // diagnostic: the placement's summary
+        int64_t leaf = 0;
         for (int s = 0; s < ns; ++s)
             if (plan.clique_down[plan.sep_down[s]].empty()) leaf += plan.seps[s].size();
         fprintf(stderr, "placement: pool %lld of %lld rows; Collect rows LDS %lld global %lld; Distribute rows LDS %lld "
                         "global %lld (registers: the rest); global rows %lld; leaf-separator rows %lld\n",
-                (long long)pool_rows, (long long)cap, (long long)lc, (long long)gc, (long long)ld, (long long)gd,
-                (long long)grow, (long long)leaf);
+                (long long)pool_rows, (long long)cap, (long long)place.lds[0], (long long)place.global[0],
+                (long long)place.lds[1], (long long)place.global[1], (long long)grow, (long long)leaf);
+        if (reg_cap > 0)
+            fprintf(stderr, "register pool (cap %lld rows): Collect rows %lld, Distribute rows %lld\n", (long long)reg_cap,
+                    (long long)place.reg[0], (long long)place.reg[1]);
         std::string u;
         for (int t = 0; t <= 2 * nc; ++t) u += std::to_string(use[t]) + (t == nc - 1 ? " | " : " ");
         fprintf(stderr, "pool rows in use by time (Collect | Distribute): %s\n", u.c_str());
@@ -782,7 +914,21 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
     // changes nothing, 2 moves 85 message rows to registers and measured slower (0.127 -> 0.132 ms,
     // gpurun_out/r05y), so the default keeps the plan's order
     const int child_order = fast && getenv("FBN_JT_CHILD_ORDER") ? atoi(getenv("FBN_JT_CHILD_ORDER")) : 0;
-    auto dfs = [&](bool collect, std::vector<int> &post_o, std::vector<int> &pre_o) {
+    // With the register pool on, the child order of each phase is chosen by the placement itself:
+    // the plan's, heaviest subtree (sum of clique entries) first, or heaviest last -- whichever
+    // leaves the fewest message rows in global memory (a tie keeps the earlier candidate, the
+    // plan's order first).  Products and sums keep the plan's child order whatever is visited first.
+    std::vector<int64_t> weight(nc, 0);
+    {
+        std::function<int64_t(int)> w = [&](int c) {
+            weight[c] = plan.cliques[c].size();
+            for (int s : plan.clique_down[c]) weight[c] += w(child(s));
+            return weight[c];
+        };
+        w(plan.root);
+    }
+    // visit: 0 = plan order, 1 = heaviest subtree first, 2 = heaviest subtree last
+    auto dfs = [&](bool collect, int visit, std::vector<int> &post_o, std::vector<int> &pre_o) {
         std::vector<std::vector<int>> kids(nc);
         for (int c = 0; c < nc; ++c) {
             kids[c] = plan.clique_down[c];
@@ -790,6 +936,10 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
             if (asc || desc)
                 std::stable_sort(kids[c].begin(), kids[c].end(), [&](int x, int y) {
                     return asc ? plan.seps[x].size() < plan.seps[y].size() : plan.seps[x].size() > plan.seps[y].size();
+                });
+            else if (visit)
+                std::stable_sort(kids[c].begin(), kids[c].end(), [&](int x, int y) {
+                    return visit == 1 ? weight[child(x)] > weight[child(y)] : weight[child(x)] < weight[child(y)];
                 });
         }
         std::vector<std::pair<int, size_t>> st{{plan.root, 0}};
@@ -807,15 +957,41 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
         }
     };
     std::vector<int> post, pre, unused;
-    dfs(true, post, unused);
+    dfs(true, 0, post, unused);
     unused.clear();
-    dfs(false, unused, pre);
+    dfs(false, 0, unused, pre);
     if ((int)post.size() != nc) return SetError(FBN_ERR_LIMIT, "codegen: tree traversal covers %zu of %d cliques", post.size(), nc);
     // fp64 values per lane: table in flight + prefetched rows (FBN_JT_PREFETCH_BUDGET: tuning)
     // (fast order: 260 -- round 5 sweep 150 / 200 / 260 / 320: 0.171 / 0.169 / 0.165 / 0.166 ms)
     const int64_t kBudget = getenv("FBN_JT_PREFETCH_BUDGET") ? atoll(getenv("FBN_JT_PREFETCH_BUDGET")) : fast ? 260 : 200;
+    // register pool: fast order only (the exact order's source is pinned); on by default for the
+    // variable-major kernel only (the case-major one is faster with it too, but spills more SGPRs)
+    int64_t reg_cap = fast && vmajor ? kDefaultRegPool : 0;
+    if (const char *e = getenv("FBN_JT_REG_POOL")) reg_cap = fast ? std::max(0, atoi(e)) : 0;
+    if (reg_cap > 0 && child_order == 0) {
+        int64_t best = -1, plan_peak = 0;
+        int bvc = 0, bvd = 0;
+        std::vector<int> bpost = post, bpre = pre;
+        for (int vc = 0; vc < 3; ++vc)
+            for (int vd = 0; vd < 3; ++vd) {
+                std::vector<int> po, pr, un;
+                dfs(true, vc, po, un);
+                un.clear();
+                dfs(false, vd, un, pr);
+                PlaceMessages(po, pr, kBudget, reg_cap, true);
+                // (an order whose ops themselves need more registers than the plan order's at their
+                // peak is left out: the plan order's peak already fills the register file)
+                if (best < 0) plan_peak = peak_need;
+                else if (peak_need > plan_peak) continue;
+                const int64_t g = place.global[0] + place.global[1];
+                if (best < 0 || g < best) best = g, bpost = po, bpre = pr, bvc = vc, bvd = vd;
+            }
+        post = bpost, pre = bpre;
+        if (getenv("FBN_JT_PLACE_DEBUG"))
+            fprintf(stderr, "child order (0 plan, 1 heaviest subtree first, 2 last): Collect %d, Distribute %d\n", bvc, bvd);
+    }
     if (fast) ChooseMarginalSources(pre);
-    PlaceMessages(post, pre, kBudget);
+    PlaceMessages(post, pre, kBudget, reg_cap, false);
     int64_t rows = 0;
     for (int s = 0; s < ns; ++s) rows = std::max<int64_t>(rows, sep_row[s] + plan.seps[s].size());
     *wave_entries = std::max<int64_t>(rows, 1);
@@ -965,6 +1141,13 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
     }
     for (int k = 0; k < nokw; ++k) o << "        unsigned okw" << k << " = 0u;\n";
     for (int k = 0; k < nobs; ++k) o << "        unsigned obs" << k << " = 0u;\n";
+    // message entries parked in registers: one per block iteration, assigned by the op that forms
+    // the message before any op reads it; not in the boundaries' operand lists (free to sit in AGPRs)
+    for (size_t i = 0; i < reg_names.size(); i += 8) {
+        o << "        double";
+        for (size_t k = i; k < std::min(reg_names.size(), i + 8); ++k) o << (k > i ? ", " : " ") << reg_names[k];
+        o << ";\n";
+    }
     for (int v = 0; v < V; ++v) {
         const unsigned full = (plan.dom[v] >= 32) ? 0xFFFFFFFFu : ((1u << plan.dom[v]) - 1u);
         o << "        { const int x = ev[" << v << "]; okw" << okw_word[v] << " |= (x < 0 ? " << full << "u : (1u << x)) << "
@@ -999,7 +1182,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
             collect_loads(k + 1, next);
             int64_t pend = 0;
             for (int s : mine) pend += plan.seps[s].size();
-            if (tsize(c) + pend + rows_of(next) <= kBudget)
+            if (tsize(c) + pend + rows_of(next) + reg_extra[k] <= kBudget)  // (less the parked rows live now)
                 for (int s : next)
                     if (!loaded_a[s]) Load("la", s), loaded_a[s] = true;
         }
@@ -1057,7 +1240,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
             // its parent message, unless still in registers or produced by this clique
             const bool ld_next = !md_reg[nup] && plan.sep_up[nup] != c;
             const int64_t nrows = (early_lb(nx) ? kids_rows(nx) : 0) + (ld_next ? plan.seps[nup].size() : 0);
-            if (tsize(c) + pend + nrows <= kBudget) {
+            if (tsize(c) + pend + nrows + reg_extra[nc + k] <= kBudget) {
                 if (early_lb(nx))
                     for (int s : plan.clique_down[nx])
                         if (!loaded_b[s] && !leaf_rc[s]) Load("lb", s), loaded_b[s] = true;
@@ -1114,9 +1297,10 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
 }  // namespace
 
 int GenerateJTKernel(const JTPlanHost &plan, std::string &src, int64_t *wave_entries, std::vector<double> &initv,
-                     int64_t *lds_bytes, bool fast, bool var_major) {
+                     int64_t *lds_bytes, bool fast, bool var_major, JTPlacement *placement) {
     JTGen g(plan, fast, var_major);
     int rc = g.Run(src, wave_entries, initv);
+    if (placement) *placement = g.place;
     if (lds_bytes) *lds_bytes = ((g.lds_rows + g.pool_rows) * 64 + (g.iv_lds ? (int64_t)initv.size() : 0)) * 8;
     return rc;
 }

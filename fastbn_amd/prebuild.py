@@ -48,10 +48,11 @@ def fixture_xmls(dirname):
 
 
 # code-generation options the GPU tests run ALARM under (tests/test_gpu_jt_fast.py)
-ALARM_TEST_OPTIONS = ({"FBN_JT_LEAF_RC": "1"}, {"FBN_JT_LDS_POOL": "0"}, {"FBN_JT_MARG_V2": "0"})
+ALARM_TEST_OPTIONS = ({"FBN_JT_LEAF_RC": "1"}, {"FBN_JT_LDS_POOL": "0"}, {"FBN_JT_MARG_V2": "0"},
+                      {"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"})
 
 
-def prebuild_options(xml, options):
+def prebuild_options(xml, options, layout=0):
     """The fast-order kernel of `xml` under each set of generator environment options (read when
     the kernel is generated), built in a child process per set."""
     import subprocess
@@ -60,7 +61,8 @@ def prebuild_options(xml, options):
     for opt in options:
         env = dict(os.environ, **opt)
         code = ("import sys; sys.path.insert(0, %r); from fastbn_amd import api; "
-                "print(api.JunctionTree(api.Network(%r), device=-1).build_kernel())" % (REPO, xml))
+                "jt = api.JunctionTree(api.Network(%r), device=-1); jt.set_output_layout(%d); "
+                "print(jt.build_kernel())" % (REPO, xml, layout))
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True)
         out.append(r.stdout.strip().splitlines()[-1])
     return out
@@ -73,6 +75,8 @@ def prebuild_default(clean=True):
     with tempfile.TemporaryDirectory() as d:
         built = prebuild([ALARM_XML], layouts=(0, 1)) + prebuild([synth_small_xml(d)] + fixture_xmls(d))
     built += prebuild_options(ALARM_XML, ALARM_TEST_OPTIONS)
+    # (tests/test_gpu_jt_regpool.py compares the register pool on / off in both output layouts)
+    built += prebuild_options(ALARM_XML, ({"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"}), layout=1)
     if clean:
         keep = {os.path.basename(p) for p in built}
         kdir = os.path.join(REPO, "fastbn_amd", "kcache")

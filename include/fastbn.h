@@ -213,6 +213,12 @@ int fbn_jt_debug_flagged_blocks(fbn_jt_plan *p, int64_t *count);
 /* Path of the specialized kernel's code object in the on-disk cache (whether or not it exists);
  * a build step may compile fbn_jt_kernel_source() there with the options of fbn_jt_kernel_options. */
 int fbn_jt_kernel_cache_path(const fbn_jt_plan *p, char *buf, int64_t cap);
+/* Where the specialized kernel of the current order and layout keeps its stored messages, in rows
+ * (one fp64 per lane): rows[0..5] = global Collect, global Distribute, LDS Collect, LDS Distribute,
+ * register Collect, register Distribute; rows[6] = rows of the per-wave global workspace in use (a
+ * separator's two messages share theirs), rows[7] = rows of the per-wave LDS pool (the most in use
+ * at one time).  No device needed. */
+int fbn_jt_kernel_placement(const fbn_jt_plan *p, int64_t *rows);
 /* Compile the specialized kernel into the on-disk cache now (no device needed); FBN_OK if cached. */
 int fbn_jt_kernel_build(const fbn_jt_plan *p);
 /* Compile options of the specialized kernel, '\n'-separated. */
