@@ -39,6 +39,7 @@ extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, co
 extern "C" hipError_t fbn_ci_pack2_build(const uint8_t *cols, int nvars, long long N, long long PW, uint32_t *pk,
                                          hipStream_t stream);
 extern "C" size_t fbn_ci_lds_bytes(int dimz, int dx, int dy);
+extern "C" size_t fbn_ci_static_lds_bytes();
 extern "C" hipError_t fbn_jt_evidence_check(const int8_t *ev, long long n, int V, const int32_t *dom,
                                             unsigned long long *first, hipStream_t s);
 extern "C" hipError_t fbn_ci_cols_check(const uint8_t *cols, const int32_t *dims, int nvars, long long N, int *bad,
@@ -1683,6 +1684,30 @@ static int CiPack2Ensure(fbn_ci_ctx *c, hipStream_t s) {
     return FBN_OK;
 }
 
+// The histogram kernel (ci_kernels.hip) holds a test's cell count, every cell index and every
+// offset of its table layout (cells, sub-histograms, marginals, term buffer: fbn_ci_lds_bytes) in
+// 32-bit ints: a test whose layout does not fit is refused here, before anything is allocated or
+// launched.  it: the test's variables (x, y, z_1 .. z_d, validated); -> its conditioning
+// configurations and layout bytes.
+static int CiTableCheck(const fbn_ci_ctx *c, const int32_t *it, int d, long long test, int64_t *dimz_out,
+                        size_t *bytes_out) {
+    int64_t dimz = 1;
+    for (int j = 0; j < d; ++j) {
+        dimz *= c->dims[it[2 + j]];
+        if (dimz > (1 << 24)) return SetError(FBN_ERR_LIMIT, "test %lld: conditioning table too large", test);
+    }
+    const int dx = c->dims[it[0]], dy = c->dims[it[1]];
+    const size_t bytes = fbn_ci_lds_bytes((int)dimz, dx, dy);
+    if (bytes / 4 > (size_t)INT32_MAX)
+        return SetError(FBN_ERR_LIMIT,
+                        "test %lld: table of %lld cells (%lld conditioning configurations x %d x %d states) is beyond "
+                        "the kernel's 32-bit int cell indexing (cells, marginals and term buffer: at most 2^31 - 1 ints)",
+                        test, (long long)(dimz * dx * dy), (long long)dimz, dx, dy);
+    if (dimz_out) *dimz_out = dimz;
+    if (bytes_out) *bytes_out = bytes;
+    return FBN_OK;
+}
+
 static int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double alpha, bool want_g2p,
                           int32_t *counts_dev, hipStream_t s, int k = 0, const int32_t *zc_items = nullptr,
                           uint8_t *zc_indep = nullptr, int32_t *zc_df = nullptr, const fbn::CiBatchStats *pre = nullptr,
@@ -1808,14 +1833,15 @@ static int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d,
     int64_t mask_rows = 0;  // bit-sliced counting: dimz * (dx + dy + d) mask rows per test
     for (int64_t i = 0; i < n; ++i) {
         const int32_t *it = items + i * w;
-        int64_t dimz = 1;
-        for (int j = 0; j < d; ++j) dimz *= c->dims[it[2 + j]];
-        if (dimz > (1 << 24)) return SetError(FBN_ERR_LIMIT, "test %lld: conditioning table too large", (long long)i);
-        lds = std::max(lds, fbn_ci_lds_bytes((int)dimz, c->dims[it[0]], c->dims[it[1]]));
+        int64_t dimz = 0;
+        size_t bytes = 0;
+        if ((rc = CiTableCheck(c, it, d, i, &dimz, &bytes))) return rc;
+        lds = std::max(lds, bytes);
         mask_rows += dimz * (c->dims[it[0]] + c->dims[it[1]] + d);
     }
     // tables beyond the LDS budget: the same layout in a per-workgroup global scratch region
-    const bool global_tables = lds > 160 * 1024;
+    // (the kernel's own static LDS comes on top of the dynamic region)
+    const bool global_tables = lds + fbn_ci_static_lds_bytes() > 160 * 1024;
     if ((rc = S.items.ensure((size_t)n * w * 4))) return rc;
     if ((rc = S.indep.ensure((size_t)n))) return rc;
     if ((rc = S.df.ensure((size_t)n * 4))) return rc;
@@ -1928,11 +1954,12 @@ int fbn_ci_counts(fbn_ci_ctx *c, int x, int y, const int32_t *z, int d, int32_t 
     for (int j = 0; j < d; ++j) item.push_back(z[j]);
     for (int32_t v : item)
         if (v < 0 || v >= c->nvars) return SetError(FBN_ERR_ARG, "variable out of range");
-    int64_t nc = (int64_t)c->dims[x] * c->dims[y];
-    for (int j = 0; j < d; ++j) nc *= c->dims[z[j]];
+    int rc;
+    int64_t dimz = 0;
+    if ((rc = CiTableCheck(c, item.data(), d, 0, &dimz, nullptr))) return rc;
+    const int64_t nc = dimz * c->dims[x] * c->dims[y];
     if (cells) *cells = nc;
     FBN_HIP(hipSetDevice(c->device));
-    int rc;
     if ((rc = c->counts.ensure((size_t)nc * 4))) return rc;
     rc = CiLaunchDevice(c, item.data(), 1, d, 0.05, false, c->counts.as<int32_t>(), nullptr);
     if (rc) return rc;
@@ -2010,6 +2037,14 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
         for (int v = 0; v < nv; ++v) st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
         if (!c->pairs_recorded && st.maxdim <= 4 && c->N >= 4096 && (rc = level0())) return rc;
         if (c->pairs_recorded) fbn::CiSetPairMode(c, 2);
+    }
+    for (int64_t t = 0; t < n; ++t) {  // the kernel writes every cell of a table: each must fit its row
+        int64_t dimz = 0;
+        if ((rc = CiTableCheck(c, items + w * t, d, t, &dimz, nullptr))) return rc;
+        const int64_t cells = dimz * c->dims[items[w * t]] * c->dims[items[w * t + 1]];
+        if (cells > cap)
+            return SetError(FBN_ERR_ARG, "test %lld: %lld cells exceed cap %lld", (long long)t, (long long)cells,
+                            (long long)cap);
     }
     if ((rc = c->counts.ensure((size_t)n * cap * 4))) return rc;
     FBN_HIP(hipMemsetAsync(c->counts.p, 0, (size_t)n * cap * 4, c->stream));  // cells beyond a table: 0

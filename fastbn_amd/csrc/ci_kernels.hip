@@ -26,6 +26,7 @@ namespace {
 // G^2 terms buffered per chunk of cells (LDS doubles) before the in-order sum
 constexpr int kTermChunk = 1024;
 constexpr long long kWideTests = 512;  // batches up to this size: 1024-thread workgroups
+constexpr long long kPackedLaneMax = 65520;  // packed 16-bit counters: samples per thread (see `packed`)
 constexpr int kDerivedInts = 256;      // MODE 3: the four full 3-way tables (4 x 64 ints) after the terms
 // MODE 3 / 4: the derived d = 2 counting with the register allocation unconstrained (2 waves per
 // SIMD) / allowing 3 waves per SIMD (the default; only the widest state-count instantiations spill)
@@ -386,7 +387,12 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
         // adds into copy w * kl + l % kl): no cross-wave contention, and kl-fold fewer same-address
         // atomics within a wave on skewed tables (a popular cell's lanes serialize in one copy);
         // copies at an odd stride, so one cell's copies fall in different banks
-        const bool packed = cells <= 16 && A.N <= (1ll << 24);
+        // (a lane's share of the samples must fit a 16-bit field even when all of them fall in one
+        // cell: at most 4 ceil(N / 4 / BS) from the dword loop, 16 ceil(N / 16 / BS) + 15 from the
+        // 2-bit words with the tail on lane 0, ceil(N / BS) from the scalar loop -- all below
+        // 65 536 for N <= 65520 BS; 2^24 samples in 256 threads would wrap a field to 0 and carry
+        // into the next cell's)
+        const bool packed = cells <= 16 && A.N <= kPackedLaneMax * BS;
         const int kl = sub_lanes(cells);
         const int nsub = kl ? 4 * kl : 1;  // = fbn_ci_lds_bytes
         const int sstr = cells | 1;
@@ -770,6 +776,10 @@ extern "C" size_t fbn_ci_lds_bytes(int dimz, int dx, int dy) {
     ints = (ints + 1) & ~(size_t)1;
     return ints * 4 + std::min<size_t>(cells, kTermChunk) * 8 + kDerivedInts * 4;
 }
+
+// the kernel's statically allocated LDS on top of that (sred, sdf, sdec: 324 bytes in the 16-wave
+// instantiation, rounded up): a launch needs both within the 160 KiB of a workgroup
+extern "C" size_t fbn_ci_static_lds_bytes() { return 512; }
 
 extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, const int32_t *items, long long N,
                                     long long n, int d, double alpha, double *g2, int32_t *df, double *p,

@@ -9,6 +9,7 @@ TEST INFRASTRUCTURE -- runs in the build container.
                 reference JunctionTree compiled in place): per-case label + 17-digit marginals
                 (ref.marg.gz) and the reference's junction-tree plan (ref.plan.gz).
   pc_c5.ci.gz   config 5: the reference's own Counts2D / Counts3D tables (pc_c5_ci below)
+  widedom.ci.gz the reference's Counts2D / Counts3D tables on the wide-domain shapes (widedom below)
   synth_nets/   networks beyond ALARM / Munin-like (tests/conftest.py SYNTH_NET_SPECS, tie_network):
                 state counts up to 21, a 12-variable clique, symmetric CPTs whose query marginals
                 tie; seeded evidence cases (.ev.npy) and the reference's own labels + marginals
@@ -207,6 +208,42 @@ def gram_ragged():
     print("gram_ragged.ci.gz: %d shapes x %d pairs" % (len(GRAM_SHAPES), GRAM_PAIRS))
 
 
+def widedom():
+    """widedom.ci.gz: the UNMODIFIED reference's Counts2D / Counts3D::FillTable (oracle/_ref/ref_dump
+    ci) on the wide-domain shape datasets of test_gpu_ci_widedom.py (tests/widedom_data.py: up to 241
+    states, asymmetric tables, unequal radices in z): the shapes of at most 5000 cells as laid out,
+    with x and y exchanged and with z reversed, one block per sample count:
+    `shape nvars N seed` then the ci dump."""
+    import struct
+
+    import numpy as np
+    import widedom_data as W
+    ref_dump = os.path.join(REPO, "oracle", "_ref", "ref_dump")
+    if not os.path.exists(ref_dump):
+        subprocess.run(["make", "-C", os.path.join(REPO, "oracle"), "ref"], check=True)
+    blocks, ntests = [], 0
+    for N in W.FIXTURE_SAMPLE_COUNTS:
+        cols, dims, items, _ = W.shape_dataset(N)
+        tests = W.fixture_tests(items)
+        ntests += len(tests)
+        with tempfile.TemporaryDirectory() as td:
+            cpath = os.path.join(td, "w.cols")
+            with open(cpath, "wb") as f:
+                f.write(struct.pack("<iq", len(dims), N))
+                f.write(np.asarray(dims, np.int32).tobytes())
+                f.write(np.ascontiguousarray(cols, np.uint8).tobytes())
+            tfile = os.path.join(td, "tests")
+            with open(tfile, "w") as f:
+                for t in tests:
+                    f.write(" ".join(map(str, t)) + "\n")
+            out = os.path.join(td, "w.ci")
+            subprocess.run([ref_dump, "ci", "cols:" + cpath, tfile, out], check=True, stdout=subprocess.DEVNULL)
+            blocks.append("shape %d %d %d\n" % (len(dims), N, W.SHAPE_SEED + N) + open(out).read())
+    path = os.path.join(HERE, "widedom.ci.gz")
+    gz_write(path, "".join(blocks))
+    print("widedom.ci.gz: %d tests in %d blocks, %d bytes" % (ntests, len(blocks), os.path.getsize(path)))
+
+
 def synth_nets():
     """synth_nets/<name>.{xml.gz, ev.npy, ref.marg.gz} for name in bigdom / wide / tie: the XMLBIF,
     the evidence cases (conftest.synth_net_cases) and the UNMODIFIED reference's labels and 17-digit
@@ -235,7 +272,7 @@ def synth_nets():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["munin", "munin_extra", "c5", "c5ci", "gram", "synth_nets"]
+    which = sys.argv[1:] or ["munin", "munin_extra", "c5", "c5ci", "gram", "synth_nets", "widedom"]
     if "munin" in which:
         munin_like()
     if "munin_extra" in which:
@@ -248,3 +285,5 @@ if __name__ == "__main__":
         gram_ragged()
     if "synth_nets" in which:
         synth_nets()
+    if "widedom" in which:
+        widedom()
