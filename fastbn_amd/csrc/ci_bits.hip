@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "ci_chisq.h"
+#include "launchers.h"
 
 
 namespace {
@@ -297,7 +298,7 @@ constexpr int kBitsCells = 64;  // count slots per test
 
 // ---- register-blocked marginal tests (a PC run's level 0, all pairs of a pair-index range)
 // One wave per task = a block of BX x-variables x BY y-variables of one state-count class each
-// (tasks built on the host, CiPairTasks in capi.hip): per 4-word step every mask row of the block's
+// (tasks built on the host, CiPairTasks in capi_ci.hip): per 4-word step every mask row of the block's
 // variables is loaded once and feeds every pair of the block, so L2 / fabric traffic per pair drops
 // from (dx-1 + dy-1) rows to (BX (dx-1) + BY (dy-1)) / (BX BY) rows.  A pair is the block's
 // (x, y) with x < y and its index in [t0, t1) (each pair of the range exactly once); the counts
@@ -550,7 +551,7 @@ __global__ __launch_bounds__(256) void ci_bits_count_derived(const uint32_t *__r
 // bits.  One wave per task = an 8 x 8 tile of (i, j) row pairs (optionally every row ANDed with a
 // mask row x_a): per 4-word step 16 (17) 16-byte loads feed 256 popcounts, counters in registers,
 // then a butterfly reduction that leaves counter l's wave total in lane l (63 shuffles instead of
-// 64 x 6).  Tasks are built on the host (capi.hip CiGram*): one block of one wave per task so the
+// 64 x 6).  Tasks are built on the host (capi_ci.hip CiGram*): one block of one wave per task so the
 // task fields and row pointers are wave-uniform (scalar registers).
 constexpr int kGramTaskInts = 8;  // mask row (-1: none), i0, ni, j0, nj, out offset (lo, hi), ld
 
@@ -1660,77 +1661,6 @@ extern "C" hipError_t fbn_ci_l1_round(const uint32_t *bits, const int32_t *dims,
     hipLaunchKernelGGL(ci_l1_resolve, dim3((unsigned)std::min(ntiles, num_cu * 4)), dim3(256), 0, s, ed, pos, len,
                        off, st, sep, counted, (const uint8_t *)indep, (const int32_t *)items, E, open_cnt, open_next,
                        next_chunk, sstat, epoch, cap, scal, plist);
-    return hipGetLastError();
-}
-
-// one byte per (leading row, sample): out[r][s] = [cols[v][s] == a] for leading row r = lead0[v] + a
-// (a < dims[v] - 1), samples N..Npad-1 zero -- the int8 operand of the level-0 Gram as a library
-// GEMM (capi.hip); 4 samples per thread
-__global__ __launch_bounds__(256) void ci_onehot_build(const uint8_t *__restrict__ cols, const int32_t *__restrict__ dims,
-                                                       const int32_t *__restrict__ lead0, long long N, long long Npad,
-                                                       int nvars, int8_t *__restrict__ out) {
-    const long long n4 = Npad / 4;
-    for (int v = blockIdx.y; v < nvars; v += gridDim.y) {
-        const int m = dims[v] - 1;
-        if (m <= 0) continue;
-        const uint8_t *c = cols + (size_t)v * N;
-        int8_t *o = out + (size_t)lead0[v] * Npad;
-        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-            uint8_t b[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) b[k] = 4 * q + k < N ? c[4 * q + k] : 0xFF;
-            for (int a = 0; a < m; ++a) {
-                uint32_t w = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) w |= (uint32_t)(b[k] == a) << (8 * k);
-                reinterpret_cast<uint32_t *>(o + (size_t)a * Npad)[q] = w;
-            }
-        }
-    }
-}
-
-extern "C" hipError_t fbn_ci_onehot_build(const uint8_t *cols, const int32_t *dims, const int32_t *lead0, long long N,
-                                          long long Npad, int nvars, int8_t *out, hipStream_t s) {
-    const long long g = (Npad / 4 + 255) / 256;
-    hipLaunchKernelGGL(ci_onehot_build, dim3((unsigned)(g < 64 ? g : 64), (unsigned)(nvars < 1024 ? nvars : 1024)),
-                       dim3(256), 0, s, cols, dims, lead0, N, Npad, nvars, out);
-    return hipGetLastError();
-}
-
-// out[i] = sum over np planes of planes[p * n + i] (split-K partial Grams; integers)
-__global__ __launch_bounds__(256) void ci_sum_planes(const int4 *__restrict__ planes, int np, long long n4,
-                                                     int4 *__restrict__ out) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        int4 a = planes[i];
-        for (int p = 1; p < np; ++p) {
-            const int4 b = planes[p * n4 + i];
-            a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w;
-        }
-        out[i] = a;
-    }
-}
-__global__ __launch_bounds__(256) void ci_sum_planes_tail(const int32_t *__restrict__ planes, int np, long long n,
-                                                          long long from, int32_t *__restrict__ out) {
-    const long long i = from + (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int32_t a = 0;
-    for (int p = 0; p < np; ++p) a += planes[p * n + i];
-    out[i] = a;
-}
-
-extern "C" hipError_t fbn_ci_sum_planes(const int32_t *planes, int np, long long n, int32_t *out, hipStream_t s) {
-    // the int4 path needs every plane 16-byte aligned: n % 4 == 0 (and 16-byte aligned bases)
-    const bool vec = n % 4 == 0 && ((uintptr_t)planes % 16) == 0 && ((uintptr_t)out % 16) == 0;
-    const long long n4 = vec ? n / 4 : 0;
-    if (n4) {
-        const long long g = (n4 + 255) / 256;
-        hipLaunchKernelGGL(ci_sum_planes, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, s,
-                           (const int4 *)planes, np, n4, (int4 *)out);
-    }
-    const long long rest = n - 4 * n4;
-    if (rest > 0)
-        hipLaunchKernelGGL(ci_sum_planes_tail, dim3((unsigned)((rest + 255) / 256)), dim3(256), 0, s, planes, np, n,
-                           4 * n4, out);
     return hipGetLastError();
 }
 

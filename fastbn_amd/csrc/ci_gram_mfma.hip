@@ -28,7 +28,7 @@
 //    (r & 3, (r >> 2) & 3) pair once) hits 16 distinct 4-bank slots (SQ_LDS_BANK_CONFLICT = 0).
 //    global_load_lds writes lane L at base + 16 L, so the swizzle is applied to the global source.
 //  * Measured (config 5, 2000 rows x 100k samples, S = 7, 252 blocks): 0.100-0.110 ms for the
-//    tiles + 0.013-0.018 ms for the reduce (rocBLAS int8 split-K: 0.26 ms).  MFMA busy 47 % of the
+//    tiles + 0.013-0.018 ms for the reduce (the int8 library GEMM it replaced, split-K: 0.26 ms).  MFMA busy 47 % of the
 //    kernel (PMC); an MFMA-only loop of the same shape reaches 7.9 PF/s (61 us), with the fragment
 //    reads and barrier 6.7 PF/s (72 us, tools/micro/mfma_fp4_rate.hip); the restaging costs
 //    ~17 us more (no change from 4 -> 5 stages in flight or from full-line staging: L2 bandwidth,
@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "launchers.h"
 
 namespace {
 

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "ci_chisq.h"
+#include "launchers.h"
 
 namespace {
 

@@ -15,6 +15,7 @@ namespace fbn {
 
 // thread-local error channel behind fbn_last_error()
 int SetError(int code, const char *fmt, ...);
+const char *LastError();
 
 // ---------------------------------------------------------------------------------------------
 // discrete Bayesian network (CustomNetwork + DiscreteNode state the hot paths read)
@@ -164,6 +165,13 @@ struct JTPlacement {
 int GenerateJTKernel(const JTPlanHost &plan, std::string &src, int64_t *wave_entries, std::vector<double> &initv,
                      int64_t *lds_bytes = nullptr, bool fast = false, bool var_major = false,
                      JTPlacement *placement = nullptr);
+
+// compile + cache of the generated kernels (jt_jit.hip): the hiprtc options (part of the cache key),
+// the cache file of a source, its code object (cache hit or compile)
+extern const char *kJitOptions[];
+extern const int kJitNumOptions;
+std::string JitCachePath(const std::string &src);
+int JitCodeObject(const std::string &src, std::vector<char> &code);
 
 }  // namespace fbn
 

@@ -24,7 +24,7 @@
 //    permitting) so their latency hides behind its arithmetic.
 // Operation order per entry is exactly the interpreter's (= the reference's), so results are
 // bit-identical; a lane whose normalization denominator leaves [2^-600, 2^600] flags its block,
-// which the exact interpreter then recomputes (see capi.hip).
+// which the exact interpreter then recomputes (see capi_jt.hip).
 #include <algorithm>
 #include <map>
 #include <cstdio>

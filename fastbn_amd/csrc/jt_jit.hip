@@ -20,9 +20,8 @@
 
 namespace fbn {
 
-extern const char *kJitOptions[];
 const char *kJitOptions[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-extern const int kJitNumOptions = 4;
+const int kJitNumOptions = 4;
 
 namespace {
 

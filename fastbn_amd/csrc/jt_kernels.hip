@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "jt_program.h"
+#include "launchers.h"
 
 namespace {
 
@@ -662,7 +663,7 @@ extern "C" hipError_t fbn_jt_lds_launch(const JtOp *ops, int nops, const int32_t
     return hipGetLastError();
 }
 
-// launch wrapper (called from capi.hip)
+// launch wrapper (called from capi_jt.hip)
 extern "C" hipError_t fbn_jt_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
                                     const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
                                     double *marg, int32_t *labels, double *ws, int32_t *wsi, long long NE, int nc,

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "jt_program.h"
+#include "launchers.h"
 
 namespace {
 

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "jt_program.h"
+#include "launchers.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// param_counts.h -- launch interface of the family-count kernel (param_counts.hip), shared with capi.hip.
+// param_counts.h -- launch interface of the family-count kernel (param_counts.hip), shared with capi_ci.hip.
 #ifndef FBN_PARAM_COUNTS_H
 #define FBN_PARAM_COUNTS_H
 

@@ -29,7 +29,7 @@ namespace fbn {
 
 namespace {
 
-constexpr int kMaxD = 8;  // CI tests take at most 8 conditioning variables (capi.hip)
+constexpr int kMaxD = 8;  // CI tests take at most 8 conditioning variables (capi_ci.hip)
 
 // one edge's search state: the current side's candidate list is adj(a) \ {b}, read in place
 // (element i = base[i + (i >= skip)]), the next combination as positions into it

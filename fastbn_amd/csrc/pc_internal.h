@@ -227,7 +227,7 @@ bool CiPairsRecorded(const fbn_ci_ctx *c);
 // last value of x, y and z from them, 0 = off (also drops what was recorded)
 void CiSetPairMode(fbn_ci_ctx *c, int mode);
 // level 1 of a PC run: per-variable masked Grams for the endpoints of edges [e_begin, e_end)
-// (capi.hip); a no-op when not eligible
+// (capi_pc.hip); a no-op when not eligible
 int CiTriplePrepare(fbn_ci_ctx *c, const std::vector<std::vector<int>> &adj,
                     const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, bool *ready);
 int CiBatchWait(fbn_ci_ctx *c, int k, uint8_t *indep, int32_t *df, PCResultHost &res);
@@ -251,17 +251,17 @@ struct LevelOut {
     int64_t counted = 0, launched = 0;
 };
 // the kept pairs of the last complete-graph level-0 batch (pairs [t0, t0 + P)), appended in pair
-// order, compacted on the device (capi.hip)
+// order, compacted on the device (capi_pc.hip)
 int CiAllPairsKept(fbn_ci_ctx *c, int64_t t0, int64_t P, std::vector<std::pair<int, int>> &kept);
-// a PC run's level 1 (group size 1) on the device (capi.hip); *done = false: not eligible
+// a PC run's level 1 (group size 1) on the device (capi_pc.hip); *done = false: not eligible
 int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<int>> &adj,
                    const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, LevelOut &out,
                    PCResultHost &res, bool *done);
-// the level-1 rounds over an edge list / adjacency already on the device (capi.hip); host_work runs
+// the level-1 rounds over an edge list / adjacency already on the device (capi_pc.hip); host_work runs
 // once while the first round is on the device
 int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out, PCResultHost &res,
                 const std::function<int()> &host_work);
-// Level 0 -> level 1 without a host round trip (capi.hip): whether the ctx qualifies (level 1 would
+// Level 0 -> level 1 without a host round trip (capi_pc.hip): whether the ctx qualifies (level 1 would
 // run on the device: pair tables recorded, bit-sliced store, every variable <= 4 states, group 1)
 bool CiL0L1DeviceEligible(fbn_ci_ctx *c, int group_size);
 // level 0 recorded its pair tables and the ctx uses them (pair mode 2): level 1 can run on the device
@@ -282,7 +282,7 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
 void ApplyRemovals(const std::vector<char> &rm, std::vector<std::pair<int, int>> &edges,
                    std::vector<std::vector<int>> &adj);
 bool ContinueAfter(const std::vector<std::vector<int>> &adj, int d);
-// decision-margin log of a ctx (capi.hip): reset / read
+// decision-margin log of a ctx (capi_pc.hip): reset / read
 int CiMarginReset(fbn_ci_ctx *c);
 int CiMarginRead(fbn_ci_ctx *c, double *min_margin, int64_t *near_alpha);
 // orientation (pc_orient.cpp): v-structures + Meek rules 1-3 on res.edges / res.sepset

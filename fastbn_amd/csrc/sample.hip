@@ -29,15 +29,15 @@
 #include <cstring>
 #include <set>
 
+#include "fbn_device.h"
 #include "fbn_internal.h"
+#include "launchers.h"
 #include "sample_model.h"
 
+using fbn::DevBuf;
 using fbn::SampleNode;
 using fbn::SetError;
 using fbn::U128;
-
-extern "C" hipError_t fbn_jt_evidence_check(const int8_t *ev, long long n, int V, const int32_t *dom,
-                                            unsigned long long *first, hipStream_t s);
 
 namespace {
 
@@ -202,36 +202,7 @@ __global__ __launch_bounds__(64) void sample_lw_kernel(LwArgs A) {
     }
 }
 
-// growable device buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t b) {
-        if (b <= bytes) return FBN_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, b);
-        if (e != hipSuccess) return SetError(FBN_ERR_NOMEM, "hipMalloc(%zu): %s", b, hipGetErrorString(e));
-        bytes = b;
-        return FBN_OK;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
 }  // namespace
-
-#define FBN_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return SetError(FBN_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 struct fbn_sampler {
     fbn::SamplerModel M;
@@ -282,29 +253,15 @@ int ForwardDevice(fbn_sampler *s, int64_t n, uint64_t seed, uint8_t *d_cols, hip
     return FBN_OK;
 }
 
-// as fbn_jt_run_device's check: on the device, one stream sync
-int CheckEvidenceDevice(fbn_sampler *s, const int8_t *d_ev, int64_t ncases, hipStream_t st) {
-    const int V = s->M.V;
-    FBN_HIP(hipMemsetAsync(s->evcheck.p, 0xFF, 8, st));
-    FBN_HIP(fbn_jt_evidence_check(d_ev, (long long)ncases * V, V, s->dom.as<int32_t>(),
-                                  s->evcheck.as<unsigned long long>(), st));
-    unsigned long long first = 0;
-    FBN_HIP(hipMemcpyAsync(&first, s->evcheck.p, 8, hipMemcpyDeviceToHost, st));
-    FBN_HIP(hipStreamSynchronize(st));
-    if (first == ~0ull) return FBN_OK;
-    int8_t code = 0;
-    FBN_HIP(hipMemcpy(&code, d_ev + first, 1, hipMemcpyDeviceToHost));
-    const int v = (int)(first % V);
-    return SetError(FBN_ERR_ARG, "case %lld: evidence %d for node %d (domain %d)", (long long)(first / V), (int)code, v,
-                    s->M.dom[v]);
-}
-
 int LwDevice(fbn_sampler *s, int method, const int8_t *d_ev, int64_t ncases, int64_t S, uint64_t seed,
              int64_t case_offset, int32_t *d_labels, double *d_marg, double *d_stats, uint8_t *dv, double *dm,
              int32_t *de, hipStream_t st) {
     if (ncases > 0x7fffffffll) return SetError(FBN_ERR_LIMIT, "%lld cases in one call", (long long)ncases);
     s->streams_used.insert(st);
-    if (int rc = CheckEvidenceDevice(s, d_ev, ncases, st)) return rc;
+    // as fbn_jt_run_device's check: on the device, one stream sync
+    if (int rc = fbn::EvidenceCheckDevice(d_ev, ncases, s->M.V, s->dom.as<int32_t>(), s->M.dom.data(),
+                                          s->evcheck.as<unsigned long long>(), st))
+        return rc;
     if (!d_marg) {  // labels only: the accumulator rows live in the handle
         if (int rc = s->scratch.ensure((size_t)ncases * s->M.sum_dom * 8)) return rc;
         d_marg = s->scratch.as<double>();
@@ -340,16 +297,8 @@ int fbn_sampler_create(const fbn_network *net, int device, fbn_sampler **out) {
     if (rc == FBN_OK && device >= 0) {
         s->device = device;
         rc = [&]() -> int {
-            int n = 0;
-            if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return SetError(FBN_ERR_NODEV, "no HIP device visible");
-            if (device >= n) return SetError(FBN_ERR_NODEV, "device %d out of range (%d visible)", device, n);
-            FBN_HIP(hipSetDevice(device));
-            hipDeviceProp_t prop;
-            FBN_HIP(hipGetDeviceProperties(&prop, device));
-            if (!strstr(prop.gcnArchName, "gfx950"))
-                return SetError(FBN_ERR_NODEV, "device %d is %s; libfastbn is built for gfx950 only", device, prop.gcnArchName);
             int r;
-            if ((r = Upload(s->nodes, s->M.nodes)) || (r = Upload(s->par, s->M.par)) || (r = Upload(s->prob, s->M.prob)) ||
+            if ((r = fbn::CheckDevice(device, nullptr)) || (r = Upload(s->nodes, s->M.nodes)) || (r = Upload(s->par, s->M.par)) || (r = Upload(s->prob, s->M.prob)) ||
                 (r = Upload(s->cdf, s->M.cdf)) || (r = Upload(s->ent, s->M.ent)) || (r = Upload(s->dom, s->M.dom)) ||
                 (r = s->evcheck.ensure(8)))
                 return r;

@@ -1,8 +1,7 @@
 """Config 5 (1000 variables x 100k samples) PC-stable through the C-ABI: median wall time per call
-with level 0's Gram on the hand-written FP4 MFMA kernel (default), on the popcount kernel
-(FBN_CI_GRAM_NO_MFMA) and on rocBLAS int8 (FBN_CI_GRAM_ROCBLAS, the previous round's path).  Each
-variant runs in its own process; under rocprofv3 --kernel-trace --stats the per-kernel times of
-all three land in one summary.  Usage: python tools/gram_timing.py [reps] [variant ...]"""
+with level 0's Gram on the hand-written FP4 MFMA kernel (default) and on the popcount kernel
+(FBN_CI_GRAM_NO_MFMA).  Each variant runs in its own process; under rocprofv3 --kernel-trace --stats
+the per-kernel times of both land in one summary.  Usage: python tools/gram_timing.py [reps] [variant ...]"""
 import ctypes
 import os
 import subprocess
@@ -14,8 +13,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-VARIANTS = {"mfma": {}, "popcount": {"FBN_CI_GRAM_NO_MFMA": "1"}, "rocblas": {"FBN_CI_GRAM_NO_MFMA": "1",
-                                                                           "FBN_CI_GRAM_ROCBLAS": "1"}}
+VARIANTS = {"mfma": {}, "popcount": {"FBN_CI_GRAM_NO_MFMA": "1"}}
 
 
 def run(reps, name):
