@@ -15,6 +15,8 @@ reference's names and argument meaning:
 * ``LikelihoodWeighting(network, num_samples, seed, method="lw" | "pls").infer(evidence)``
   -- the reference's ``-a 5`` / ``-a 4`` stubs (src/main.cpp:97-121); ``Sampler(network).forward_sample(n, seed)``
   generates datasets on the device
+* ``LoopyBeliefPropagation(network, iterations, tol, damping).infer(evidence)``
+  -- the reference's ``-a 7`` stub (src/main.cpp:136-147); exact on polytrees, approximate on loopy graphs
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -29,6 +31,7 @@ from .api import (  # noqa: F401
     ParameterLearning,
     Sampler,
     LikelihoodWeighting,
+    LoopyBeliefPropagation,
     score_marginals,
     family_sizes,
     pdag_to_dag,
@@ -43,6 +46,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -117,6 +117,14 @@ _SIGS = {
     "fbn_lw_debug_samples": [_vp, C.c_int, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp],
     "fbn_sampler_last_kernel_ms": [_vp, _vp],
     "fbn_score_marginals": [_vp, _vp, _vp, _i64, _vp, _vp],
+    "fbn_lbp_create": [_vp, C.c_int, _pp],
+    "fbn_lbp_destroy": [_vp],
+    "fbn_lbp_info": [_vp, _vp, _vp, _vp, _vp],
+    "fbn_lbp_run": [_vp, _vp, _i64, C.c_int, _dbl, _dbl, _vp, _vp, _vp],
+    "fbn_lbp_run_device": [_vp, _vp, _i64, C.c_int, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "fbn_lbp_debug_messages": [_vp, _vp, _i64, C.c_int, _dbl, _vp],
+    "fbn_lbp_set_tuning": [_vp, _i64, C.c_int],
+    "fbn_lbp_last_kernel_ms": [_vp, _vp],
 }
 
 
@@ -176,6 +184,7 @@ lib = _Lib()
 # then host-only handles.
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
+                "LoopyBeliefPropagation": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -937,6 +946,78 @@ class LikelihoodWeighting(Sampler):
         lib.fbn_lw_debug_samples(self._h, self.method, _p(ev), n, self.num_samples, self.seed, int(case_offset),
                                  _p(vals), _p(m), _p(e))
         return vals, m, e
+
+    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
+        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
+        labels, marg = self.infer(evidence)
+        acc = float(np.mean(labels == np.asarray(ground_truths)))
+        if golden is None:
+            return acc
+        mse, hd = score_marginals(self.network, marg, golden)
+        return acc, mse / len(labels), hd / len(labels)
+
+
+class LoopyBeliefPropagation(_Handle):
+    """Loopy belief propagation (fbn_lbp; the reference's -a 7 stub, src/main.cpp:136-147), mirroring
+    JunctionTree: `iterations` flooding sweeps (the reference's propagation length, -d), stopping
+    early once an iteration's residual is <= tol; `damping` in [0, 1) on the factor -> variable
+    messages.  Exact on forests / polytrees, an approximation on loopy graphs.  Works on any DAG, a
+    disconnected learned network included.  device < 0: the host twin (bit-identical results)."""
+
+    _destroy = "fbn_lbp_destroy"
+
+    def __init__(self, network, iterations=2, tol=0.0, damping=0.0, device=0):
+        self.network = network
+        self.iterations, self.tol, self.damping = int(iterations), float(tol), float(damping)
+        self.sum_dom = int(np.sum(network.dims))
+        self.stats = None
+        h = C.c_void_p()
+        lib.fbn_lbp_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def info(self):
+        """dict(edges, msg_doubles, lds_bytes, path): path 0 = messages in LDS, 1 = global workspace."""
+        e, m, b, p = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+        lib.fbn_lbp_info(self._h, C.byref(e), C.byref(m), C.byref(b), C.byref(p))
+        return {"edges": e.value, "msg_doubles": m.value, "lds_bytes": b.value, "path": p.value}
+
+    def infer(self, evidence, marginals=True):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
+        self.stats = (iterations used, last residual) per case."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        labels = np.zeros(n, np.int32)
+        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
+        st = np.zeros((n, 2), np.float64)
+        lib.fbn_lbp_run(self._h, _p(ev), n, self.iterations, self.tol, self.damping, _p(labels), _p(marg), _p(st))
+        self.stats = (st[:, 0].astype(np.int32), st[:, 1].copy())
+        return labels, marg
+
+    def run_device(self, d_evidence_ptr, ncases, d_labels_ptr, d_marg_ptr, d_stats_ptr=None, stream_ptr=None):
+        """Device-resident run (asynchronous on the stream after the evidence check)."""
+        lib.fbn_lbp_run_device(self._h, C.c_void_p(d_evidence_ptr), int(ncases), self.iterations, self.tol,
+                               self.damping, C.c_void_p(d_labels_ptr), C.c_void_p(d_marg_ptr) if d_marg_ptr else None,
+                               C.c_void_p(d_stats_ptr) if d_stats_ptr else None, stream_ptr)
+
+    def debug_messages(self, evidence, iterations):
+        """Both message arrays [ncases][2][msg_doubles] (factor -> variable, then variable ->
+        factor) after exactly `iterations` iterations."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        out = np.zeros((n, 2, self.info()["msg_doubles"]), np.float64)
+        lib.fbn_lbp_debug_messages(self._h, _p(ev), n, int(iterations), self.damping, _p(out))
+        return out
+
+    def set_tuning(self, lds_bytes_max=0, max_groups=0):
+        """fbn_lbp_set_tuning: lds_bytes_max < 0 forces the global message workspace; max_groups caps
+        the persistent grid.  0 = default.  Results do not change."""
+        lib.fbn_lbp_set_tuning(self._h, int(lds_bytes_max), int(max_groups))
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_lbp_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
 
     def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
         """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""

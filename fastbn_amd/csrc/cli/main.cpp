@@ -1,8 +1,10 @@
-// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
+// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|7 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
 // same flags, defaults and "../dataset/" path prefix; -a 0 (PC-stable), -a 2 (junction tree), -a 4
-// (probabilistic logic sampling) and -a 5 (likelihood weighting; -q samples per case, the reference's
-// default 10000) run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL:
-// MultiGpu.h), --depth D (PC-stable max depth, reference default 1000), --seed N (sampling seed, 0).
+// (probabilistic logic sampling), -a 5 (likelihood weighting; -q samples per case, the reference's
+// default 10000) and -a 7 (loopy belief propagation; -d propagation length, the reference's default 2)
+// run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL: MultiGpu.h),
+// --depth D (PC-stable max depth, reference default 1000), --seed N (sampling seed, 0), --tol T and
+// --damping L (LBP: stop once an iteration's residual is <= T, default 0; damping in [0, 1), default 0).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,7 +17,8 @@
 #include "fastbn.h"
 
 int main(int argc, char **argv) {
-    int algorithm = 2, num_threads = 1, group_size = 1, device = 0, depth = 1000, gpus = 1;
+    int algorithm = 2, num_threads = 1, group_size = 1, device = 0, depth = 1000, gpus = 1, propagation_length = 2;
+    double tol = 0.0, damping = 0.0;
     long long num_samples = 10000;
     unsigned long long seed = 0;
     std::string net_file = "alarm/alarm.xml", ref_net_file = "alarm/alarm.bif",
@@ -29,17 +32,21 @@ int main(int argc, char **argv) {
         if (a == "--depth" && i + 1 < argc) { depth = atoi(argv[++i]); continue; }
         if (a == "--prefix" && i + 1 < argc) { prefix = argv[++i]; continue; }
         if (a == "--seed" && i + 1 < argc) { seed = strtoull(argv[++i], nullptr, 10); continue; }
+        if (a == "--tol" && i + 1 < argc) { tol = atof(argv[++i]); continue; }
+        if (a == "--damping" && i + 1 < argc) { damping = atof(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5] [-t threads] [-g group] [-q samples] [-f0 net] [-f1 refnet] "
-                         "[-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] [--prefix DIR]"
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|7] [-t threads] [-g group] [-q samples] [-d length] [-f0 net] "
+                         "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
+                         "[--tol T] [--damping L] [--prefix DIR]"
                       << std::endl;
             return 0;
         case 'a': algorithm = atoi(argv[++i]); break;
         case 't': num_threads = atoi(argv[++i]); break;
         case 'g': group_size = atoi(argv[++i]); break;
         case 'q': num_samples = atoll(argv[++i]); break;
-        case 'm': case 'l': case 'd': ++i; break;  // flags of the other sampling algorithms: accepted
+        case 'd': propagation_length = atoi(argv[++i]); break;  // src/Parameter.cpp:40
+        case 'm': case 'l': ++i; break;  // flags of the other sampling algorithms: accepted
         case 'f':
             switch (argv[i][2]) {
             case '0': net_file = argv[++i]; break;
@@ -153,8 +160,58 @@ int main(int argc, char **argv) {
         std::cout << "accuracy = " << correct / (double)nc << std::endl;
         fbn_sampler_destroy(smp);
         fbn_network_destroy(net);
+    } else if (algorithm == 7) {
+        // the reference's LBP stub (src/main.cpp:136-147): its header lines, then -a 2's result lines
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: loopy belief propagation (LBP) for approximate inference, #threads = " << num_threads
+                  << std::endl
+                  << ", propagation length = " << propagation_length << std::endl
+                  << "\tBN: " << net_file << std::endl
+                  << "\ttesting set: " << test_set_file << std::endl
+                  << "\treference potential table: " << pt_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        fbn_network *net = nullptr;
+        if (fbn_network_load_xmlbif(net_file.c_str(), &net)) return die();
+        int n = 0;
+        fbn_network_num_nodes(net, &n);
+        TestSet tester;
+        if (tester.Load(test_set_file, n)) return die();
+        const int64_t nc = tester.num_instances();
+        std::vector<int32_t> dims(n);
+        fbn_network_dims(net, dims.data());
+        int sum_dom = 0;
+        for (int d : dims) sum_dom += d;
+        std::vector<double> golden = LoadGroundTruth(pt_file, dims, nc);
+        std::cout << "==================================================" << '\n'
+                  << "Begin testing the trained network." << std::endl;
+        fbn_lbp *lbp = nullptr;
+        if (fbn_lbp_create(net, device, &lbp)) return die();
+        std::vector<int32_t> predictions((size_t)nc);
+        std::vector<double> marginals((size_t)nc * sum_dom), stats((size_t)nc * 2);
+        if (fbn_lbp_run(lbp, tester.evidence.data(), nc, propagation_length, tol, damping, predictions.data(),
+                        marginals.data(), stats.data()))
+            return die();
+        float kms = 0.f;
+        const bool timed = fbn_lbp_last_kernel_ms(lbp, &kms) == 0;  // not on the host path (--device -1)
+        double mse = 0, hd = 0, iters = 0;
+        if (fbn_score_marginals(net, marginals.data(), golden.data(), nc, &mse, &hd)) return die();
+        int64_t correct = 0;
+        for (int64_t c = 0; c < nc; ++c) correct += predictions[c] == tester.ground_truths[c], iters += stats[2 * c];
+        std::cout << "average MSE = " << mse / nc << std::endl;
+        std::cout << "average HD = " << hd / nc << std::endl;
+        std::cout << "==================================================" << std::endl;
+        if (timed)
+            std::cout << "lbp: device kernel " << kms * 1e-3 << " s, " << iters / (kms * 1e-3) << " case-iterations/s"
+                      << std::endl;
+        std::cout << "accuracy = " << correct / (double)nc << std::endl;
+        fbn_lbp_destroy(lbp);
+        fbn_network_destroy(net);
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4 and 5)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5 and 7)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

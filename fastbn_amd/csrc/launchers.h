@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits.hip,
-// ci_gram_mfma.hip) and by every caller (capi_*.hip, sample.hip), so a definition that disagrees with
+// ci_gram_mfma.hip, lbp.hip) and by every caller (capi_*.hip, sample.hip), so a definition that disagrees with
 // its declaration does not compile.  Internal to libfastbn.  (pc_small.h and param_counts.h carry
 // their own kernels' launchers.)
 #ifndef FBN_LAUNCHERS_H
@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "jt_program.h"
+#include "lbp_model.h"
 
 extern "C" hipError_t fbn_jt_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
                                     const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
@@ -104,5 +105,8 @@ extern "C" hipError_t fbn_jt_lds_launch(const JtOp *ops, int nops, const int32_t
                                         long long spill_off, int nc, int cap, bool spill, int force_exact,
                                         const int *flags, int grid, unsigned long long *prof, int vmajor,
                                         hipStream_t stream);
+// lds != 0: the messages in lds_bytes of LDS per workgroup; else in a->ws, 3 * a->M doubles per workgroup
+extern "C" hipError_t fbn_lbp_launch(const fbn::LbpDeviceArgs *a, int lds, size_t lds_bytes, int grid,
+                                     hipStream_t stream);
 
 #endif

@@ -496,6 +496,66 @@ int fbn_sampler_last_kernel_ms(const fbn_sampler *s, float *ms);
 int fbn_score_marginals(const fbn_network *net, const double *marginals, const double *golden, int64_t ncases,
                         double *mse_sum, double *hd_sum);
 
+/* ------------------------------------------------------------------ loopy belief propagation
+ * The reference's -a 7 (ALGLBP), which only prints "LBP is under development" (src/main.cpp:136-147);
+ * `iters` is its propagation length, -d (Parameter::propagation_length, include/Parameter.h:33,
+ * src/Parameter.cpp:40, default 2).  Sum-product message passing on the factor graph of the families:
+ * EXACT on a forest / polytree once the iterations reach its diameter, an APPROXIMATION on a graph with
+ * loops (no JT-like accuracy: see DESIGN.md 5.6 for measured errors).  It needs only the families and
+ * their CPTs, so it runs where fbn_jt_plan_create refuses (a disconnected moral graph, a plan past
+ * the JT kernels' limits), does not sample and does not depend on a seed.
+ *
+ * Factor graph: one factor per node f over (f, GIVEN parents in the node's own order) with the table
+ * P[pc * d + q] ((count + 1) / (total + |dom|); pc over the GIVEN parents, last fastest).  Edges
+ * (f, slot), f ascending, slot ascending (slot 0 = f), carry a factor -> variable message m and a
+ * variable -> factor message mu of dom(x) doubles each; M = the sum of dom(x) over the edges.
+ * Start: every entry 1.0 / d; an observed x = e sends mu = indicator of e throughout.
+ * One iteration (flooding): (1) for every edge on an unobserved variable and every q,
+ *   raw(q) = sum over the cells c with x_slot(c) = q, ascending c, from 0.0, of
+ *            ((P[c] * mu_u1[x_u1(c)]) * mu_u2[..]) ... over the other slots u in ascending order,
+ *   Z = sum_q raw(q) in ascending q, new = raw / Z, with damping != 0: (1.0 - damping) * new + damping * old;
+ * (2) for every unobserved x, every edge (f, s) on it and every q, raw(q) = the product from 1.0 of
+ *   m_g(q) over the other edges on x in ascending order, normalised the same way, undamped.
+ * The residual of an iteration is max |new - old| over every entry written.  The run stops after
+ * `iters` iterations or after the first whose residual is <= tol.  The belief of an unobserved x is the
+ * product from 1.0 of m_g(q) over all its edges, divided by its sum in ascending q.
+ *   marginals [ncases][sum_dom] fp64 (or NULL), zeros for an observed variable (fbn_jt_run's convention);
+ *   labels [ncases] = arg-max of variable 0's row (strict '>' from state 0, as fbn_jt_run);
+ *   stats [ncases][2] fp64 (or NULL) = iterations used, last residual.
+ * A case in which some Z is 0 or not finite (underflow of a product over very many neighbours) gets
+ * a row of zeros, label -1 and residual +inf, never a NaN; other cases are unaffected.
+ * Only +, *, /, fabs and comparisons in the stated order: host twin and device agree bit for bit, as
+ * do two runs and any split of a batch.
+ * Limits: FBN_PARAM_MAX_CELLS table cells in all, else FBN_ERR_LIMIT; a cyclic network is FBN_ERR_ARG.
+ * iters < 1, tol < 0 or NaN, damping outside [0, 1): FBN_ERR_ARG. */
+typedef struct fbn_lbp fbn_lbp;
+/* Flatten the network and upload it to `device` once.  device < 0: a host-only handle that runs the
+ * same algorithm on CPU threads (bit-identical); its *_device entry returns FBN_ERR_NODEV. */
+int fbn_lbp_create(const fbn_network *net, int device, fbn_lbp **out);
+int fbn_lbp_destroy(fbn_lbp *s);
+/* edges E, message doubles M, bytes one case's messages take in LDS, and the path the next run
+ * takes: 0 = messages in LDS, 1 = in a per-workgroup global workspace (sized by the grid). */
+int fbn_lbp_info(const fbn_lbp *s, int64_t *edges, int64_t *msg_doubles, int64_t *lds_bytes, int *path /*0 LDS, 1 global*/);
+/* evidence [ncases][V] int8, -1 = unobserved, every code -1 or < the node's state count (checked
+ * before anything indexes with it: FBN_ERR_ARG naming the first bad case / node).  Host arrays,
+ * synchronous.  Replaces the LBP stub of src/main.cpp:136-147. */
+int fbn_lbp_run(fbn_lbp *s, const int8_t *evidence, int64_t ncases, int iters, double tol, double damping,
+                int32_t *labels, double *marginals /*or NULL*/, double *stats /*[ncases][2] or NULL*/);
+/* The same with device-resident buffers; asynchronous on hip_stream after the evidence check (one
+ * stream sync, as fbn_jt_run_device's).  d_marginals / d_stats may be NULL. */
+int fbn_lbp_run_device(fbn_lbp *s, const int8_t *d_evidence, int64_t ncases, int iters, double tol, double damping,
+                       int32_t *d_labels, double *d_marginals, double *d_stats, void *hip_stream);
+/* Testing interface: both message arrays [ncases][2][M] (m, then mu) after exactly `iters`
+ * iterations (no tolerance), ncases * 2 * M <= 2^24.  Host arrays.  Replaces no reference interface. */
+int fbn_lbp_debug_messages(fbn_lbp *s, const int8_t *evidence, int64_t ncases, int iters, double damping, double *messages);
+/* Kernel tuning (an explicit API, not an environment variable).  lds_bytes_max: the most LDS a case's
+ * messages may take before they go to the global workspace; 0 = default (64 KiB, also the maximum),
+ * < 0 forces the global path.  max_groups: cap of the persistent grid, 0 = default.  Results do not
+ * depend on either. */
+int fbn_lbp_set_tuning(fbn_lbp *s, int64_t lds_bytes_max, int max_groups);
+/* Device kernel time (ms, hipEvent) of the handle's last launch. */
+int fbn_lbp_last_kernel_ms(const fbn_lbp *s, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
