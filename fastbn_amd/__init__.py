@@ -17,6 +17,9 @@ reference's names and argument meaning:
   generates datasets on the device
 * ``LoopyBeliefPropagation(network, iterations, tol, damping).infer(evidence)``
   -- the reference's ``-a 7`` stub (src/main.cpp:136-147); exact on polytrees, approximate on loopy graphs
+* ``EPISBN(network, num_samples, iterations, tol, damping, eps, seed).infer(evidence)``
+  -- the reference's ``-a 6`` stub (src/main.cpp:123-134): LBP's messages as the importance function of
+  an unbiased sampler
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -32,6 +35,7 @@ from .api import (  # noqa: F401
     Sampler,
     LikelihoodWeighting,
     LoopyBeliefPropagation,
+    EPISBN,
     score_marginals,
     family_sizes,
     pdag_to_dag,
@@ -46,6 +50,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

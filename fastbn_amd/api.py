@@ -125,6 +125,14 @@ _SIGS = {
     "fbn_lbp_debug_messages": [_vp, _vp, _i64, C.c_int, _dbl, _vp],
     "fbn_lbp_set_tuning": [_vp, _i64, C.c_int],
     "fbn_lbp_last_kernel_ms": [_vp, _vp],
+    "fbn_epis_create": [_vp, C.c_int, _pp],
+    "fbn_epis_destroy": [_vp],
+    "fbn_epis_run": [_vp, _vp, _i64, _i64, C.c_uint64, _i64, C.c_int, _dbl, _dbl, _dbl, _vp, _vp, _vp],
+    "fbn_epis_run_device": [_vp, _vp, _i64, _i64, C.c_uint64, _i64, C.c_int, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "fbn_epis_debug_samples": [_vp, _vp, _i64, _i64, C.c_uint64, _i64, C.c_int, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "fbn_epis_set_tuning": [_vp, _i64],
+    "fbn_epis_info": [_vp, _vp, _vp],
+    "fbn_epis_last_kernel_ms": [_vp, _vp, _vp],
 }
 
 
@@ -184,7 +192,7 @@ lib = _Lib()
 # then host-only handles.
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
-                "LoopyBeliefPropagation": 2,
+                "LoopyBeliefPropagation": 2, "EPISBN": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -1018,6 +1026,96 @@ class LoopyBeliefPropagation(_Handle):
         ms = C.c_float()
         lib.fbn_lbp_last_kernel_ms(self._h, C.byref(ms))
         return ms.value
+
+    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
+        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
+        labels, marg = self.infer(evidence)
+        acc = float(np.mean(labels == np.asarray(ground_truths)))
+        if golden is None:
+            return acc
+        mse, hd = score_marginals(self.network, marg, golden)
+        return acc, mse / len(labels), hd / len(labels)
+
+
+class EPISBN(_Handle):
+    """EPIS-BN (fbn_epis; the reference's -a 6 stub, src/main.cpp:123-134), mirroring JunctionTree:
+    `iterations` sweeps of loopy belief propagation (tol, damping as LoopyBeliefPropagation), then
+    importance sampling with num_samples samples per case (-q) from each CPT row times the lambda
+    message LBP left on the variable.  eps: the cutoff in [0, 1), None = the defaults by state count.
+    iterations=0 is likelihood weighting's draws.  Unbiased; works on any DAG, a disconnected learned
+    network included.  device < 0: the host twin (bit-identical results)."""
+
+    _destroy = "fbn_epis_destroy"
+
+    def __init__(self, network, num_samples=10000, iterations=20, tol=0.0, damping=0.0, eps=None, seed=0, device=0):
+        self.network = network
+        self.num_samples, self.seed = int(num_samples), int(seed)
+        self.iterations, self.tol, self.damping = int(iterations), float(tol), float(damping)
+        self.eps = -1.0 if eps is None else float(eps)
+        if eps is not None and self.eps < 0.0:  # the C entry reads a negative eps as "the defaults"
+            err = FastBNError(f"eps {eps!r}: in [0, 1), or None for the defaults")
+            err.code = -1  # FBN_ERR_ARG
+            raise err
+        self.sum_dom = int(np.sum(network.dims))
+        self.stats = None
+        h = C.c_void_p()
+        lib.fbn_epis_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def _run_args(self, n, case_offset):
+        return (n, self.num_samples, self.seed, int(case_offset), self.iterations, self.tol, self.damping, self.eps)
+
+    def infer(self, evidence, marginals=True, case_offset=0):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
+        self.stats = (log_evidence, ess, LBP iterations used, LBP residual) per case.  case_offset: the
+        global index of the first case (a batch split over calls gives the bits of the whole batch)."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        labels = np.zeros(n, np.int32)
+        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
+        st = np.zeros((n, 4), np.float64)
+        lib.fbn_epis_run(self._h, _p(ev), *self._run_args(n, case_offset), _p(labels), _p(marg), _p(st))
+        self.stats = (st[:, 0].copy(), st[:, 1].copy(), st[:, 2].astype(np.int32), st[:, 3].copy())
+        return labels, marg
+
+    def run_device(self, d_evidence_ptr, ncases, d_labels_ptr, d_marg_ptr=None, d_stats_ptr=None, case_offset=0,
+                   stream_ptr=None):
+        """Device-resident run (two launches, asynchronous on the stream after the evidence check);
+        d_stats [ncases][4]."""
+        lib.fbn_epis_run_device(self._h, C.c_void_p(d_evidence_ptr), *self._run_args(int(ncases), case_offset),
+                                C.c_void_p(d_labels_ptr), C.c_void_p(d_marg_ptr) if d_marg_ptr else None,
+                                C.c_void_p(d_stats_ptr) if d_stats_ptr else None, stream_ptr)
+
+    def debug_samples(self, evidence, case_offset=0):
+        """The samples behind infer(evidence): (values uint8 [V][ncases * S], mantissas fp64, exponents
+        int32 [ncases * S], lambda rows fp64 [ncases][sum_dom]); sample s of case c at c * S + s."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        tot = n * self.num_samples
+        vals = np.zeros((self.network.num_nodes, tot), np.uint8)
+        m = np.zeros(tot, np.float64)
+        e = np.zeros(tot, np.int32)
+        lam = np.zeros((n, self.sum_dom), np.float64)
+        lib.fbn_epis_debug_samples(self._h, _p(ev), *self._run_args(n, case_offset), _p(vals), _p(m), _p(e), _p(lam))
+        return vals, m, e, lam
+
+    def set_tuning(self, lds_bytes_max=0):
+        """fbn_epis_set_tuning: lds_bytes_max < 0 reads the lambda rows from global memory instead of
+        LDS; 0 = default.  Results do not change."""
+        lib.fbn_epis_set_tuning(self._h, int(lds_bytes_max))
+
+    def info(self):
+        """dict(lds_bytes, path): path 0 = the lambda row in LDS, 1 = in global memory."""
+        b, p = C.c_int64(), C.c_int()
+        lib.fbn_epis_info(self._h, C.byref(b), C.byref(p))
+        return {"lds_bytes": b.value, "path": p.value}
+
+    def last_kernel_ms(self):
+        """(LBP kernel ms, sampling kernel ms) of the last run."""
+        a, b = C.c_float(), C.c_float()
+        lib.fbn_epis_last_kernel_ms(self._h, C.byref(a), C.byref(b))
+        return a.value, b.value
 
     def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
         """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""

@@ -24,7 +24,7 @@ struct fbn_lbp {
     int device = -1, num_cu = 0;
     int64_t lds_bytes_max = kLbpLdsDefault;
     int max_groups = 0;
-    DevBuf edges, terms, bin_edge, order, var_off, var_moff, marg_var, marg_off, prob, dom, evcheck, ws;
+    DevBuf edges, terms, bin_edge, order, var_off, var_moff, marg_var, marg_off, self_moff, prob, dom, evcheck, ws;
     DevBuf evid, labels, marg, stats, msgs;  // staging of the host-buffer entries
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -46,13 +46,16 @@ int Upload(DevBuf &b, const std::vector<T> &v) {
     return FBN_OK;
 }
 
+// d_lambda: LbpDeviceArgs::lambda or NULL.  checked: the caller has range-checked the evidence already.
 int LbpDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double tol, double damping, int32_t *d_labels,
-              double *d_marg, double *d_stats, double *d_msgs, hipStream_t st) {
+              double *d_marg, double *d_stats, double *d_msgs, hipStream_t st, double *d_lambda = nullptr,
+              bool checked = false) {
     s->streams_used.insert(st);
     // as fbn_jt_run_device's check: on the device, one stream sync
-    if (int rc = fbn::EvidenceCheckDevice(d_ev, ncases, s->M.V, s->dom.as<int32_t>(), s->M.dom.data(),
-                                          s->evcheck.as<unsigned long long>(), st))
-        return rc;
+    if (!checked)
+        if (int rc = fbn::EvidenceCheckDevice(d_ev, ncases, s->M.V, s->dom.as<int32_t>(), s->M.dom.data(),
+                                              s->evcheck.as<unsigned long long>(), st))
+            return rc;
     const bool lds = s->lds_path();
     int per_cu = kLbpGroupsPerCu;
     if (lds) per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(per_cu, 160 * 1024 / std::max<int64_t>(1, s->lds_bytes())));
@@ -71,6 +74,7 @@ int LbpDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double 
     a.ncases = ncases, a.iters = iters, a.tol = tol, a.damping = damping;
     a.labels = d_labels, a.marg = d_marg, a.stats = d_stats, a.messages = d_msgs;
     a.ws = s->ws.as<double>();
+    a.lambda = d_lambda, a.self_moff = s->self_moff.as<int32_t>();
     FBN_HIP(hipEventRecord(s->ev0, st));
     FBN_HIP(fbn_lbp_launch(&a, lds ? 1 : 0, (size_t)s->lds_bytes(), (int)grid, st));
     FBN_HIP(hipEventRecord(s->ev1, st));
@@ -107,6 +111,18 @@ int LbpHostBuffers(fbn_lbp *s, const int8_t *evidence, int64_t ncases, int iters
 
 }  // namespace
 
+namespace fbn {
+
+const LbpModel &LbpModelOf(const fbn_lbp *s) { return s->M; }
+
+int LbpLambdaDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double tol, double damping,
+                    int32_t *d_labels, double *d_stats, double *d_lambda, void *hip_stream) {
+    return LbpDevice(s, d_ev, ncases, iters, tol, damping, d_labels, nullptr, d_stats, nullptr,
+                     static_cast<hipStream_t>(hip_stream), d_lambda, true);
+}
+
+}  // namespace fbn
+
 extern "C" {
 
 int fbn_lbp_create(const fbn_network *net, int device, fbn_lbp **out) {
@@ -123,6 +139,7 @@ int fbn_lbp_create(const fbn_network *net, int device, fbn_lbp **out) {
                 (r = Upload(s->order, s->M.order)) ||
                 (r = Upload(s->var_off, s->M.var_off)) || (r = Upload(s->var_moff, s->M.var_moff)) ||
                 (r = Upload(s->marg_var, s->M.marg_var)) || (r = Upload(s->marg_off, s->M.marg_off)) ||
+                (r = Upload(s->self_moff, s->M.self_moff)) ||
                 (r = Upload(s->prob, s->M.prob)) || (r = Upload(s->dom, s->M.dom)) || (r = s->evcheck.ensure(8)))
                 return r;
             FBN_HIP(hipEventCreate(&s->ev0));

@@ -1,10 +1,11 @@
-// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|7 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
+// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|6|7 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
 // same flags, defaults and "../dataset/" path prefix; -a 0 (PC-stable), -a 2 (junction tree), -a 4
 // (probabilistic logic sampling), -a 5 (likelihood weighting; -q samples per case, the reference's
-// default 10000) and -a 7 (loopy belief propagation; -d propagation length, the reference's default 2)
-// run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL: MultiGpu.h),
+// default 10000), -a 6 (EPIS-BN; -q samples per case after -d iterations of LBP) and -a 7 (loopy belief
+// propagation; -d propagation length, the reference's default 2) run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL: MultiGpu.h),
 // --depth D (PC-stable max depth, reference default 1000), --seed N (sampling seed, 0), --tol T and
-// --damping L (LBP: stop once an iteration's residual is <= T, default 0; damping in [0, 1), default 0).
+// --damping L (LBP: stop once an iteration's residual is <= T, default 0; damping in [0, 1), default 0),
+// --eps E (EPIS-BN's cutoff in [0, 1); default: by state count).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,7 +19,7 @@
 
 int main(int argc, char **argv) {
     int algorithm = 2, num_threads = 1, group_size = 1, device = 0, depth = 1000, gpus = 1, propagation_length = 2;
-    double tol = 0.0, damping = 0.0;
+    double tol = 0.0, damping = 0.0, eps = -1.0;
     long long num_samples = 10000;
     unsigned long long seed = 0;
     std::string net_file = "alarm/alarm.xml", ref_net_file = "alarm/alarm.bif",
@@ -34,11 +35,12 @@ int main(int argc, char **argv) {
         if (a == "--seed" && i + 1 < argc) { seed = strtoull(argv[++i], nullptr, 10); continue; }
         if (a == "--tol" && i + 1 < argc) { tol = atof(argv[++i]); continue; }
         if (a == "--damping" && i + 1 < argc) { damping = atof(argv[++i]); continue; }
+        if (a == "--eps" && i + 1 < argc) { eps = atof(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|7] [-t threads] [-g group] [-q samples] [-d length] [-f0 net] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7] [-t threads] [-g group] [-q samples] [-d length] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
-                         "[--tol T] [--damping L] [--prefix DIR]"
+                         "[--tol T] [--damping L] [--eps E] [--prefix DIR]"
                       << std::endl;
             return 0;
         case 'a': algorithm = atoi(argv[++i]); break;
@@ -160,6 +162,56 @@ int main(int argc, char **argv) {
         std::cout << "accuracy = " << correct / (double)nc << std::endl;
         fbn_sampler_destroy(smp);
         fbn_network_destroy(net);
+    } else if (algorithm == 6) {
+        // the reference's EPIS-BN stub (src/main.cpp:123-134): its header lines, then -a 2's result lines
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: EPIS-BN for approximate inference, #threads = " << num_threads << std::endl
+                  << "#samples = " << num_samples << ", propagation length = " << propagation_length << std::endl
+                  << "\tBN: " << net_file << std::endl
+                  << "\ttesting set: " << test_set_file << std::endl
+                  << "\treference potential table: " << pt_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        fbn_network *net = nullptr;
+        if (fbn_network_load_xmlbif(net_file.c_str(), &net)) return die();
+        int n = 0;
+        fbn_network_num_nodes(net, &n);
+        TestSet tester;
+        if (tester.Load(test_set_file, n)) return die();
+        const int64_t nc = tester.num_instances();
+        std::vector<int32_t> dims(n);
+        fbn_network_dims(net, dims.data());
+        int sum_dom = 0;
+        for (int d : dims) sum_dom += d;
+        std::vector<double> golden = LoadGroundTruth(pt_file, dims, nc);
+        std::cout << "==================================================" << '\n'
+                  << "Begin testing the trained network." << std::endl;
+        fbn_epis *ep = nullptr;
+        if (fbn_epis_create(net, device, &ep)) return die();
+        std::vector<int32_t> predictions((size_t)nc);
+        std::vector<double> marginals((size_t)nc * sum_dom), stats((size_t)nc * 4);
+        if (fbn_epis_run(ep, tester.evidence.data(), nc, num_samples, seed, 0, propagation_length, tol, damping, eps,
+                         predictions.data(), marginals.data(), stats.data()))
+            return die();
+        float lms = 0.f, sms = 0.f;
+        const bool timed = fbn_epis_last_kernel_ms(ep, &lms, &sms) == 0;  // not on the host path (--device -1)
+        double mse = 0, hd = 0, ess = 0;
+        if (fbn_score_marginals(net, marginals.data(), golden.data(), nc, &mse, &hd)) return die();
+        int64_t correct = 0;
+        for (int64_t c = 0; c < nc; ++c) correct += predictions[c] == tester.ground_truths[c], ess += stats[4 * c + 1];
+        std::cout << "average MSE = " << mse / nc << std::endl;
+        std::cout << "average HD = " << hd / nc << std::endl;
+        std::cout << "average ESS = " << ess / nc << std::endl;
+        std::cout << "==================================================" << std::endl;
+        if (timed)
+            std::cout << "epis: device kernels lbp " << lms * 1e-3 << " s, sampling " << sms * 1e-3 << " s, "
+                      << (double)nc * (double)num_samples / (sms * 1e-3) << " samples/s" << std::endl;
+        std::cout << "accuracy = " << correct / (double)nc << std::endl;
+        fbn_epis_destroy(ep);
+        fbn_network_destroy(net);
     } else if (algorithm == 7) {
         // the reference's LBP stub (src/main.cpp:136-147): its header lines, then -a 2's result lines
         std::cout << "===============================" << std::endl
@@ -211,7 +263,7 @@ int main(int argc, char **argv) {
         fbn_lbp_destroy(lbp);
         fbn_network_destroy(net);
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5 and 7)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6 and 7)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

@@ -3,8 +3,8 @@
 //
 // One evidence case per wave (64-thread workgroups), a persistent grid that strides over the cases.
 // The case's two message arrays and one array of unnormalised values, 3 M doubles, live in LDS
-// (lbp_kernel<true>) or, for a network whose 24 M bytes exceed the LDS budget, in the workgroup's
-// slice of a global workspace sized by the grid (lbp_kernel<false>).  Lanes take message entries
+// (lbp_kernel<true, .>) or, for a network whose 24 M bytes exceed the LDS budget, in the workgroup's
+// slice of a global workspace sized by the grid (lbp_kernel<false, .>).  Lanes take message entries
 // (edge, q) in strides of 64, in the model's cost order (a pass of 64 entries lasts as long as its
 // heaviest, so entries of similar cost go together).  A half-step is two passes with a barrier between them: every lane
 // stores the unnormalised value of its entries, then every lane adds the d values of its entry's
@@ -29,7 +29,9 @@ __device__ __forceinline__ double wave_fmax(double x) {
     return x;
 }
 
-template <bool LDS>
+// LAMBDA: the run also writes EPIS-BN's importance function (LbpDeviceArgs::lambda); without it the
+// kernel is fbn_lbp_run's, instruction for instruction what it was before that output existed
+template <bool LDS, bool LAMBDA>
 __global__ __launch_bounds__(64) void lbp_kernel(LbpDeviceArgs A) {
     extern __shared__ __align__(16) double lbp_lds[];
     const int lane = threadIdx.x, V = A.V, SD = A.SD, M = A.M;
@@ -127,6 +129,11 @@ __global__ __launch_bounds__(64) void lbp_kernel(LbpDeviceArgs A) {
         }
         if (A.messages)
             for (int j = lane; j < 2 * M; j += 64) A.messages[(size_t)c * 2 * (size_t)M + j] = m[j];
+        if (LAMBDA)  // every variable's message into its own family
+            for (int j = lane; j < SD; j += 64) {
+                const int x = A.marg_var[j];
+                A.lambda[(size_t)c * SD + j] = bad ? 1.0 : mu[A.self_moff[x] + j - A.marg_off[x]];
+            }
         __syncthreads();  // the next case's initialisation overwrites what other lanes still read
     }
 }
@@ -134,9 +141,13 @@ __global__ __launch_bounds__(64) void lbp_kernel(LbpDeviceArgs A) {
 }  // namespace
 
 extern "C" hipError_t fbn_lbp_launch(const LbpDeviceArgs *a, int lds, size_t lds_bytes, int grid, hipStream_t stream) {
-    if (lds)
-        hipLaunchKernelGGL(lbp_kernel<true>, dim3((unsigned)grid), dim3(64), lds_bytes, stream, *a);
+    if (lds && a->lambda)
+        hipLaunchKernelGGL((lbp_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds_bytes, stream, *a);
+    else if (lds)
+        hipLaunchKernelGGL((lbp_kernel<true, false>), dim3((unsigned)grid), dim3(64), lds_bytes, stream, *a);
+    else if (a->lambda)
+        hipLaunchKernelGGL((lbp_kernel<false, true>), dim3((unsigned)grid), dim3(64), 0, stream, *a);
     else
-        hipLaunchKernelGGL(lbp_kernel<false>, dim3((unsigned)grid), dim3(64), 0, stream, *a);
+        hipLaunchKernelGGL((lbp_kernel<false, false>), dim3((unsigned)grid), dim3(64), 0, stream, *a);
     return hipGetLastError();
 }

@@ -46,6 +46,7 @@ int BuildLbpModel(const Network &net, LbpModel &M) {
     M.cells = cells;
     M.prob.resize((size_t)cells);
     M.marg_off.resize(V);
+    M.self_moff.resize(V);
     for (int v = 0; v < V; ++v) {
         M.marg_off[v] = M.sum_dom;
         M.marg_var.insert(M.marg_var.end(), net.dom[v], v);
@@ -76,6 +77,7 @@ int BuildLbpModel(const Network &net, LbpModel &M) {
         }
         std::vector<int32_t> smoff(ns);
         for (int j = 0; j < ns; ++j) smoff[j] = moff, moff += net.dom[var[j]];
+        M.self_moff[f] = smoff[0];
         for (int j = 0; j < ns; ++j) {
             LbpEdge e;
             e.x = var[j], e.d = net.dom[var[j]], e.moff = smoff[j], e.toff = (int32_t)toff;
@@ -146,7 +148,7 @@ int Threads() {
 }  // namespace
 
 int HostLbp(const LbpModel &M, const int8_t *ev, int64_t ncases, int iters, double tol, double damping,
-            int32_t *labels, double *marg, double *stats, double *messages) {
+            int32_t *labels, double *marg, double *stats, double *messages, double *lambda) {
     if (ncases == 0) return FBN_OK;
     const int V = M.V, SD = M.sum_dom;
     const size_t MM = (size_t)M.M;
@@ -222,6 +224,11 @@ int HostLbp(const LbpModel &M, const int8_t *ev, int64_t ncases, int iters, doub
                 stats[2 * c + 1] = bad ? std::numeric_limits<double>::infinity() : res;
             }
             if (messages) std::copy(m, m + 2 * MM, messages + (size_t)c * 2 * MM);
+            if (lambda)
+                for (int j = 0; j < SD; ++j) {
+                    const int x = M.marg_var[j];
+                    lambda[(size_t)c * SD + j] = bad ? 1.0 : mu[M.self_moff[x] + j - M.marg_off[x]];
+                }
         }
     };
     const int T = (int)std::min<int64_t>(Threads(), ncases);

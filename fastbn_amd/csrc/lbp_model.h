@@ -111,6 +111,7 @@ struct LbpModel {
     std::vector<int32_t> var_moff;   // the edges on a variable, ascending: their moff
     std::vector<int32_t> marg_var;   // marginal entry -> variable
     std::vector<int32_t> marg_off;   // [V] first marginal entry
+    std::vector<int32_t> self_moff;  // [V] moff of edge (f = x, slot 0): x's message into its own family
     std::vector<double> prob;
 };
 // the kernel's arguments (device pointers): the model, one batch, where the messages live
@@ -129,6 +130,10 @@ struct LbpDeviceArgs {
     double *stats;     // [ncases][2] or NULL
     double *messages;  // [ncases][2][M] or NULL
     double *ws;        // global path: [grid][3][M]
+    // EPIS-BN's importance function (epis_model.h), or NULL: lambda [ncases][SD], entry (x, q) = mu of
+    // edge (f = x, slot 0) at q as the run leaves it, a row of 1.0 for a case that failed
+    double *lambda;
+    const int32_t *self_moff;
 };
 struct Network;
 // FBN_ERR_ARG for a cyclic network, FBN_ERR_LIMIT past FBN_PARAM_MAX_CELLS table cells
@@ -140,10 +145,21 @@ int CheckLbpArgs(int64_t ncases, int iters, double tol, double damping);
 int CheckLbpEvidence(const LbpModel &M, const int8_t *ev, int64_t ncases);
 // The algorithm over cases on CPU threads, operation for operation what the kernel does.  labels
 // [ncases], marg [ncases][sum_dom] or NULL, stats [ncases][2] or NULL, messages [ncases][2][M] or
-// NULL.  tol < 0: never stops early (fbn_lbp_debug_messages).
+// NULL, lambda [ncases][sum_dom] (LbpDeviceArgs::lambda) or NULL.  tol < 0: never stops early
+// (fbn_lbp_debug_messages).
 int HostLbp(const LbpModel &M, const int8_t *ev, int64_t ncases, int iters, double tol, double damping,
-            int32_t *labels, double *marg, double *stats, double *messages);
+            int32_t *labels, double *marg, double *stats, double *messages, double *lambda = nullptr);
 
+}  // namespace fbn
+
+// What EPIS-BN's handle (capi_epis.hip) needs of an fbn_lbp beyond include/fastbn.h (capi_lbp.hip):
+// its model, and a run on the device that writes the lambda rows [ncases][sum_dom] (no marginals;
+// d_stats [ncases][2]) for evidence the caller has range-checked, asynchronous on the stream.
+struct fbn_lbp;
+namespace fbn {
+const LbpModel &LbpModelOf(const fbn_lbp *s);
+int LbpLambdaDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double tol, double damping,
+                    int32_t *d_labels, double *d_stats, double *d_lambda, void *hip_stream);
 }  // namespace fbn
 
 #endif

@@ -32,22 +32,19 @@
 #include "fbn_device.h"
 #include "fbn_internal.h"
 #include "launchers.h"
+#include "sample_device.h"
 #include "sample_model.h"
 
 using fbn::DevBuf;
+using fbn::DeviceModel;
+using fbn::parent_config;
+using fbn::wave_max;
+using fbn::wave_sum;
 using fbn::SampleNode;
 using fbn::SetError;
 using fbn::U128;
 
 namespace {
-
-struct DeviceModel {
-    const SampleNode *nodes;
-    const int32_t *par;
-    const double *prob, *cdf;
-    const int32_t *ent;
-    int V, sum_dom, d0;  // d0: states of variable 0, the query
-};
 
 struct ForwardArgs {
     DeviceModel M;
@@ -72,15 +69,6 @@ struct LwArgs {
     int32_t *de;
 };
 
-__device__ __forceinline__ int parent_config(const DeviceModel &M, const SampleNode &nd, const uint8_t *vals, int lane) {
-    int pc = 0;
-    for (int j = 0; j < nd.npar; ++j) {
-        const int p = M.par[2 * (nd.poff + j)], dp = M.par[2 * (nd.poff + j) + 1];
-        pc = pc * dp + vals[p * 64 + lane];
-    }
-    return pc;
-}
-
 __global__ __launch_bounds__(64) void sample_forward_kernel(ForwardArgs A) {
     extern __shared__ __align__(16) uint8_t vals[];  // [V][64]
     const int lane = threadIdx.x;
@@ -97,23 +85,6 @@ __global__ __launch_bounds__(64) void sample_forward_kernel(ForwardArgs A) {
         vals[nd.v * 64 + lane] = (uint8_t)q;
         if (active) A.cols[(long long)nd.v * A.n + i] = (uint8_t)q;
     }
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-    return x;
-}
-__device__ __forceinline__ int wave_max(int x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = max(x, __shfl_xor(x, off, 64));
-    return x;
-}
-__device__ __forceinline__ double read_lane(double x, int l) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 __global__ __launch_bounds__(64) void sample_lw_kernel(LwArgs A) {
@@ -164,20 +135,7 @@ __global__ __launch_bounds__(64) void sample_lw_kernel(LwArgs A) {
         sumw = sumw * f + wave_sum(w);
         sumw2 = sumw2 * f * f + wave_sum(w * w);
         __syncthreads();
-        for (int j = lane; j < SD; j += 64) {
-            const int en = A.M.ent[j], q = en & 255;
-            double acc = s0 == 0 ? 0.0 : row[j] * f;
-            const uint4 *xv = reinterpret_cast<const uint4 *>(vals + (en >> 8) * 64);
-#pragma unroll 1  // 16 lanes at a time: unrolled over all 64 the selected terms alone take 128 VGPRs
-            for (int t = 0; t < 4; ++t) {
-                const uint4 b = xv[t];
-                const unsigned wd[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-                for (int l = 0; l < 16; ++l)
-                    acc += (int)((wd[l >> 2] >> (8 * (l & 3))) & 0xFFu) == q ? read_lane(w, 16 * t + l) : 0.0;
-            }
-            row[j] = acc;
-        }
+        fbn::accumulate_marginals(A.M, vals, row, w, f, s0 == 0, lane);
         __syncthreads();
     }
     int lab = -1;

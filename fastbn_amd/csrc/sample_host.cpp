@@ -11,6 +11,9 @@
 // so a case's result depends on (seed, global case index, S) only.  Every variable consumes its
 // position whether or not its draw is used.
 //
+// HostImportance is the inference loop itself: HostLw calls it without an importance function, EPIS-BN's
+// twin (epis_host.cpp) with the lambda rows of its pre-propagation (epis_model.h).
+//
 // The twin repeats the kernels' arithmetic operation for operation -- 64-sample chunks, the same
 // butterfly and per-entry summation orders, the same power-of-two rescaling -- so the two agree bit
 // for bit on (value, mantissa, exponent) and on every sum.
@@ -20,6 +23,7 @@
 #include <cstdlib>
 #include <thread>
 
+#include "epis_model.h"
 #include "fbn_internal.h"
 #include "sample_model.h"
 
@@ -200,6 +204,13 @@ int CheckLwShape(const SamplerModel &M, int method, int64_t ncases, int64_t S, i
 int HostLw(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases, int64_t S, uint64_t seed,
            int64_t case_offset, int32_t *labels, double *marg, double *stats, uint8_t *dbg_vals, double *dbg_m,
            int32_t *dbg_e) {
+    return HostImportance(M, method, ev, ncases, S, seed, case_offset, nullptr, 0.0, nullptr, labels, marg, stats, dbg_vals,
+                          dbg_m, dbg_e);
+}
+
+int HostImportance(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases, int64_t S, uint64_t seed,
+                   int64_t case_offset, const double *lam, double eps, const double *lbp_stats, int32_t *labels,
+                   double *marg, double *stats, uint8_t *dbg_vals, double *dbg_m, int32_t *dbg_e) {
     if (ncases == 0) return FBN_OK;
     const int V = M.V, SD = M.sum_dom;
     const size_t total = (size_t)ncases * (size_t)S;
@@ -231,6 +242,13 @@ int HostLw(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases, 
                             q = evv;
                             int de;
                             mm = frexp(mm * M.prob[(size_t)nd.toff + (size_t)pc * nd.d + q], &de);
+                            ee += de;
+                        } else if (lam) {  // EPIS-BN: draw from P * lambda, weigh by the ratio
+                            double fac;
+                            q = EpisDraw(M.prob.data() + nd.toff + (int64_t)pc * nd.d, lam + c * SD + nd.moff, nd.d,
+                                         EpisCutoff(eps, nd.d), PcgDouble(PcgOutput(s)), &fac);
+                            int de;
+                            mm = frexp(mm * fac, &de);
                             ee += de;
                         } else {
                             q = SelectValue(M.cdf.data() + nd.toff + (int64_t)pc * nd.d, nd.d, PcgDouble(PcgOutput(s)));
@@ -273,8 +291,10 @@ int HostLw(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases, 
             }
             labels[c] = lab;
             if (stats) {
-                stats[2 * c] = sumw > 0.0 ? log(sumw / (double)S) + (double)emax * 0.6931471805599453 : -INFINITY;
-                stats[2 * c + 1] = sumw > 0.0 ? sumw * sumw / sumw2 : 0.0;
+                double *st = stats + (lam ? 4 : 2) * c;
+                st[0] = sumw > 0.0 ? log(sumw / (double)S) + (double)emax * 0.6931471805599453 : -INFINITY;
+                st[1] = sumw > 0.0 ? sumw * sumw / sumw2 : 0.0;
+                if (lam) st[2] = lbp_stats ? lbp_stats[2 * c] : 0.0, st[3] = lbp_stats ? lbp_stats[2 * c + 1] : 0.0;
             }
         }
     });

@@ -106,6 +106,13 @@ int HostForward(const SamplerModel &M, int64_t n, uint64_t seed, uint8_t *cols);
 int HostLw(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases, int64_t S, uint64_t seed,
            int64_t case_offset, int32_t *labels, double *marg, double *stats, uint8_t *dbg_vals, double *dbg_m,
            int32_t *dbg_e);
+// HostLw's loop with an importance function (EPIS-BN, epis_model.h).  lam == NULL: HostLw itself.  Else
+// lam [ncases][sum_dom], method 0: an unobserved variable is drawn by EpisDraw from its table row and
+// its lambda row with cutoff EpisCutoff(eps, d) and the weight takes the draw's factor through the same
+// frexp pair; stats is then [ncases][4], the last two copied from lbp_stats [ncases][2] (NULL: zeros).
+int HostImportance(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases, int64_t S, uint64_t seed,
+                   int64_t case_offset, const double *lam, double eps, const double *lbp_stats, int32_t *labels,
+                   double *marg, double *stats, uint8_t *dbg_vals, double *dbg_m, int32_t *dbg_e);
 // -1 .. dom - 1 everywhere, else FBN_ERR_ARG naming the first bad case / node
 int CheckEvidenceHost(const SamplerModel &M, const int8_t *ev, int64_t ncases);
 // S >= 1, method 0 / 1, and stream positions ((case_offset + ncases) * S + 64) * V below 2^63

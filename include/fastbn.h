@@ -556,6 +556,81 @@ int fbn_lbp_set_tuning(fbn_lbp *s, int64_t lds_bytes_max, int max_groups);
 /* Device kernel time (ms, hipEvent) of the handle's last launch. */
 int fbn_lbp_last_kernel_ms(const fbn_lbp *s, float *ms);
 
+/* ------------------------------------------------------------------ EPIS-BN
+ * The reference's -a 6 (ALGEPISBN, include/Parameter.h:18; its propagation length -d is "for epis-bn
+ * and lbp", :33), which only prints "EPIS-BN is under development" (src/main.cpp:123-134).  Evidence
+ * Pre-propagation Importance Sampling (Yuan & Druzdzel 2003): loopy belief propagation first, then
+ * importance sampling whose proposal for every unobserved variable is its CPT row times the lambda
+ * message LBP left on it.  Unbiased like likelihood weighting for any lambda, deterministic given the
+ * seed, and it runs on every network the sampler takes (disconnected ones included); where LBP is
+ * exact (forests in which every node has at most one parent) every sample carries the same weight.
+ *
+ * Pre-propagation: per evidence case, fbn_lbp_run's algorithm exactly (flooding, `iters` iterations,
+ * stop at tol, damping).  lambda of an unobserved x is the variable -> factor message mu on edge
+ * (f = x, slot 0) as the run leaves it: the normalised product of the factor -> variable messages from
+ * every family in which x is a parent.  iters == 0: no pre-propagation, lambda = 1.0 exactly (the
+ * draws are then likelihood weighting's).  A case whose LBP run fails (some Z zero or not finite)
+ * also gets lambda = 1.0 and residual +inf in its stats, never a NaN.
+ * One draw: stream positions, topological order, parent configuration and the selection rule are
+ * fbn_lw_run's inference map (i * V + k, i = (case_offset + c) * S + s; every variable consumes its
+ * position).  An observed variable is clamped and weighed as in likelihood weighting,
+ * (m, de) = frexp(m * P(ev | pa)), e += de.  An unobserved variable of d states with table row P[0..d)
+ * and lambda[0..d):
+ *   g(q) = P[q] * lambda[q];  Z = sum_q g(q), ascending from 0.0;
+ *   Z zero or not finite: this draw uses g' = P (a likelihood-weighting draw, no cutoff);
+ *   else with cutoff eps > 0: g'(q) = max(g(q), eps * Z); else g' = g;
+ *   c(q) = the running sum of g', ascending from 0.0;  x = u * c(d - 1);
+ *   value = min(#{q : x >= c(q)}, d - 1);
+ *   (m, de) = frexp(m * ((P[value] * c(d - 1)) / g'(value))), e += de
+ *   (a value with g' = 0, reachable only by x == c(d - 1) through rounding, gives m = 0).
+ * Cutoff: eps in [0, 1); eps < 0 selects the defaults by state count after Yuan & Druzdzel: 0.006
+ * below 5 states, 0.001 for 5 to 8, 0.0005 above.  Raise-and-renormalise as written above is this
+ * library's rule; the paper describes replacing small probabilities by the threshold and subtracting
+ * the excess from the largest entry, which differs in form (the weights keep either one unbiased).
+ * Only +, *, /, frexp and comparisons in the stated order: host twin and device agree bit for bit.
+ * Outputs per case as fbn_lw_run (marginals with zeros for observed variables, label by the same
+ * arg-max, emax rescaling, no floating-point atomics, one fixed summation order); stats
+ * [ncases][4] = log_evidence, ess, LBP iterations used, LBP residual (+inf where the case fell back to
+ * lambda = 1; 0, 0 with iters == 0).
+ * Limits and errors are the sampler's and LBP's: 2048 variables, FBN_PARAM_MAX_CELLS table cells
+ * (FBN_ERR_LIMIT), a cyclic network FBN_ERR_ARG, evidence codes checked first (FBN_ERR_ARG naming the
+ * first bad case / node); S < 1, iters < 0, tol < 0 or NaN, damping outside [0, 1), eps >= 1 or NaN:
+ * FBN_ERR_ARG. */
+typedef struct fbn_epis fbn_epis;
+/* Flatten the network for the sampler and for LBP and upload both to `device` once.  device < 0: a
+ * host-only handle that runs the same algorithm on CPU threads (bit-identical); its *_device entry
+ * returns FBN_ERR_NODEV. */
+int fbn_epis_create(const fbn_network *net, int device, fbn_epis **out);
+int fbn_epis_destroy(fbn_epis *s);
+/* Host arrays, synchronous.  marginals / stats may be NULL.  Replaces the EPIS-BN stub of
+ * src/main.cpp:123-134. */
+int fbn_epis_run(fbn_epis *s, const int8_t *evidence, int64_t ncases, int64_t S, uint64_t seed, int64_t case_offset,
+                 int iters, double tol, double damping, double eps, int32_t *labels, double *marginals,
+                 double *stats /*[ncases][4]*/);
+/* The same with device-resident buffers: two launches (LBP, then sampling) on hip_stream,
+ * asynchronous after the evidence check (one stream sync, as fbn_jt_run_device's).  d_marginals /
+ * d_stats may be NULL. */
+int fbn_epis_run_device(fbn_epis *s, const int8_t *d_evidence, int64_t ncases, int64_t S, uint64_t seed,
+                        int64_t case_offset, int iters, double tol, double damping, double eps, int32_t *d_labels,
+                        double *d_marginals, double *d_stats, void *hip_stream);
+/* Testing interface: the samples behind fbn_epis_run for a small batch (ncases * S <= 2^22) as
+ * fbn_lw_debug_samples gives them (values [V][ncases * S], mantissas, exponents [ncases * S]), and the
+ * lambda rows [ncases][sum_dom] the draws used (an observed variable's row is the indicator LBP keeps
+ * for it and is not read).  Host arrays.  Replaces no reference interface. */
+int fbn_epis_debug_samples(fbn_epis *s, const int8_t *evidence, int64_t ncases, int64_t S, uint64_t seed,
+                           int64_t case_offset, int iters, double tol, double damping, double eps, uint8_t *values,
+                           double *mantissas, int32_t *exponents, double *lambda);
+/* Kernel tuning (an explicit API, not an environment variable).  lds_bytes_max: the most LDS the
+ * values (64 V bytes) and the case's lambda row (8 sum_dom bytes) may take together with the row in
+ * LDS; beyond it the row is read from global memory.  0 = default (64 KiB, also the maximum), < 0
+ * forces the global placement.  Results do not depend on it.  fbn_epis_info: those bytes and the
+ * placement the next run takes. */
+int fbn_epis_set_tuning(fbn_epis *s, int64_t lds_bytes_max);
+int fbn_epis_info(const fbn_epis *s, int64_t *lds_bytes, int *path /*0 lambda in LDS, 1 global*/);
+/* Device kernel times (ms, hipEvent) of the handle's last run: the LBP launch (0 with iters == 0)
+ * and the sampling launch. */
+int fbn_epis_last_kernel_ms(const fbn_epis *s, float *lbp_ms, float *sample_ms);
+
 #ifdef __cplusplus
 }
 #endif
