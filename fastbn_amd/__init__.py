@@ -20,6 +20,9 @@ reference's names and argument meaning:
 * ``EPISBN(network, num_samples, iterations, tol, damping, eps, seed).infer(evidence)``
   -- the reference's ``-a 6`` stub (src/main.cpp:123-134): LBP's messages as the importance function of
   an unbiased sampler
+* ``AISBN(network, num_samples, max_updates, interval, eps, seed).infer(evidence)`` and
+  ``SelfImportanceSampling(...)`` -- the reference's ``-a 10`` / ``-a 8`` stubs (src/main.cpp:175-186,
+  :149-160): samplers that learn their importance function from their own weighted samples
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -36,6 +39,8 @@ from .api import (  # noqa: F401
     LikelihoodWeighting,
     LoopyBeliefPropagation,
     EPISBN,
+    AISBN,
+    SelfImportanceSampling,
     score_marginals,
     family_sizes,
     pdag_to_dag,
@@ -50,6 +55,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -133,6 +133,15 @@ _SIGS = {
     "fbn_epis_set_tuning": [_vp, _i64],
     "fbn_epis_info": [_vp, _vp, _vp],
     "fbn_epis_last_kernel_ms": [_vp, _vp, _vp],
+    "fbn_ais_create": [_vp, C.c_int, _pp],
+    "fbn_ais_destroy": [_vp],
+    "fbn_ais_run": [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _dbl, _vp, _vp, _vp],
+    "fbn_ais_run_device": [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _dbl, _vp, _vp, _vp, _vp],
+    "fbn_ais_debug_samples": [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _dbl, _vp, _vp, _vp, _vp],
+    "fbn_ais_set_tuning": [_vp, _i64, C.c_int],
+    "fbn_ais_info": [_vp, _i64, _vp, _vp, _vp, _vp],
+    "fbn_ais_last_kernel_ms": [_vp, _vp],
+    "fbn_ais_eta": [C.c_int, C.c_int, _vp],
 }
 
 
@@ -192,7 +201,7 @@ lib = _Lib()
 # then host-only handles.
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
-                "LoopyBeliefPropagation": 2, "EPISBN": 2,
+                "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -1125,3 +1134,122 @@ class EPISBN(_Handle):
             return acc
         mse, hd = score_marginals(self.network, marg, golden)
         return acc, mse / len(labels), hd / len(labels)
+
+
+class AISBN(_Handle):
+    """AIS-BN (fbn_ais, method 0; the reference's -a 10 stub, src/main.cpp:175-186), mirroring EPISBN:
+    max_updates (-m) learning stages of `interval` (-l) samples, each followed by an update of the
+    importance CPT of the evidence's unobserved ancestors from the stage's weighted family counts,
+    then num_samples (-q) counted samples.  eps: the cutoff in [0, 1), None = the defaults by state
+    count.  max_updates=0 is likelihood weighting's draws.  Unbiased; needs no LBP; works on any DAG,
+    a disconnected learned network included.  device < 0: the host twin (bit-identical results)."""
+
+    _destroy = "fbn_ais_destroy"
+    _method = 0
+
+    def __init__(self, network, num_samples=10000, max_updates=10, interval=2500, eps=None, seed=0, device=0):
+        self.network = network
+        self.num_samples, self.seed = int(num_samples), int(seed)
+        self.max_updates, self.interval = int(max_updates), int(interval)
+        self.eps = -1.0 if eps is None else float(eps)
+        if eps is not None and self.eps < 0.0:  # the C entry reads a negative eps as "the defaults"
+            err = FastBNError(f"eps {eps!r}: in [0, 1), or None for the defaults")
+            err.code = -1  # FBN_ERR_ARG
+            raise err
+        self.sum_dom = int(np.sum(network.dims))
+        self.stats = None
+        h = C.c_void_p()
+        lib.fbn_ais_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    @property
+    def draws_per_case(self):
+        """T: every draw of a case, the learning stages included."""
+        if self._method == 0:
+            return self.max_updates * self.interval + self.num_samples
+        return self.num_samples
+
+    def _run_args(self, n, case_offset):
+        return (n, self.num_samples, self.max_updates, self.interval, self.seed, int(case_offset), self.eps)
+
+    def infer(self, evidence, marginals=True, case_offset=0):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
+        self.stats = (log_evidence, ess, updates applied, ess / n of the first stage) per case.
+        case_offset: the global index of the first case (a batch split over calls gives the bits of the
+        whole batch)."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        labels = np.zeros(n, np.int32)
+        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
+        st = np.zeros((n, 4), np.float64)
+        lib.fbn_ais_run(self._h, self._method, _p(ev), *self._run_args(n, case_offset), _p(labels), _p(marg), _p(st))
+        self.stats = (st[:, 0].copy(), st[:, 1].copy(), st[:, 2].astype(np.int32), st[:, 3].copy())
+        return labels, marg
+
+    def run_device(self, d_evidence_ptr, ncases, d_labels_ptr, d_marg_ptr=None, d_stats_ptr=None, case_offset=0,
+                   stream_ptr=None):
+        """Device-resident run (one launch, asynchronous on the stream after the evidence check);
+        d_stats [ncases][4]."""
+        lib.fbn_ais_run_device(self._h, self._method, C.c_void_p(d_evidence_ptr),
+                               *self._run_args(int(ncases), case_offset), C.c_void_p(d_labels_ptr),
+                               C.c_void_p(d_marg_ptr) if d_marg_ptr else None,
+                               C.c_void_p(d_stats_ptr) if d_stats_ptr else None, stream_ptr)
+
+    def debug_samples(self, evidence, case_offset=0):
+        """Every draw behind infer(evidence): (values uint8 [V][ncases * T], mantissas fp64, exponents
+        int32 [ncases * T], the importance CPT after the last update fp64 [ncases][cells]); draw t of
+        case c at c * T + t, T = draws_per_case."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        tot = n * self.draws_per_case
+        vals = np.zeros((self.network.num_nodes, tot), np.uint8)
+        m = np.zeros(tot, np.float64)
+        e = np.zeros(tot, np.int32)
+        icpt = np.zeros((n, self.info()["state_bytes"] // 16), np.float64)
+        lib.fbn_ais_debug_samples(self._h, self._method, _p(ev), *self._run_args(n, case_offset), _p(vals), _p(m), _p(e),
+                                  _p(icpt))
+        return vals, m, e, icpt
+
+    def set_tuning(self, lds_bytes_max=0, max_workgroups=0):
+        """fbn_ais_set_tuning: lds_bytes_max < 0 keeps the importance CPT and the counts in a global
+        workspace instead of LDS; max_workgroups caps the persistent grid.  0 = default.  Results do not
+        change."""
+        lib.fbn_ais_set_tuning(self._h, int(lds_bytes_max), int(max_workgroups))
+
+    def info(self, ncases=1):
+        """dict(lds_bytes, state_bytes, path, grid): path 0 = the state in LDS, 1 = in global memory;
+        grid = the workgroups a run of ncases cases launches."""
+        b, sb, p, g = C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
+        lib.fbn_ais_info(self._h, int(ncases), C.byref(b), C.byref(sb), C.byref(p), C.byref(g))
+        return {"lds_bytes": b.value, "state_bytes": sb.value, "path": p.value, "grid": g.value}
+
+    def eta(self):
+        """The learning rates eta[0 .. max_updates) the runs use (fbn_ais_eta)."""
+        out = np.zeros(max(self.max_updates, 1), np.float64)
+        lib.fbn_ais_eta(self._method, self.max_updates, _p(out))
+        return out[:self.max_updates]
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_ais_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
+        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
+        labels, marg = self.infer(evidence)
+        acc = float(np.mean(labels == np.asarray(ground_truths)))
+        if golden is None:
+            return acc
+        mse, hd = score_marginals(self.network, marg, golden)
+        return acc, mse / len(labels), hd / len(labels)
+
+
+class SelfImportanceSampling(AISBN):
+    """Self-importance sampling (fbn_ais, method 1; the reference's -a 8 stub, src/main.cpp:149-160):
+    all num_samples (-q) samples are counted; after each full block of `interval` (-l) samples, while
+    samples remain and at most max_updates (-m) times, the importance CPT rows of the evidence's
+    unobserved ancestors are replaced by the cumulative weighted frequencies.  It relies on the
+    cutoff's floor for support, so eps=0 is refused.  Otherwise as AISBN."""
+
+    _method = 1

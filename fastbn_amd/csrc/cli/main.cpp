@@ -1,11 +1,13 @@
-// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|6|7 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
+// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|6|7|8|10 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
 // same flags, defaults and "../dataset/" path prefix; -a 0 (PC-stable), -a 2 (junction tree), -a 4
 // (probabilistic logic sampling), -a 5 (likelihood weighting; -q samples per case, the reference's
 // default 10000), -a 6 (EPIS-BN; -q samples per case after -d iterations of LBP) and -a 7 (loopy belief
-// propagation; -d propagation length, the reference's default 2) run on the GPU.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL: MultiGpu.h),
+// propagation; -d propagation length, the reference's default 2), -a 10 (AIS-BN) and -a 8 (SIS; both: -q
+// samples per case, -m maximum updates, default 10, -l updating interval, default 2,500) run on the GPU.
+// -a 9 ("SISv1") stays refused: the reference defines it nowhere.  Extra flags: --device N, --gpus G (devices N .. N + G - 1, RCCL: MultiGpu.h),
 // --depth D (PC-stable max depth, reference default 1000), --seed N (sampling seed, 0), --tol T and
 // --damping L (LBP: stop once an iteration's residual is <= T, default 0; damping in [0, 1), default 0),
-// --eps E (EPIS-BN's cutoff in [0, 1); default: by state count).
+// --eps E (the cutoff of EPIS-BN, AIS-BN and SIS in [0, 1); default: by state count).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,7 +22,7 @@
 int main(int argc, char **argv) {
     int algorithm = 2, num_threads = 1, group_size = 1, device = 0, depth = 1000, gpus = 1, propagation_length = 2;
     double tol = 0.0, damping = 0.0, eps = -1.0;
-    long long num_samples = 10000;
+    long long num_samples = 10000, max_updating = 10, updating_interval = 2500;  // src/Parameter.cpp:14-15
     unsigned long long seed = 0;
     std::string net_file = "alarm/alarm.xml", ref_net_file = "alarm/alarm.bif",
                 train_set_file = "alarm/alarm_s5000.txt", test_set_file = "alarm/testing_alarm_1k_p20",
@@ -38,7 +40,8 @@ int main(int argc, char **argv) {
         if (a == "--eps" && i + 1 < argc) { eps = atof(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7] [-t threads] [-g group] [-q samples] [-d length] [-f0 net] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+                         "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
                          "[--tol T] [--damping L] [--eps E] [--prefix DIR]"
                       << std::endl;
@@ -48,7 +51,8 @@ int main(int argc, char **argv) {
         case 'g': group_size = atoi(argv[++i]); break;
         case 'q': num_samples = atoll(argv[++i]); break;
         case 'd': propagation_length = atoi(argv[++i]); break;  // src/Parameter.cpp:40
-        case 'm': case 'l': ++i; break;  // flags of the other sampling algorithms: accepted
+        case 'm': max_updating = atoll(argv[++i]); break;       // src/Parameter.cpp:38
+        case 'l': updating_interval = atoll(argv[++i]); break;  // src/Parameter.cpp:39
         case 'f':
             switch (argv[i][2]) {
             case '0': net_file = argv[++i]; break;
@@ -262,8 +266,68 @@ int main(int argc, char **argv) {
         std::cout << "accuracy = " << correct / (double)nc << std::endl;
         fbn_lbp_destroy(lbp);
         fbn_network_destroy(net);
+    } else if (algorithm == 8 || algorithm == 10) {
+        // the reference's SIS / AIS-BN stubs (src/main.cpp:149-160, :175-186): its header lines, then -a 2's result lines
+        std::cout << "===============================" << std::endl
+                  << (algorithm == 8 ? "Algorithm: self importance sampling (SIS) for approximate inference, #threads = "
+                                     : "Algorithm: AIS-BN for approximate inference, #threads = ")
+                  << num_threads << std::endl
+                  << "#samples = " << num_samples << "updating interval = " << updating_interval
+                  << "maximum updating times = " << max_updating << std::endl
+                  << "\tBN: " << net_file << std::endl
+                  << "\ttesting set: " << test_set_file << std::endl
+                  << "\treference potential table: " << pt_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        const int method = algorithm == 8 ? 1 : 0;
+        fbn_network *net = nullptr;
+        if (fbn_network_load_xmlbif(net_file.c_str(), &net)) return die();
+        int n = 0;
+        fbn_network_num_nodes(net, &n);
+        TestSet tester;
+        if (tester.Load(test_set_file, n)) return die();
+        const int64_t nc = tester.num_instances();
+        std::vector<int32_t> dims(n);
+        fbn_network_dims(net, dims.data());
+        int sum_dom = 0;
+        for (int d : dims) sum_dom += d;
+        std::vector<double> golden = LoadGroundTruth(pt_file, dims, nc);
+        std::cout << "==================================================" << '\n'
+                  << "Begin testing the trained network." << std::endl;
+        fbn_ais *ais = nullptr;
+        if (fbn_ais_create(net, device, &ais)) return die();
+        std::vector<int32_t> predictions((size_t)nc);
+        std::vector<double> marginals((size_t)nc * sum_dom), stats((size_t)nc * 4);
+        if (fbn_ais_run(ais, method, tester.evidence.data(), nc, num_samples, max_updating, updating_interval, seed, 0, eps,
+                        predictions.data(), marginals.data(), stats.data()))
+            return die();
+        float kms = 0.f;
+        const bool timed = fbn_ais_last_kernel_ms(ais, &kms) == 0;  // not on the host path (--device -1)
+        double mse = 0, hd = 0, ess = 0;
+        if (fbn_score_marginals(net, marginals.data(), golden.data(), nc, &mse, &hd)) return die();
+        int64_t correct = 0;
+        for (int64_t c = 0; c < nc; ++c) correct += predictions[c] == tester.ground_truths[c], ess += stats[4 * c + 1];
+        const double draws = method == 0 ? (double)max_updating * (double)updating_interval + (double)num_samples
+                                         : (double)num_samples;
+        std::cout << "average MSE = " << mse / nc << std::endl;
+        std::cout << "average HD = " << hd / nc << std::endl;
+        std::cout << "average ESS = " << ess / nc << std::endl;
+        std::cout << "==================================================" << std::endl;
+        if (timed)
+            std::cout << (method == 0 ? "ais-bn: " : "sis: ") << "device kernel " << kms * 1e-3 << " s, "
+                      << (double)nc * draws / (kms * 1e-3) << " samples/s" << std::endl;
+        std::cout << "accuracy = " << correct / (double)nc << std::endl;
+        fbn_ais_destroy(ais);
+        fbn_network_destroy(net);
+    } else if (algorithm == 9) {
+        // SISv1 (ALGSISV1, src/main.cpp:162-173): the reference names it and defines it nowhere, in code or papers
+        std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
+                  << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6 and 7)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8 and 10)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits.hip,
-// ci_gram_mfma.hip, lbp.hip, epis.hip) and by every caller (capi_*.hip, sample.hip), so a definition that disagrees with
+// ci_gram_mfma.hip, lbp.hip, epis.hip, ais.hip) and by every caller (capi_*.hip, sample.hip), so a definition that disagrees with
 // its declaration does not compile.  Internal to libfastbn.  (pc_small.h and param_counts.h carry
 // their own kernels' launchers.)
 #ifndef FBN_LAUNCHERS_H
@@ -115,5 +115,13 @@ struct EpisDeviceArgs;
 }
 extern "C" hipError_t fbn_epis_launch(const fbn::EpisDeviceArgs *a, int lds_lambda, hipStream_t stream);
 extern "C" hipError_t fbn_epis_fill(double *p, long long n, double x, hipStream_t stream);
+// The adaptive samplers' kernel (ais_model.h's arguments): a persistent grid of `grid` one-wave
+// workgroups striding over the cases, lds_bytes of dynamic LDS each; lds_state != 0: the ICPT and the
+// counts in LDS behind the values and the weights, else in a->ws, 2 * a->cells doubles per workgroup.
+namespace fbn {
+struct AisDeviceArgs;
+}
+extern "C" hipError_t fbn_ais_launch(const fbn::AisDeviceArgs *a, int lds_state, size_t lds_bytes, int grid,
+                                     hipStream_t stream);
 
 #endif

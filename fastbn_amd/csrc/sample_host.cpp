@@ -124,33 +124,21 @@ void PcgJump(const PcgStream &R, uint64_t delta, U128 *mult, U128 *plus) {
     *mult = am, *plus = ap;
 }
 
-namespace {
-
-int Threads() {
+int HostThreads() {
     const unsigned hc = std::thread::hardware_concurrency();
     int t = (int)std::max(1u, std::min(16u, hc ? hc : 1u));
     if (const char *e = getenv("OMP_NUM_THREADS")) t = std::max(1, std::min(t, atoi(e)));
     return t;
 }
 
-// fn(begin, end) over [0, n) in contiguous ranges of at least `grain`, in parallel
-template <class F>
-void ParallelRanges(int64_t n, int64_t grain, F fn) {
-    const int T = (int)std::min<int64_t>(Threads(), std::max<int64_t>(1, n / grain));
+void ParallelRanges(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)> &fn) {
+    const int T = (int)std::min<int64_t>(HostThreads(), std::max<int64_t>(1, n / grain));
     std::vector<std::thread> th;
     for (int t = 1; t < T; ++t) th.emplace_back(fn, n * t / T, n * (t + 1) / T);
     fn(0, n / T);
     for (auto &x : th) x.join();
 }
 
-// the parent configuration of node nd from one sample's values (stride between variables: vs)
-inline int ParentConfig(const SamplerModel &M, const SampleNode &nd, const uint8_t *x, size_t vs) {
-    int pc = 0;
-    for (int j = 0; j < nd.npar; ++j) pc = pc * M.par[2 * (nd.poff + j) + 1] + x[(size_t)M.par[2 * (nd.poff + j)] * vs];
-    return pc;
-}
-
-// sum over 64 lanes in the kernels' butterfly order (lane i adds lane i ^ off, off = 32 .. 1)
 double Butterfly(double *a) {
     double t[64];
     for (int off = 32; off >= 1; off >>= 1) {
@@ -159,8 +147,6 @@ double Butterfly(double *a) {
     }
     return a[0];
 }
-
-}  // namespace
 
 int HostForward(const SamplerModel &M, int64_t n, uint64_t seed, uint8_t *cols) {
     if (n == 0) return FBN_OK;

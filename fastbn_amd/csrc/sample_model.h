@@ -3,7 +3,9 @@
 #ifndef FBN_SAMPLE_MODEL_H
 #define FBN_SAMPLE_MODEL_H
 
+#include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -96,6 +98,19 @@ FBN_HD U128 PcgJumpTo(U128 s, uint64_t delta, const uint64_t *jump) {
         if ((delta >> j) & 1)
             s = Affine(s, U128{jump[4 * j], jump[4 * j + 1]}, U128{jump[4 * j + 2], jump[4 * j + 3]});
     return s;
+}
+
+// what the host twins share (sample_host.cpp, ais_host.cpp): the thread count (at most 16, at most
+// OMP_NUM_THREADS); fn(begin, end) over [0, n) in contiguous ranges of at least `grain`, in parallel; the
+// sum over 64 lanes in the kernels' butterfly order (lane i adds lane i ^ off, off = 32 .. 1; a is
+// overwritten); the parent configuration of node nd from one sample's values (stride between variables: vs)
+int HostThreads();
+void ParallelRanges(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)> &fn);
+double Butterfly(double *a);
+inline int ParentConfig(const SamplerModel &M, const SampleNode &nd, const uint8_t *x, size_t vs) {
+    int pc = 0;
+    for (int j = 0; j < nd.npar; ++j) pc = pc * M.par[2 * (nd.poff + j) + 1] + x[(size_t)M.par[2 * (nd.poff + j)] * vs];
+    return pc;
 }
 
 // the host path (device < 0 samplers, tools/sample_host_check.cpp): the kernels' algorithm, chunk

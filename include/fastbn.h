@@ -631,6 +631,93 @@ int fbn_epis_info(const fbn_epis *s, int64_t *lds_bytes, int *path /*0 lambda in
  * and the sampling launch. */
 int fbn_epis_last_kernel_ms(const fbn_epis *s, float *lbp_ms, float *sample_ms);
 
+/* ------------------------------------------------------------------ adaptive importance sampling
+ * The reference's -a 10 (ALGAISBN) and -a 8 (ALGSIS, include/Parameter.h:20-22), which only print
+ * "AIS-BN is under development" / "SIS is under development" (src/main.cpp:175-186, :149-160); -m is its
+ * maximum number of updates (default 10), -l its updating interval (default 2,500).  AIS-BN (Cheng & Druzdzel 2000, method 0) and
+ * self-importance sampling (after Shachter & Peot 1989, method 1) learn, per evidence case, an
+ * importance CPT (ICPT) from the weighted family counts of their own samples: no LBP launch, every DAG
+ * the sampler takes (disconnected ones included), unbiased, deterministic given the seed.  -a 9
+ * ("SISv1") is not built: the reference defines it nowhere.
+ *
+ * Parameters: method, S >= 1 counted samples, m in [0, 1024] maximum updates, l >= 1 interval, eps
+ * (fbn_epis_run's cutoff convention: negative = the defaults by state count), seed, case_offset.
+ * Stages, per case: nupd learning stages of l samples, each followed by an update, then one stage of
+ * `last` samples; T = nupd * l + last draws.  AIS-BN: nupd = m, last = S, only the last stage enters the
+ * estimate.  SIS: every sample is counted, T = S; an update follows each full block of l samples while
+ * samples remain, at most m times: nupd = min(m, (S - 1) / l), last = S - nupd * l.  A stage of n samples is
+ * ceil(n / 64) chunks of 64; the lanes past n in a last chunk sample in bounds with weight 0.
+ * Stream: position i * V + k with i = (case_offset + c) * T + t, t the sample's index within the case
+ * over all stages, k the variable's topological index (every variable consumes its position).  A
+ * case's result depends on (seed, global case index, method, S, m, l, eps) only.
+ * Learnable set, per case: the unobserved variables with an observed descendant (only ancestors of
+ * evidence need an importance function other than their CPT).  Every other unobserved variable is
+ * drawn as in fbn_lw_run (cdf row, no weight factor); observed variables are clamped and weighed as
+ * there.  A learnable variable with table row P[0..d) and ICPT row I[0..d) is drawn by fbn_epis_run's
+ * rule with g(q) = I[q] in place of P[q] * lambda[q]: Z ascending from 0.0; Z zero or not finite: a
+ * likelihood-weighting draw; with cutoff g' = max(g, eps * Z); the running sum of g' selects the value;
+ * the weight takes (P[value] * c(d - 1)) / g'(value), or 0.0 when g'(value) is 0.
+ * ICPT: `cells` doubles indexed like the CPTs (topological node order, parent configurations over the
+ * GIVEN parents last fastest, states); it starts as the CPTs at the start of every case.
+ * Counts N, `cells` doubles: zeroed at the start of each stage (AIS-BN) or once per case (SIS,
+ * cumulative).  After a chunk of a learning stage, with w_s = ldexp(m_s, e_s - emax), every learnable
+ * node x adds N[toff + pc_s * d + x_s] += w_s over the chunk's samples in ascending order (the lanes
+ * past n excluded).  emax runs over the stage (AIS-BN) or the case (SIS); when it grows, N is rescaled
+ * by the exact power of two, as the weight sums are.  No floating-point atomics, one order.
+ * Update k = 0 .. nupd - 1, after learning stage k, for every row (x, pc) of a learnable node:
+ * t = sum_q N[q] ascending from 0.0; t > 0 and finite: I[q] <- I[q] + eta_k * (N[q] / t - I[q]); else the
+ * row is left alone (a stage whose weights are all 0 included).  Rows are not renormalised.
+ * eta_k: AIS-BN 0.4 * (0.14 / 0.4)^(k / m), the paper's schedule; SIS 1.  The host computes the table
+ * (fbn_ais_eta) and the kernel reads it.
+ * Support: AIS-BN keeps I > 0 wherever P > 0, so any eps >= 0 is unbiased; SIS relies on the cutoff's
+ * floor, so method 1 with eps == 0 is FBN_ERR_ARG.
+ * This library's rules, where the papers differ: the raise-and-renormalise cutoff stands in for the
+ * paper's own theta cutoff; AIS-BN's "uniform parents of unlikely evidence" initialisation is not built
+ * (it needs prior marginals); SIS's update replaces a row by the cumulative weighted frequencies.
+ * Outputs per case as fbn_lw_run over the counted samples (labels, marginals with zeros for observed
+ * variables); stats [ncases][4] = log_evidence, ess, updates applied (those whose weights were not
+ * all 0), ess / n of the first stage (likelihood weighting's figure: the ICPT is still the CPTs).  A
+ * case whose counted weights are all 0 gives zeros, label -1, -inf, 0 and no NaN.
+ * Errors: the sampler's limits; method not 0 / 1, S < 1, m outside [0, 1024], l < 1, eps >= 1 or NaN,
+ * method 1 with eps == 0, a stream position ((case_offset + ncases) * T + 64) * V at or past 2^63:
+ * FBN_ERR_ARG.  Evidence codes are checked first, as everywhere. */
+typedef struct fbn_ais fbn_ais;
+/* Flatten the network and upload it to `device` once.  device < 0: a host-only handle that runs the
+ * same algorithm on CPU threads (bit-identical); its *_device entry returns FBN_ERR_NODEV. */
+int fbn_ais_create(const fbn_network *net, int device, fbn_ais **out);
+int fbn_ais_destroy(fbn_ais *s);
+/* Host arrays, synchronous.  marginals / stats may be NULL.  Replaces the AIS-BN (method 0) and SIS
+ * (method 1) stubs of src/main.cpp:175-186 and :149-160. */
+int fbn_ais_run(fbn_ais *s, int method, const int8_t *evidence, int64_t ncases, int64_t S, int64_t m, int64_t l,
+                uint64_t seed, int64_t case_offset, double eps, int32_t *labels, double *marginals,
+                double *stats /*[ncases][4]*/);
+/* The same with device-resident buffers: one launch on hip_stream, asynchronous after the evidence
+ * check (one stream sync, as fbn_jt_run_device's).  d_marginals / d_stats may be NULL.  Replaces the
+ * same stubs. */
+int fbn_ais_run_device(fbn_ais *s, int method, const int8_t *d_evidence, int64_t ncases, int64_t S, int64_t m, int64_t l,
+                       uint64_t seed, int64_t case_offset, double eps, int32_t *d_labels, double *d_marginals,
+                       double *d_stats, void *hip_stream);
+/* Testing interface: all T draws per case behind fbn_ais_run for a small batch (ncases * T and
+ * ncases * cells <= 2^22): values [V][ncases * T], mantissas and exponents [ncases * T] (draw t of case c
+ * at c * T + t), and the ICPT after the last update [ncases][cells].  Host arrays.  Replaces no
+ * reference interface. */
+int fbn_ais_debug_samples(fbn_ais *s, int method, const int8_t *evidence, int64_t ncases, int64_t S, int64_t m,
+                          int64_t l, uint64_t seed, int64_t case_offset, double eps, uint8_t *values, double *mantissas,
+                          int32_t *exponents, double *icpt);
+/* Kernel tuning (an explicit API, not an environment variable).  lds_bytes_max: the most LDS a
+ * workgroup may take with the state (ICPT and counts, 16 * cells bytes) in LDS behind the values (64 V
+ * bytes), the weights (512) and the flags (V, padded to 8); beyond it the state lives in the workgroup's
+ * slice of a global workspace sized by the grid.  0 = default (64 KiB, also the maximum), < 0 forces
+ * the global home.  max_workgroups: cap of the persistent grid, 0 = default.  Results do not depend on
+ * either.  fbn_ais_info: those LDS bytes, the state's bytes, and the home (0 LDS, 1 global) and grid a
+ * run of ncases cases takes next.  Replace no reference interface. */
+int fbn_ais_set_tuning(fbn_ais *s, int64_t lds_bytes_max, int max_workgroups);
+int fbn_ais_info(const fbn_ais *s, int64_t ncases, int64_t *lds_bytes, int64_t *state_bytes, int *path, int *grid);
+/* Device kernel time (ms, hipEvent) of the handle's last launch. */
+int fbn_ais_last_kernel_ms(const fbn_ais *s, float *ms);
+/* eta[0 .. m) of a method, as the runs use it (for restatements that must not depend on pow). */
+int fbn_ais_eta(int method, int m, double *eta);
+
 #ifdef __cplusplus
 }
 #endif
