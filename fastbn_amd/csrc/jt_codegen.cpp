@@ -1278,9 +1278,13 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
         if (in_merged) o << B(8);
         in_merged = false;
     }
+    // an observed query: label 0, the ArgMax of its row of zeros (the unbranched marginals write the
+    // label of the other lanes only; here, at the block's end, the store costs the ALARM kernel nothing)
+    if (marg_v2) o << "        if (ACT && " << observed(0) << ") labels[CS] = 0;\n";
     for (int v = 0; v < V && !marg_v2; ++v) {  // (unbranched marginals store the zeros themselves)
         o << "        if (ACT && " << observed(v) << ") {";
         for (int d = 0; d < plan.dom[v]; ++d) o << " OUTS(" << out_off[v] + d << ", 0.0);";
+        if (v == 0) o << " labels[CS] = 0;";  // an observed query: the ArgMax of its row of zeros
         o << " }\n";
     }
     o << R"(        const bool any_bad = __builtin_amdgcn_ballot_w64(bad != 0u) != 0ull;

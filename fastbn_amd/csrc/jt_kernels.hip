@@ -291,9 +291,11 @@ __global__ __launch_bounds__(64) void jt_interp_kernel(JtArgs A) {
             case JT_OP_MARG: {  // src/JunctionTree.cpp:1339-1454, src/Inference.cpp:92-102
                 const int dim = op.b;
                 const MOut o = out + op.a;
-                if (ev[op.e] >= 0) {  // evidence node: probabilities stay 0
-                    if (act)
+                if (ev[op.e] >= 0) {  // evidence node: probabilities stay 0 (an observed query: label 0,
+                    if (act) {        // the ArgMax of that row)
                         for (int d = 0; d < dim; ++d) o[d] = 0.0;
+                        if (op.f) A.labels[cs] = 0;
+                    }
                     break;
                 }
                 const int32_t *__restrict__ cd = aux + op.c;
@@ -601,8 +603,10 @@ __global__ __launch_bounds__(64) void jt_lds_kernel(const JtOp *__restrict__ ops
                 break;
             }
             case JT_L_EVZERO: {
-                if (act && ev[op.e] >= 0)
+                if (act && ev[op.e] >= 0) {
                     for (int d = 0; d < op.b; ++d) out[op.a + d] = 0.0;
+                    if (op.e == 0) labels[cs] = 0;  // an observed query: the ArgMax of its row of zeros
+                }
                 break;
             }
             default:

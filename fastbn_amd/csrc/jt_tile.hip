@@ -564,6 +564,7 @@ __global__ __launch_bounds__(64 * kMaxW, 16 / kMaxW) void jt_tile_kernel(const J
                     // reference's exact values: the block goes to the exact pass
                     bad |= act && !obs && mx - m2 <= 1e-12 * mx;
                 }
+                if (var == 0 && act && obs && s == 0) labels[cs] = 0;  // an observed query: the ArgMax of its zeros
             }
             if (prof) pc[5] += dclock() - t0;
         }

@@ -821,6 +821,7 @@ void jt_virt_kernel(
                 if (ev[v] >= 0) {
                     const int off = vsel[4 * v + 2], dim = vsel[4 * v + 3];
                     for (int d = 0; d < dim; ++d) out[off + d] = 0.0;
+                    if (v == 0) labels[cs] = 0;  // an observed query: the ArgMax of its row of zeros
                 }
         const unsigned long long b = __ballot(bad);
         if (lane == 0) sbad[wv] = b != 0ull;

@@ -47,6 +47,36 @@ def fixture_xmls(dirname):
     return out
 
 
+def count_map_nets():
+    """The eligible count-map networks of the GPU tests (tests/test_gpu_jt_range.py,
+    tests/test_gpu_jt_counts.py), from the tests' own generators (tests/jt_nets.py, plain Python):
+    [(namespace with dims / parents / counts, output layouts)]."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("jt_nets", os.path.join(REPO, "tests", "jt_nets.py"))
+    J = importlib.util.module_from_spec(spec)
+    keep, sys.dont_write_bytecode = sys.dont_write_bytecode, True  # (leave tests/ as it is)
+    try:
+        spec.loader.exec_module(J)
+    finally:
+        sys.dont_write_bytecode = keep
+    return [(J.conflict_net(*J.CONFLICT_FORMS["xmlbif"]), (0,)), (J.conflict_net(*J.CONFLICT_FORMS["counts"]), (0, 1)),
+            (J.counts_net(J.COUNTS_SEED, "small"), (0,)), (J.counts_net(J.COUNTS_SEED, "dom32"), (0,))]
+
+
+def prebuild_count_maps():
+    out = []
+    for net, layouts in count_map_nets():
+        jt = api.JunctionTree(api.Network.from_counts(net.dims, net.parents, net.counts), device=-1)
+        assert jt.info["specialized_eligible"]
+        for layout in layouts:
+            jt.set_output_layout(layout)
+            for exact in (None, True):
+                jt.set_exact(exact)
+                out.append(jt.build_kernel())
+    return out
+
+
 # code-generation options the GPU tests run ALARM under (tests/test_gpu_jt_fast.py)
 ALARM_TEST_OPTIONS = ({"FBN_JT_LEAF_RC": "1"}, {"FBN_JT_LDS_POOL": "0"}, {"FBN_JT_MARG_V2": "0"},
                       {"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"})
@@ -77,6 +107,8 @@ def prebuild_default(clean=True):
     built += prebuild_options(ALARM_XML, ALARM_TEST_OPTIONS)
     # (tests/test_gpu_jt_regpool.py compares the register pool on / off in both output layouts)
     built += prebuild_options(ALARM_XML, ({"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"}), layout=1)
+    # (the exact-order kernels of the conflict networks and of the 32-state network take 5 .. 20 s each)
+    built += prebuild_count_maps()
     if clean:
         keep = {os.path.basename(p) for p in built}
         kdir = os.path.join(REPO, "fastbn_amd", "kcache")

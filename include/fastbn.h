@@ -132,7 +132,8 @@ int fbn_jt_plan_dump(const fbn_jt_plan *p, const char *plan_path, const char *in
 int fbn_jt_stream_schedule(const fbn_jt_plan *p, int32_t *order, int64_t order_cap, int32_t *sched,
                            int64_t sched_cap, int64_t *n_order, int64_t *n_sched);
 /* Evidence cases on the host: evidence [ncases][num_nodes] int8; labels_out [ncases] (arg-max
- * of the query variable 0, InferenceUsingJT src/JunctionTree.cpp:1459-1467); marginals_out
+ * of the query variable 0, InferenceUsingJT src/JunctionTree.cpp:1459-1467; 0 for a case that
+ * observes the query itself: the arg-max of its row of zeros, as the sampling engines); marginals_out
  * [ncases][sum_dom] fp64 or NULL (GetProbabilitiesAllNodes :1385-1454, evidence nodes = 0).
  * Copies in/out over PCIe; synchronous. */
 int fbn_jt_run(fbn_jt_plan *p, const int8_t *evidence, int64_t ncases, int32_t *labels_out,

@@ -39,6 +39,32 @@ double BayesNet::Prob(int v, int q, const std::vector<int> &pv) const {
     return ((double)fc + 1.0) / ((double)tot + 1.0 * (double)dom[v]);
 }
 
+BayesNet FromCounts(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                    const int64_t *counts) {
+    BayesNet bn;
+    bn.n = n;
+    bn.dom.assign(dims, dims + n);
+    bn.given.assign(n, {});
+    bn.parents_asc.assign(n, {});
+    bn.counts.assign(n, {});
+    bn.totals.assign(n, {});
+    int64_t off = 0;
+    for (int v = 0; v < n; ++v) {
+        bn.names.push_back("X" + std::to_string(v));
+        bn.given[v].assign(parents + parent_off[v], parents + parent_off[v + 1]);
+        std::set<int> ps(bn.given[v].begin(), bn.given[v].end());
+        bn.parents_asc[v].assign(ps.begin(), ps.end());
+        long long npc = 1;
+        for (int p : bn.parents_asc[v]) npc *= bn.dom[p];
+        bn.counts[v].assign(counts + off, counts + off + bn.dom[v] * npc);
+        bn.totals[v].assign((size_t)npc, 0);
+        for (int q = 0; q < bn.dom[v]; ++q)
+            for (long long pc = 0; pc < npc; ++pc) bn.totals[v][pc] += bn.counts[v][q * npc + pc];
+        off += bn.dom[v] * npc;
+    }
+    return bn;
+}
+
 BayesNet LoadXmlbif(const std::string &path) {
     BayesNet bn;
     std::unique_ptr<mini_xml::Element> doc;

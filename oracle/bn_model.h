@@ -28,6 +28,13 @@ struct BayesNet {
     double Prob(int v, int q, const std::vector<int> &parent_vals_asc) const;
 };
 
+// A network from a count map in fbn_network_create's layout (include/fastbn.h): parents of node v
+// = parents[parent_off[v] .. parent_off[v+1]) in the node's own order, counts family after family,
+// counts[value][parent configuration], configurations over the parents in ascending index order,
+// last fastest (DiscreteNode::AddCount, src/DiscreteNode.cpp:114-147).  The caller passes a DAG.
+BayesNet FromCounts(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                    const int64_t *counts);
+
 // XMLBIF reader; exits the process on malformed input (the reference does the same)
 BayesNet LoadXmlbif(const std::string &path);
 

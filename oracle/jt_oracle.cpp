@@ -30,9 +30,16 @@ static int Loc(const PTable &t, int v) {  // GetVariableIndex, src/PotentialTabl
     return (int)t.vars.size();
 }
 
-static void Normalize(PTable &t) {  // src/PotentialTableBase.cpp:433-445
+// st (optional): the range of the denominators and the smallest non-zero entry divided so far
+static void Normalize(PTable &t, InferStats *st = nullptr) {  // src/PotentialTableBase.cpp:433-445
     double den = 0;
     for (double p : t.pot) den += p;
+    if (st) {
+        st->min_den = std::min(st->min_den, den);
+        st->max_den = std::max(st->max_den, den);
+        for (double p : t.pot)
+            if (p != 0) st->min_entry = std::min(st->min_entry, p);
+    }
     for (double &p : t.pot) p /= den;
 }
 
@@ -334,7 +341,7 @@ static int MapToSub(const PTable &t, const PTable &sub, int k, std::vector<int> 
     return idx;
 }
 
-int JTree::Infer(const int8_t *ev, double *marg) const {
+int JTree::Infer(const int8_t *ev, double *marg, InferStats *st) const {
     std::vector<PTable> C = clique_init, S = sep_init;
     // LoadDiscreteEvidence: evidence in ascending var order (src/JunctionTree.cpp:316-383)
     for (int v = 0; v < bn.n; ++v) {
@@ -344,7 +351,7 @@ int JTree::Infer(const int8_t *ev, double *marg) const {
         for (auto &t : S)
             if (Loc(t, v) < (int)t.vars.size()) Reduce(t, v, ev[v]);
     }
-    for (auto &t : C) Normalize(t);  // src/JunctionTree.cpp:1479-1483
+    for (auto &t : C) Normalize(t, st);  // src/JunctionTree.cpp:1479-1483
     std::vector<int> cfg(64);
     const int L = (int)levels.size();
     // Collect, src/JunctionTree.cpp:1240-1306
@@ -370,7 +377,7 @@ int JTree::Infer(const int8_t *ev, double *marg) const {
                     for (int e = 0; e < p.size(); ++e) p.pot[e] *= sp.pot[MapToSub(p, sp, e, cfg)];
                 }
                 for (int c : levels[i])
-                    if (clique_down[c].size() > k) Normalize(C[c]);
+                    if (clique_down[c].size() > k) Normalize(C[c], st);
             }
         }
     }
@@ -391,7 +398,7 @@ int JTree::Infer(const int8_t *ev, double *marg) const {
                 const PTable &sp = S[clique_up[c]];
                 int Ts = sp.size();
                 for (int k = 0; k < t.size(); ++k) t.pot[k] *= sp.pot[k % Ts];
-                Normalize(t);
+                Normalize(t, st);
             }
         }
     }
@@ -434,7 +441,7 @@ int JTree::Infer(const int8_t *ev, double *marg) const {
             // CalculateMarginalProbability returns the clique table itself (not re-normalized)
             // when it has 1 variable; otherwise the normalized marginal.  ArgMax: strict '>'.
             PTable q = pt;
-            if (best_nv > 1) Normalize(q);
+            if (best_nv > 1) Normalize(q, st);
             double mp = 0;
             for (int i = 0; i < q.size(); ++i)
                 if (q.pot[i] > mp) {
@@ -442,7 +449,7 @@ int JTree::Infer(const int8_t *ev, double *marg) const {
                     label = i;
                 }
         }
-        Normalize(pt);
+        Normalize(pt, st);
         for (int j = 0; j < d; ++j) marg[off + j] = pt.pot[j];
         off += d;
     }

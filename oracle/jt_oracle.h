@@ -7,6 +7,7 @@
 #ifndef FBN_ORACLE_JT_H
 #define FBN_ORACLE_JT_H
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -20,6 +21,13 @@ struct PTable {  // PotentialTableBase (include/PotentialTableBase.h:21-38)
     std::vector<double> pot;
     int size() const { return (int)pot.size(); }
     void Rebuild();  // cum_levels + size, src/PotentialTableBase.cpp:599-607
+};
+
+// What the Normalize calls of one case saw (tests/test_jt_counts_host.py: the conditions the
+// kernels' denominator range guard, DESIGN §4, is tested under).
+struct InferStats {
+    double min_den = HUGE_VAL, max_den = 0;  // smallest / largest denominator of any Normalize
+    double min_entry = HUGE_VAL;             // smallest non-zero table entry any Normalize divided
 };
 
 struct JTree {
@@ -37,7 +45,8 @@ struct JTree {
 
     // one case: PredictUseJTInfer(E, ...) src/JunctionTree.cpp:1473-1502.
     // ev[v] = observed value or -1.  marg gets sum(dom) doubles (evidence nodes = 0).
-    int Infer(const int8_t *ev, double *marg) const;
+    // st (optional): statistics of the case's Normalize calls.
+    int Infer(const int8_t *ev, double *marg, InferStats *st = nullptr) const;
 };
 
 double Round7(double x);  // Round(x, 7), src/Inference.cpp:195-206

@@ -25,7 +25,9 @@ def _load():
     sig = {
         "or_jt_load": ([C.c_char_p], _vp), "or_jt_destroy": ([_vp], None), "or_jt_nvars": ([_vp], C.c_int),
         "or_jt_dims": ([_vp, _vp], C.c_int), "or_jt_dump_plan": ([_vp, C.c_char_p, C.c_char_p], C.c_int),
-        "or_jt_infer": ([_vp, _vp, _i64, _vp, _vp], C.c_int), "or_round7": ([_dbl], _dbl),
+        "or_jt_infer": ([_vp, _vp, _i64, _vp, _vp], C.c_int),
+        "or_jt_create": ([C.c_int, _vp, _vp, _vp, _vp], _vp),
+        "or_jt_infer_stats": ([_vp, _vp, _i64, _vp, _vp, _vp], C.c_int), "or_round7": ([_dbl], _dbl),
         "or_libsvm_load": ([C.c_char_p, C.c_int, _vp, _vp, _i64], _i64),
         "or_csv_load": ([C.c_char_p], _vp), "or_ds_from_columns": ([_vp, C.c_int, _i64, _vp], _vp),
         "or_ds_destroy": ([_vp], None), "or_ds_shape": ([_vp, _vp, _vp], C.c_int),
@@ -55,13 +57,28 @@ def L():
 
 
 class OracleJT:
-    def __init__(self, xml_path):
-        self.h = L().or_jt_load(os.fsencode(xml_path))
+    def __init__(self, xml_path, _handle=None):
+        self.h = L().or_jt_load(os.fsencode(xml_path)) if _handle is None else _handle
         self.n = L().or_jt_nvars(self.h)
         d = (C.c_int * self.n)()
         L().or_jt_dims(self.h, d)
         self.dims = np.array(list(d), np.int32)
         self.sum_dom = int(self.dims.sum())
+
+    @classmethod
+    def from_counts(cls, dims, parents, counts):
+        """A network given as a count map in Network.from_counts' layout: parents[v] in the node's own
+        order, counts[v] = int [dims[v]][parent configurations] over the parents in ascending index
+        order, last fastest."""
+        d = np.ascontiguousarray(dims, np.int32)
+        off = np.zeros(len(d) + 1, np.int32)
+        off[1:] = np.cumsum([len(ps) for ps in parents])
+        par = np.ascontiguousarray([q for ps in parents for q in ps] or [0], np.int32)
+        cnt = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int64).reshape(-1) for c in counts]))
+        h = L().or_jt_create(len(d), d.ctypes.data, off.ctypes.data, par.ctypes.data, cnt.ctypes.data)
+        if not h:
+            raise ValueError("or_jt_create: bad arguments")
+        return cls(None, _handle=h)
 
     def dump_plan(self, plan, init):
         L().or_jt_dump_plan(self.h, os.fsencode(plan), os.fsencode(init))
@@ -73,6 +90,17 @@ class OracleJT:
         lab = np.zeros(n, np.int32)
         L().or_jt_infer(self.h, ev.ctypes.data, n, marg.ctypes.data, lab.ctypes.data)
         return lab, marg
+
+    def infer_stats(self, evidence):
+        """infer() plus stats [n][3]: per case the smallest and the largest denominator any Normalize
+        used and the smallest non-zero table entry one divided."""
+        ev = np.ascontiguousarray(evidence, np.int8)
+        n = ev.shape[0]
+        marg = np.zeros((n, self.sum_dom))
+        lab = np.zeros(n, np.int32)
+        stats = np.zeros((n, 3))
+        L().or_jt_infer_stats(self.h, ev.ctypes.data, n, marg.ctypes.data, lab.ctypes.data, stats.ctypes.data)
+        return lab, marg, stats
 
     def __del__(self):
         if getattr(self, "h", None):

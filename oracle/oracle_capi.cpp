@@ -19,6 +19,14 @@ void *or_jt_load(const char *xml_path) {
     t->Build(LoadXmlbif(xml_path));
     return t;
 }
+// a network given as a count map in fbn_network_create's layout (bn_model.h: FromCounts)
+void *or_jt_create(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                   const int64_t *counts) {
+    if (n < 1 || !dims || !parent_off || !counts || (!parents && parent_off[n] > 0)) return nullptr;
+    auto *t = new JTree();
+    t->Build(FromCounts(n, dims, parent_off, parents, counts));
+    return t;
+}
 void or_jt_destroy(void *h) { delete static_cast<JTree *>(h); }
 int or_jt_nvars(void *h) { return static_cast<JTree *>(h)->bn.n; }
 int or_jt_dims(void *h, int *out) {
@@ -39,6 +47,23 @@ int or_jt_infer(void *h, const int8_t *ev, int64_t ncases, double *marg, int32_t
     for (int64_t c = 0; c < ncases; ++c) {
         double *m = marg ? marg + c * sd : tmp.data();
         labels[c] = t->Infer(ev + c * t->bn.n, m);
+    }
+    return 0;
+}
+// or_jt_infer plus, per case, stats[c] = {smallest denominator, largest denominator, smallest
+// non-zero entry divided} over the case's Normalize calls
+int or_jt_infer_stats(void *h, const int8_t *ev, int64_t ncases, double *marg, int32_t *labels, double *stats) {
+    auto *t = static_cast<JTree *>(h);
+    int sd = 0;
+    for (int d : t->bn.dom) sd += d;
+    std::vector<double> tmp(sd);
+    for (int64_t c = 0; c < ncases; ++c) {
+        InferStats st;
+        double *m = marg ? marg + c * sd : tmp.data();
+        labels[c] = t->Infer(ev + c * t->bn.n, m, &st);
+        stats[3 * c] = st.min_den;
+        stats[3 * c + 1] = st.max_den;
+        stats[3 * c + 2] = st.min_entry;
     }
     return 0;
 }
