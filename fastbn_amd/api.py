@@ -68,6 +68,8 @@ _SIGS = {
     "fbn_ci_last_kernel_ms": [_vp, _vp],
     "fbn_ci_decision_margin": [_vp, _vp, _vp, C.c_int],
     "fbn_ci_debug_counts": [_vp, _vp, _i64, C.c_int, _vp, _i64],
+    "fbn_ci_level0_info": [_vp, _vp],
+    "fbn_ci_debug_level0_range": [_vp, _i64, _i64, _vp],
     "fbn_pc_decision_margin": [_vp, _vp, _vp],
     "fbn_ci_ctx_destroy": [_vp],
     "fbn_pc_stable": [_vp, _dbl, C.c_int, C.c_int, _pp],
@@ -630,6 +632,22 @@ class IndependenceTest(_Handle):
             cap = int(np.max(np.prod(dims[items], axis=1))) if len(items) else 1
         out = np.zeros((len(items), cap), np.int32)
         lib.fbn_ci_debug_counts(self._h, _p(items), len(items), d, _p(out), cap)
+        return out
+
+    def level0_info(self):
+        """The last level-0 all-pairs launch of this context (fbn_ci_level0_info): path (1 popcount
+        Gram, 2 MFMA Gram, 3 tiled pairs kernel, 0 none yet), R, Rp, KS, nt, S and the shortest /
+        longest split-K slice in stages."""
+        out = np.zeros(8, np.int64)
+        lib.fbn_ci_level0_info(self._h, _p(out))
+        keys = ("path", "R", "Rp", "KS", "nt", "S", "shortest", "longest")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def level0_range_counts(self, pair0, n):
+        """The complete-graph pairs [pair0, pair0 + n) as one batch of the PC driver's level-0 chunk
+        loop, the level-0 Gram poisoned first (fbn_ci_debug_level0_range) -> int32 [n][16]."""
+        out = np.zeros((n, 16), np.int32)
+        lib.fbn_ci_debug_level0_range(self._h, int(pair0), int(n), _p(out))
         return out
 
     def counts(self, x, y, z=()):

@@ -320,7 +320,9 @@ static int CiGram0Mfma(fbn_ci_ctx *c, int64_t t0, int64_t n, hipStream_t s, bool
     }
     int64_t r0, r1;
     CiPairRowRange(c, t0, n, &r0, &r1);
-    if (r1 <= r0) {
+    const int64_t info0[8] = {2, R, Rp, KS, 0, 0, 0, 0};
+    std::copy(info0, info0 + 8, c->l0_info);
+    if (r1 <= r0) {  // the range's x variables have no leading rows: nothing of G is read
         *done = true;
         return FBN_OK;
     }
@@ -339,6 +341,8 @@ static int CiGram0Mfma(fbn_ci_ctx *c, int64_t t0, int64_t n, hipStream_t s, bool
     int64_t S = std::max<int64_t>(1, EnvOr0("FBN_CI_GRAM4_SPLITS", c->num_cu / nt));
     S = std::max<int64_t>(S, (KS + 510) / 511);  // slices of <= 511 stages x 128 samples
     S = std::min<int64_t>(S, KS);
+    // slice `split` covers stages [split * KS / S, (split + 1) * KS / S): floor or ceil of KS / S
+    c->l0_info[4] = nt, c->l0_info[5] = S, c->l0_info[6] = KS / S, c->l0_info[7] = (KS + S - 1) / S;
     if ((rc = c->g4slab.ensure((size_t)(nt * S * T * T * 2)))) return rc;
     hipError_t e = fbn_ci_gram4(c->onehot4.as<uint8_t>(), Rp, c->g4tasks.as<int2>(), nt, (int)S, (int)KS,
                                 c->g4slab.as<uint16_t>(), (int)R, R, c->gram0.as<int32_t>(), s);
@@ -481,6 +485,10 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
         const bool gram0 = all_pairs && d == 0 && CiGram0Eligible(c);
         const bool tiled = all_pairs && d == 0 && !gram0 && !getenv("FBN_CI_NO_TILED");
         if (tiled && (rc = CiPairTasks(c, pair0, pair0 + n, s))) return rc;
+        if (all_pairs && d == 0) {  // fbn_ci_level0_info (the Gram branches below fill in theirs)
+            std::fill(c->l0_info, c->l0_info + 8, 0);
+            c->l0_info[0] = tiled ? 3 : 0;
+        }
         hipError_t e = hipSuccess;
         if (gram0) {  // Gram of the leading rows, then every pair's table from it
             if ((rc = CiLeadEnsure(c, s))) return rc;
@@ -490,6 +498,7 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
             if ((rc = CiGram0Mfma(c, pair0, n, s, &done))) return rc;
             if (!done) {
                 if ((rc = CiGram0Tasks(c, pair0, pair0 + n, s))) return rc;
+                c->l0_info[0] = 1, c->l0_info[1] = R, c->l0_info[4] = c->g0_ntasks;
                 e = fbn_ci_gram(c->bits.as<uint32_t>(), c->bits_W, c->leadrows.as<int32_t>(),
                                 c->g0tasks.as<int32_t>(), c->g0_ntasks, 0, c->gram0.as<int32_t>(), c->num_cu, s);
             }
@@ -673,6 +682,17 @@ int fbn_ci_counts(fbn_ci_ctx *c, int x, int y, const int32_t *z, int d, int32_t 
     return FBN_OK;
 }
 
+// a debug call must not change which path later batches on this ctx take: the pair mode (and
+// with it the derived level-1 / level-2 counting) is restored on every exit
+namespace {
+struct PairModeGuard {
+    fbn_ci_ctx *c;
+    int mode;
+    bool recorded, triples;
+    ~PairModeGuard() { c->pair_mode = mode, c->pairs_recorded = recorded, c->triples_ready = triples; }
+};
+}  // namespace
+
 // Counts of n tests through the kernels a PC run uses at level d (parity pinning of the production
 // paths): d = 0 the complete-graph level-0 batch (the Gram of the leading mask rows, then every
 // pair's table, recorded for level 1), d = 1 the derived counting from those recorded pair tables
@@ -689,14 +709,7 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
     int rc;
     const int nv = c->nvars;
     fbn::PCResultHost scratch;
-    // a debug call must not change which path later batches on this ctx take: the pair mode (and
-    // with it the derived level-1 / level-2 counting) is restored on every exit
-    struct PairModeGuard {
-        fbn_ci_ctx *c;
-        int mode;
-        bool recorded, triples;
-        ~PairModeGuard() { c->pair_mode = mode, c->pairs_recorded = recorded, c->triples_ready = triples; }
-    } guard{c, c->pair_mode, c->pairs_recorded, c->triples_ready};
+    PairModeGuard guard{c, c->pair_mode, c->pairs_recorded, c->triples_ready};
     auto level0 = [&]() -> int {  // the PC run's level 0, pair tables recorded
         fbn::CiBatchStats st{0, 0};
         for (int v = 0; v < nv; ++v) st.dim_rows += (int64_t)(nv - 1) * c->dims[v], st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
@@ -759,6 +772,59 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
     if (rc) return rc;
     FBN_HIP(hipStreamSynchronize(c->stream));
     FBN_HIP(hipMemcpy(counts, c->counts.p, (size_t)n * cap * 4, hipMemcpyDeviceToHost));
+    return FBN_OK;
+}
+
+int fbn_ci_level0_info(const fbn_ci_ctx *c, int64_t out[8]) {
+    if (!c || !out) return SetError(FBN_ERR_ARG, "null pointer");
+    std::copy(c->l0_info, c->l0_info + 8, out);
+    return FBN_OK;
+}
+
+// The complete-graph pairs [pair0, pair0 + n) as one batch of the PC driver's level-0 chunk loop
+// (pair tables recorded); counts [n][16]: pair pair0 + t's table, cells beyond it 0.  The level-0
+// Gram is filled with 0xFF bytes first, so an entry the Gram kernels leave unwritten reads as -1
+// (a wrong count) instead of a stale value of an earlier launch or context.
+int fbn_ci_debug_level0_range(fbn_ci_ctx *c, int64_t pair0, int64_t n, int32_t *counts) {
+    if (!c || n < 0 || (!counts && n > 0)) return SetError(FBN_ERR_ARG, "bad argument");
+    const int nv = c->nvars;
+    const int64_t P = (int64_t)nv * (nv - 1) / 2;
+    if (pair0 < 0 || pair0 > P || n > P - pair0)
+        return SetError(FBN_ERR_ARG, "pairs [%lld, %lld) outside the complete graph's %lld", (long long)pair0,
+                        (long long)(pair0 + n), (long long)P);
+    if (n == 0) return FBN_OK;
+    FBN_HIP(hipSetDevice(c->device));
+    PairModeGuard guard{c, c->pair_mode, c->pairs_recorded, c->triples_ready};
+    fbn::CiBatchStats st{0, 0};
+    int64_t R = 0;
+    for (int v = 0; v < nv; ++v) {
+        st.dim_rows += (int64_t)(nv - 1) * c->dims[v], st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
+        R += c->dims[v] - 1;
+    }
+    if (!fbn::CiAllPairsEligible(c, st))
+        return SetError(FBN_ERR_ARG, "dataset not eligible for the bit-sliced level-0 path");
+    int rc;
+    if (fbn::CiGram0Eligible(c)) {
+        if ((rc = c->gram0.ensure((size_t)(R * R * 4)))) return rc;
+        FBN_HIP(hipMemsetAsync(c->gram0.p, 0xFF, (size_t)(R * R * 4), c->stream));
+    }
+    fbn::PCResultHost scratch;
+    std::vector<uint8_t> flags((size_t)n);
+    fbn::CiSetPairMode(c, 1);
+    if ((rc = fbn::CiBatchLaunchAllPairs(c, 0.05, &st, pair0, n)) ||
+        (rc = fbn::CiBatchWait(c, 0, flags.data(), nullptr, scratch)))
+        return rc;
+    FBN_HIP(hipStreamSynchronize(c->stream));
+    std::vector<int32_t> rec((size_t)n * 64);
+    FBN_HIP(hipMemcpy(rec.data(), c->slot[0].bcounts.p, rec.size() * 4, hipMemcpyDeviceToHost));
+    int x = 0;
+    while ((int64_t)(x + 1) * nv - (int64_t)(x + 1) * (x + 2) / 2 <= pair0) ++x;  // the row of pair0
+    int y = x + 1 + (int)(pair0 - ((int64_t)x * nv - (int64_t)x * (x + 1) / 2));
+    for (int64_t t = 0; t < n; ++t) {
+        const int cells = c->dims[x] * c->dims[y];
+        std::fill(std::copy(rec.begin() + t * 64, rec.begin() + t * 64 + cells, counts + t * 16), counts + t * 16 + 16, 0);
+        if (++y == nv) ++x, y = x + 1;
+    }
     return FBN_OK;
 }
 

@@ -152,6 +152,9 @@ struct fbn_ci_ctx {
     int64_t g4_r0 = -1, g4_r1 = -1;
     int g4_nt = 0;
     bool onehot4_ready = false;
+    // fbn_ci_level0_info: the last level-0 all-pairs launch -- path (1 popcount Gram, 2 MFMA Gram,
+    // 3 tiled pairs kernel, 0 none yet), R, Rp, KS, nt, S, shortest / longest slice in stages
+    int64_t l0_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int *h_kept = nullptr;
     unsigned *h_open = nullptr;
     void *h_xfer = nullptr;  // pinned staging of level-0 kept pairs / level-1 results (read-back)

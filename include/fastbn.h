@@ -263,6 +263,18 @@ int fbn_ci_last_kernel_ms(const fbn_ci_ctx *c, float *ms);
  * recorded pair tables, d >= 2 the histogram kernel (2-bit packed columns at >= 64k samples) over
  * one batch.  counts [n][cap], Counts3D cell order (src/CellTable.cpp:277-281). */
 int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, int32_t *counts, int64_t cap);
+/* Which kernels the context's last level-0 all-pairs launch took (tests assert the path they mean
+ * to check): out = {path, R, Rp, KS, nt, S, shortest slice, longest slice}.  path: 1 the popcount
+ * Gram, 2 the FP4 MFMA Gram, 3 the tiled pairs kernel, 0 none yet (or none of the three).  R leading
+ * rows (paths 1, 2); path 2: Rp = R padded to the 256-row tile, KS stages of 128 samples, nt tiles,
+ * S split-K slices and the shortest / longest slice in stages (nt = S = 0: the range's x variables
+ * have one state each, nothing was launched); path 1: nt = its 8 x 8 tile tasks.  Others 0. */
+int fbn_ci_level0_info(const fbn_ci_ctx *c, int64_t out[8]);
+/* The complete-graph pairs [pair0, pair0 + n) (lexicographic (x < y) order) launched as one batch of
+ * a PC run's level-0 chunk loop; counts [n][16]: each pair's table, cells beyond it 0.  The level-0
+ * Gram is poisoned (0xFF bytes) before the launch: an entry the Gram kernels did not write shows as
+ * a wrong count, never as a stale right one.  The pair mode is restored on exit. */
+int fbn_ci_debug_level0_range(fbn_ci_ctx *c, int64_t pair0, int64_t n, int32_t *counts);
 /* Decision-margin log: the p-value CDF (stats::pchisq, src/IndependenceTest.cpp:146,
  * 268,355) is not pinned by any reference fixture, so every test records min |p - alpha| and counts
  * tests with |p - alpha| < 1e-9 (a decision a different-but-accurate CDF could flip).  Covers every

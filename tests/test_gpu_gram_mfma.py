@@ -37,7 +37,10 @@ def test_gram_pair_tables_equal_reference_counts2d(monkeypatch, ref_blocks, nvar
     if gram == "popcount":
         monkeypatch.setenv("FBN_CI_GRAM_NO_MFMA", "1")
     items = np.array([[x, y] for x, y, _, _ in tests], np.int32)
-    got = F.IndependenceTest(F.Dataset(columns=cols, dims=dims)).production_counts(items, 0, 16)
+    ci = F.IndependenceTest(F.Dataset(columns=cols, dims=dims))
+    got = ci.production_counts(items, 0, 16)
+    # the kernel this parametrization means: the MFMA Gram runs only above its eligibility threshold
+    assert ci.level0_info()["path"] == (2 if gram == "mfma" else 1)
     for k, (x, y, _, ref) in enumerate(tests):
         np.testing.assert_array_equal(got[k, :len(ref)], ref, err_msg=f"pair ({x}, {y}) of shape {nvars}x{N}")
 
@@ -45,9 +48,13 @@ def test_gram_pair_tables_equal_reference_counts2d(monkeypatch, ref_blocks, nvar
 @pytest.mark.parametrize("nvars,N,seed", GRAM_SHAPES)
 def test_mfma_gram_equals_popcount_gram(monkeypatch, nvars, N, seed):
     cols, dims, pairs = gram_dataset(nvars, N, seed)
-    got = F.IndependenceTest(F.Dataset(columns=cols, dims=dims)).production_counts(pairs, 0, 16)
+    ci = F.IndependenceTest(F.Dataset(columns=cols, dims=dims))
+    got = ci.production_counts(pairs, 0, 16)
+    assert ci.level0_info()["path"] == 2
     monkeypatch.setenv("FBN_CI_GRAM_NO_MFMA", "1")
-    ref = F.IndependenceTest(F.Dataset(columns=cols, dims=dims)).production_counts(pairs, 0, 16)
+    ci = F.IndependenceTest(F.Dataset(columns=cols, dims=dims))
+    ref = ci.production_counts(pairs, 0, 16)
+    assert ci.level0_info()["path"] == 1
     np.testing.assert_array_equal(got, ref)
     cells = dims[pairs[:, 0]] * dims[pairs[:, 1]]
     for k in range(0, len(pairs), 97):
