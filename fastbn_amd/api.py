@@ -902,6 +902,47 @@ def score_marginals(network, marginals, golden):
     return mse.value, hd.value
 
 
+class _CaseInference:
+    """What the approximate case-inference classes share: the buffers of infer and debug_samples, the
+    eps argument and EvaluateAccuracy.  The class sets self.network and self.sum_dom and defines infer."""
+
+    def _outputs(self, evidence, marginals, k):
+        """(evidence int8, ncases, labels, marginals or None, stats [ncases][k]) of one infer call."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        labels = np.zeros(n, np.int32)
+        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
+        return ev, n, labels, marg, np.zeros((n, k), np.float64)
+
+    def _debug_outputs(self, evidence, draws):
+        """(evidence int8, ncases, values, mantissas, exponents) for `draws` samples per case."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        tot = n * draws
+        return (ev, n, np.zeros((self.network.num_nodes, tot), np.uint8), np.zeros(tot, np.float64),
+                np.zeros(tot, np.int32))
+
+    @staticmethod
+    def _eps_arg(eps):
+        """The C entries' eps: None -> -1.0 (they read a negative eps as "the defaults")."""
+        if eps is None:
+            return -1.0
+        if float(eps) < 0.0:
+            err = FastBNError(f"eps {eps!r}: in [0, 1), or None for the defaults")
+            err.code = -1  # FBN_ERR_ARG
+            raise err
+        return float(eps)
+
+    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
+        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
+        labels, marg = self.infer(evidence)
+        acc = float(np.mean(labels == np.asarray(ground_truths)))
+        if golden is None:
+            return acc
+        mse, hd = score_marginals(self.network, marg, golden)
+        return acc, mse / len(labels), hd / len(labels)
+
+
 class Sampler(_Handle):
     """The sampling engine of one network on one device (fbn_sampler).  device < 0: the host path,
     the same algorithm on CPU threads (bit-identical results)."""
@@ -932,7 +973,7 @@ class Sampler(_Handle):
         return ms.value
 
 
-class LikelihoodWeighting(Sampler):
+class LikelihoodWeighting(_CaseInference, Sampler):
     """Sampling inference, mirroring JunctionTree: likelihood weighting (method="lw", the reference's
     -a 5) or probabilistic logic sampling ("pls", -a 4) with num_samples samples per case (-q).
     Works on any DAG, a disconnected learned network included."""
@@ -951,11 +992,7 @@ class LikelihoodWeighting(Sampler):
         """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
         self.stats = (log_evidence, ess) per case.  case_offset: the global index of the first case
         (a batch split over calls gives the bits of the whole batch)."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        labels = np.zeros(n, np.int32)
-        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
-        st = np.zeros((n, 2), np.float64)
+        ev, n, labels, marg, st = self._outputs(evidence, marginals, 2)
         lib.fbn_lw_run(self._h, self.method, _p(ev), n, self.num_samples, self.seed, int(case_offset), _p(labels),
                        _p(marg), _p(st))
         self.stats = (st[:, 0].copy(), st[:, 1].copy())
@@ -972,27 +1009,13 @@ class LikelihoodWeighting(Sampler):
     def debug_samples(self, evidence, case_offset=0):
         """The samples behind infer(evidence): (values uint8 [V][ncases * S], mantissas fp64,
         exponents int32 [ncases * S]); sample s of case c at c * S + s."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        tot = n * self.num_samples
-        vals = np.zeros((self.network.num_nodes, tot), np.uint8)
-        m = np.zeros(tot, np.float64)
-        e = np.zeros(tot, np.int32)
+        ev, n, vals, m, e = self._debug_outputs(evidence, self.num_samples)
         lib.fbn_lw_debug_samples(self._h, self.method, _p(ev), n, self.num_samples, self.seed, int(case_offset),
                                  _p(vals), _p(m), _p(e))
         return vals, m, e
 
-    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
-        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
-        labels, marg = self.infer(evidence)
-        acc = float(np.mean(labels == np.asarray(ground_truths)))
-        if golden is None:
-            return acc
-        mse, hd = score_marginals(self.network, marg, golden)
-        return acc, mse / len(labels), hd / len(labels)
 
-
-class LoopyBeliefPropagation(_Handle):
+class LoopyBeliefPropagation(_CaseInference, _Handle):
     """Loopy belief propagation (fbn_lbp; the reference's -a 7 stub, src/main.cpp:136-147), mirroring
     JunctionTree: `iterations` flooding sweeps (the reference's propagation length, -d), stopping
     early once an iteration's residual is <= tol; `damping` in [0, 1) on the factor -> variable
@@ -1020,11 +1043,7 @@ class LoopyBeliefPropagation(_Handle):
     def infer(self, evidence, marginals=True):
         """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
         self.stats = (iterations used, last residual) per case."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        labels = np.zeros(n, np.int32)
-        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
-        st = np.zeros((n, 2), np.float64)
+        ev, n, labels, marg, st = self._outputs(evidence, marginals, 2)
         lib.fbn_lbp_run(self._h, _p(ev), n, self.iterations, self.tol, self.damping, _p(labels), _p(marg), _p(st))
         self.stats = (st[:, 0].astype(np.int32), st[:, 1].copy())
         return labels, marg
@@ -1054,17 +1073,8 @@ class LoopyBeliefPropagation(_Handle):
         lib.fbn_lbp_last_kernel_ms(self._h, C.byref(ms))
         return ms.value
 
-    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
-        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
-        labels, marg = self.infer(evidence)
-        acc = float(np.mean(labels == np.asarray(ground_truths)))
-        if golden is None:
-            return acc
-        mse, hd = score_marginals(self.network, marg, golden)
-        return acc, mse / len(labels), hd / len(labels)
 
-
-class EPISBN(_Handle):
+class EPISBN(_CaseInference, _Handle):
     """EPIS-BN (fbn_epis; the reference's -a 6 stub, src/main.cpp:123-134), mirroring JunctionTree:
     `iterations` sweeps of loopy belief propagation (tol, damping as LoopyBeliefPropagation), then
     importance sampling with num_samples samples per case (-q) from each CPT row times the lambda
@@ -1078,11 +1088,7 @@ class EPISBN(_Handle):
         self.network = network
         self.num_samples, self.seed = int(num_samples), int(seed)
         self.iterations, self.tol, self.damping = int(iterations), float(tol), float(damping)
-        self.eps = -1.0 if eps is None else float(eps)
-        if eps is not None and self.eps < 0.0:  # the C entry reads a negative eps as "the defaults"
-            err = FastBNError(f"eps {eps!r}: in [0, 1), or None for the defaults")
-            err.code = -1  # FBN_ERR_ARG
-            raise err
+        self.eps = self._eps_arg(eps)
         self.sum_dom = int(np.sum(network.dims))
         self.stats = None
         h = C.c_void_p()
@@ -1097,11 +1103,7 @@ class EPISBN(_Handle):
         """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None);
         self.stats = (log_evidence, ess, LBP iterations used, LBP residual) per case.  case_offset: the
         global index of the first case (a batch split over calls gives the bits of the whole batch)."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        labels = np.zeros(n, np.int32)
-        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
-        st = np.zeros((n, 4), np.float64)
+        ev, n, labels, marg, st = self._outputs(evidence, marginals, 4)
         lib.fbn_epis_run(self._h, _p(ev), *self._run_args(n, case_offset), _p(labels), _p(marg), _p(st))
         self.stats = (st[:, 0].copy(), st[:, 1].copy(), st[:, 2].astype(np.int32), st[:, 3].copy())
         return labels, marg
@@ -1117,12 +1119,7 @@ class EPISBN(_Handle):
     def debug_samples(self, evidence, case_offset=0):
         """The samples behind infer(evidence): (values uint8 [V][ncases * S], mantissas fp64, exponents
         int32 [ncases * S], lambda rows fp64 [ncases][sum_dom]); sample s of case c at c * S + s."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        tot = n * self.num_samples
-        vals = np.zeros((self.network.num_nodes, tot), np.uint8)
-        m = np.zeros(tot, np.float64)
-        e = np.zeros(tot, np.int32)
+        ev, n, vals, m, e = self._debug_outputs(evidence, self.num_samples)
         lam = np.zeros((n, self.sum_dom), np.float64)
         lib.fbn_epis_debug_samples(self._h, _p(ev), *self._run_args(n, case_offset), _p(vals), _p(m), _p(e), _p(lam))
         return vals, m, e, lam
@@ -1144,17 +1141,8 @@ class EPISBN(_Handle):
         lib.fbn_epis_last_kernel_ms(self._h, C.byref(a), C.byref(b))
         return a.value, b.value
 
-    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
-        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
-        labels, marg = self.infer(evidence)
-        acc = float(np.mean(labels == np.asarray(ground_truths)))
-        if golden is None:
-            return acc
-        mse, hd = score_marginals(self.network, marg, golden)
-        return acc, mse / len(labels), hd / len(labels)
 
-
-class AISBN(_Handle):
+class AISBN(_CaseInference, _Handle):
     """AIS-BN (fbn_ais, method 0; the reference's -a 10 stub, src/main.cpp:175-186), mirroring EPISBN:
     max_updates (-m) learning stages of `interval` (-l) samples, each followed by an update of the
     importance CPT of the evidence's unobserved ancestors from the stage's weighted family counts,
@@ -1169,11 +1157,7 @@ class AISBN(_Handle):
         self.network = network
         self.num_samples, self.seed = int(num_samples), int(seed)
         self.max_updates, self.interval = int(max_updates), int(interval)
-        self.eps = -1.0 if eps is None else float(eps)
-        if eps is not None and self.eps < 0.0:  # the C entry reads a negative eps as "the defaults"
-            err = FastBNError(f"eps {eps!r}: in [0, 1), or None for the defaults")
-            err.code = -1  # FBN_ERR_ARG
-            raise err
+        self.eps = self._eps_arg(eps)
         self.sum_dom = int(np.sum(network.dims))
         self.stats = None
         h = C.c_void_p()
@@ -1196,11 +1180,7 @@ class AISBN(_Handle):
         self.stats = (log_evidence, ess, updates applied, ess / n of the first stage) per case.
         case_offset: the global index of the first case (a batch split over calls gives the bits of the
         whole batch)."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        labels = np.zeros(n, np.int32)
-        marg = np.zeros((n, self.sum_dom), np.float64) if marginals else None
-        st = np.zeros((n, 4), np.float64)
+        ev, n, labels, marg, st = self._outputs(evidence, marginals, 4)
         lib.fbn_ais_run(self._h, self._method, _p(ev), *self._run_args(n, case_offset), _p(labels), _p(marg), _p(st))
         self.stats = (st[:, 0].copy(), st[:, 1].copy(), st[:, 2].astype(np.int32), st[:, 3].copy())
         return labels, marg
@@ -1218,12 +1198,7 @@ class AISBN(_Handle):
         """Every draw behind infer(evidence): (values uint8 [V][ncases * T], mantissas fp64, exponents
         int32 [ncases * T], the importance CPT after the last update fp64 [ncases][cells]); draw t of
         case c at c * T + t, T = draws_per_case."""
-        ev = np.ascontiguousarray(evidence, dtype=np.int8)
-        n = ev.shape[0]
-        tot = n * self.draws_per_case
-        vals = np.zeros((self.network.num_nodes, tot), np.uint8)
-        m = np.zeros(tot, np.float64)
-        e = np.zeros(tot, np.int32)
+        ev, n, vals, m, e = self._debug_outputs(evidence, self.draws_per_case)
         icpt = np.zeros((n, self.info()["state_bytes"] // 16), np.float64)
         lib.fbn_ais_debug_samples(self._h, self._method, _p(ev), *self._run_args(n, case_offset), _p(vals), _p(m), _p(e),
                                   _p(icpt))
@@ -1252,15 +1227,6 @@ class AISBN(_Handle):
         ms = C.c_float()
         lib.fbn_ais_last_kernel_ms(self._h, C.byref(ms))
         return ms.value
-
-    def EvaluateAccuracy(self, evidence, ground_truths, golden=None):
-        """Accuracy of the query-variable arg-max (+ average MSE/HD vs golden if given)."""
-        labels, marg = self.infer(evidence)
-        acc = float(np.mean(labels == np.asarray(ground_truths)))
-        if golden is None:
-            return acc
-        mse, hd = score_marginals(self.network, marg, golden)
-        return acc, mse / len(labels), hd / len(labels)
 
 
 class SelfImportanceSampling(AISBN):

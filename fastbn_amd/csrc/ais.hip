@@ -19,8 +19,6 @@
 // or from a learning stage's last chunk to the next stage's first (sm, sc).
 #include <hip/hip_runtime.h>
 
-#include <climits>
-
 #include "ais_model.h"
 #include "launchers.h"
 
@@ -62,15 +60,16 @@ __global__ __launch_bounds__(64) void sample_ais_kernel(AisDeviceArgs A) {
         for (int j = lane; j < V; j += 64) lrn[j] = lrn[j] && ev[j] < 0;
         __syncthreads();
         U128 s;
-        int emax = 0, upd = 0;
-        double sumw = 0.0, sumw2 = 0.0, ess0 = 0.0;
+        fbn::WeightState ws;
+        int upd = 0;
+        double ess0 = 0.0;
         bool first = true;  // the next chunk opens the scope of emax, the sums and the counts
         long long tbase = 0;
         for (long long st = 0; st <= nupd; ++st) {
             const long long n = st < nupd ? A.sch.l : A.sch.last;
             const bool counted = A.method == 1 || st == nupd, learn = st < nupd;
             if (A.method == 0 || st == 0) {
-                first = true, sumw = 0.0, sumw2 = 0.0;
+                first = true, ws.sumw = 0.0, ws.sumw2 = 0.0;
                 if (learn) {
                     for (long long j = lane; j < cells; j += 64) N[j] = 0.0;
                     __syncthreads();
@@ -111,17 +110,8 @@ __global__ __launch_bounds__(64) void sample_ais_kernel(AisDeviceArgs A) {
                     vals[nd.v * 64 + lane] = (uint8_t)q;
                     if (A.dv && active) A.dv[(long long)nd.v * total + c * T + t] = (uint8_t)q;
                 }
-                if (A.dm && active) {
-                    A.dm[c * T + t] = m;
-                    A.de[c * T + t] = e;
-                }
-                const int cm = fbn::wave_max(active ? e : INT_MIN);
-                double f = 1.0;
-                if (first) emax = cm;
-                else if (cm > emax) f = ldexp(1.0, emax - cm), emax = cm;
-                const double w = active ? ldexp(m, e - emax) : 0.0;
-                sumw = sumw * f + fbn::wave_sum(w);
-                sumw2 = sumw2 * f * f + fbn::wave_sum(w * w);
+                double f;
+                const double w = fbn::chunk_weights(ws, m, e, active, first, A.dm, A.de, c * T + t, &f);
                 wl[lane] = w;
                 if (learn && f != 1.0)
                     for (long long j = lane; j < cells; j += 64) N[j] = N[j] * f;
@@ -151,9 +141,9 @@ __global__ __launch_bounds__(64) void sample_ais_kernel(AisDeviceArgs A) {
                 __syncthreads();
                 first = false;
             }
-            if (st == 0) ess0 = sumw > 0.0 ? sumw * sumw / sumw2 / (double)n : 0.0;
+            if (st == 0) ess0 = fbn::WeightEss(ws) / (double)n;
             if (learn) {  // update st: a row (x, pc) per lane
-                if (sumw > 0.0) ++upd;
+                if (ws.sumw > 0.0) ++upd;
                 const double eta = A.eta[st];
                 for (int k = 0; k < V; ++k) {
                     const SampleNode nd = A.M.nodes[k];
@@ -166,30 +156,14 @@ __global__ __launch_bounds__(64) void sample_ais_kernel(AisDeviceArgs A) {
             }
             tbase += n;
         }
-        if (sumw > 0.0) {
-            for (int j = lane; j < SD; j += 64) row[j] = ev[A.M.ent[j] >> 8] >= 0 ? 0.0 : row[j] / sumw;
-        } else {
-            for (int j = lane; j < SD; j += 64) row[j] = 0.0;
-        }
         if (A.di)
             for (long long j = lane; j < cells; j += 64) A.di[c * cells + j] = I[j];
-        __syncthreads();  // the row's entries are other lanes' stores; I and the flags are rewritten next
-        if (lane == 0) {
-            int lab = -1;
-            if (sumw > 0.0) {
-                lab = 0;
-                double mp = 0.0;  // ArgMax, strict '>' from 0 (src/Inference.cpp:92-102), as fbn_jt_run
-                for (int q = 0; q < A.M.d0; ++q)
-                    if (row[q] > mp) mp = row[q], lab = q;
-            }
-            A.labels[c] = lab;
-            if (A.stats) {
-                double *o = A.stats + 4 * c;
-                o[0] = sumw > 0.0 ? log(sumw / (double)A.S) + (double)emax * 0.6931471805599453 : -INFINITY;
-                o[1] = sumw > 0.0 ? sumw * sumw / sumw2 : 0.0;
-                o[2] = (double)upd;
-                o[3] = ess0;
-            }
+        double *o = A.stats ? A.stats + 4 * c : nullptr;
+        // its barrier also stands between the reads of I above and the next case's rewrite of I and the flags
+        fbn::finish_case(A.M, ev, row, ws, A.S, A.labels + c, o, lane);
+        if (lane == 0 && o) {
+            o[2] = (double)upd;
+            o[3] = ess0;
         }
     }
 }

@@ -61,20 +61,21 @@ int HostAis(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases,
             }
             for (int v = 0; v < V; ++v) lrn[v] = lrn[v] && e_row[v] < 0;
             std::copy(M.prob.begin(), M.prob.end(), I.begin());
-            int emax = 0, upd = 0;
-            double sumw = 0.0, sumw2 = 0.0, ess0 = 0.0;
+            WeightState ws;
+            int upd = 0;
+            double ess0 = 0.0;
             bool first = true;  // the next chunk opens the scope of emax, the sums and the counts
             int64_t tbase = 0;
             for (int64_t st = 0; st <= sch.nupd; ++st) {
                 const int64_t n = st < sch.nupd ? sch.l : sch.last;
                 const bool counted = method == 1 || st == sch.nupd, learn = st < sch.nupd;
                 if (method == 0 || st == 0) {
-                    first = true, sumw = 0.0, sumw2 = 0.0;
+                    first = true, ws.sumw = 0.0, ws.sumw2 = 0.0;
                     if (learn) std::fill(N.begin(), N.end(), 0.0);
                 }
                 for (int64_t s0 = 0; s0 < n; s0 += 64) {
                     const int act = (int)std::min<int64_t>(64, n - s0);
-                    double mm[64], w[64], w2[64];
+                    double mm[64], w[64];
                     int e[64];
                     for (int ln = 0; ln < act; ++ln) {
                         const uint64_t i = (uint64_t)(case_offset + c) * (uint64_t)sch.T + (uint64_t)(tbase + s0 + ln);
@@ -107,23 +108,8 @@ int HostAis(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases,
                         mm[ln] = mant, e[ln] = ee;
                         if (dbg_m) dbg_m[di] = mant, dbg_e[di] = ee;
                     }
-                    int cm = INT_MIN;
-                    for (int ln = 0; ln < act; ++ln) cm = std::max(cm, e[ln]);
-                    double f = 1.0;
-                    if (first) emax = cm;
-                    else if (cm > emax) f = ldexp(1.0, emax - cm), emax = cm;
-                    for (int ln = 0; ln < 64; ++ln) {
-                        w[ln] = ln < act ? ldexp(mm[ln], e[ln] - emax) : 0.0;
-                        w2[ln] = w[ln] * w[ln];
-                    }
-                    if (counted)
-                        for (int j = 0; j < SD; ++j) {
-                            const int v = M.ent[j] >> 8, q = M.ent[j] & 255;
-                            double acc = first ? 0.0 : row[j] * f;
-                            const uint8_t *xv = x.data() + (size_t)v * 64;
-                            for (int ln = 0; ln < act; ++ln) acc += xv[ln] == q ? w[ln] : 0.0;
-                            row[j] = acc;
-                        }
+                    const double f = HostChunkWeights(ws, mm, e, act, first, w);
+                    if (counted) HostAccumulateChunk(M, x.data(), w, act, f, first, row);
                     if (learn) {
                         if (f != 1.0)
                             for (int64_t j = 0; j < cells; ++j) N[(size_t)j] = N[(size_t)j] * f;
@@ -135,13 +121,11 @@ int HostAis(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases,
                             }
                         }
                     }
-                    sumw = sumw * f + Butterfly(w);
-                    sumw2 = sumw2 * f * f + Butterfly(w2);
                     first = false;
                 }
-                if (st == 0) ess0 = sumw > 0.0 ? sumw * sumw / sumw2 / (double)n : 0.0;
+                if (st == 0) ess0 = WeightEss(ws) / (double)n;
                 if (learn) {
-                    if (sumw > 0.0) ++upd;
+                    if (ws.sumw > 0.0) ++upd;
                     for (int k = 0; k < V; ++k) {
                         const SampleNode &nd = M.nodes[k];
                         if (!lrn[nd.v]) continue;
@@ -152,24 +136,9 @@ int HostAis(const SamplerModel &M, int method, const int8_t *ev, int64_t ncases,
                 }
                 tbase += n;
             }
-            int lab = -1;
-            if (sumw > 0.0) {
-                for (int j = 0; j < SD; ++j) row[j] = e_row[M.ent[j] >> 8] >= 0 ? 0.0 : row[j] / sumw;
-                lab = 0;
-                double mp = 0.0;  // ArgMax, strict '>' from 0 (src/Inference.cpp:92-102), as fbn_jt_run
-                for (int q = 0; q < M.dom[0]; ++q)
-                    if (row[q] > mp) mp = row[q], lab = q;
-            } else {
-                std::fill(row, row + SD, 0.0);
-            }
-            labels[c] = lab;
-            if (stats) {
-                double *st = stats + 4 * c;
-                st[0] = sumw > 0.0 ? log(sumw / (double)S) + (double)emax * 0.6931471805599453 : -INFINITY;
-                st[1] = sumw > 0.0 ? sumw * sumw / sumw2 : 0.0;
-                st[2] = (double)upd;
-                st[3] = ess0;
-            }
+            double *st = stats ? stats + 4 * c : nullptr;
+            HostFinishCase(M, e_row, row, ws, S, labels + c, st);
+            if (st) st[2] = (double)upd, st[3] = ess0;
             if (dbg_icpt) std::copy(I.begin(), I.end(), dbg_icpt + c * cells);
         }
     });

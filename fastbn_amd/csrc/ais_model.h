@@ -109,26 +109,16 @@ int CheckAisArgs(const SamplerModel &M, int method, int64_t ncases, int64_t S, i
 
 namespace fbn {
 
-// sample_ais_kernel's arguments (ais.hip; filled by capi_ais.hip)
-struct AisDeviceArgs {
-    DeviceModel M;
-    U128 state, inc, jm, jc;  // the jump of 63 V positions (the same lane's sample in the next chunk)
-    U128 sm, sc;              // a learning stage's last chunk to the next stage's first: (l - 64 ((l - 1) / 64) - 1) V
-    uint64_t jump[256];       // this seed's 2^j jump pairs (PcgStream::jump), read from the kernel arguments
-    const int8_t *ev;         // [ncases][V], checked
-    long long ncases, S, case0, cells;
+// sample_ais_kernel's arguments (ais.hip; filled by capi_ais.hip); stats [ncases][4], draws = sch.T
+struct AisDeviceArgs : SampleCaseArgs {
+    U128 sm, sc;  // a learning stage's last chunk to the next stage's first: (l - 64 ((l - 1) / 64) - 1) V
+    long long cells;
     int method;
     AisSchedule sch;
     double eps;         // < 0: EpisCutoff's defaults
     const double *eta;  // [sch.nupd]
     double *ws;         // state in global memory: [grid][2 * cells], or NULL (state in LDS)
-    int32_t *labels;
-    double *marg;   // [ncases][sum_dom]: accumulators, then the result
-    double *stats;  // [ncases][4] or NULL
-    uint8_t *dv;    // debug (all or none): values [V][ncases * T], mantissas, exponents [ncases * T], ICPT
-    double *dm;
-    int32_t *de;
-    double *di;  // [ncases][cells]
+    double *di;         // debug, with dv: the ICPT after the last update [ncases][cells]
 };
 
 }  // namespace fbn

@@ -13,6 +13,7 @@
 
 using fbn::DevBuf;
 using fbn::SetError;
+using fbn::Upload;
 
 // what a workgroup's dynamic LDS may hold without a function attribute
 static constexpr int64_t kLbpLdsDefault = 64 * 1024;
@@ -38,13 +39,6 @@ struct fbn_lbp {
 };
 
 namespace {
-
-template <class T>
-int Upload(DevBuf &b, const std::vector<T> &v) {
-    if (int rc = b.ensure(std::max<size_t>(v.size() * sizeof(T), 16))) return rc;
-    if (!v.empty()) FBN_HIP(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FBN_OK;
-}
 
 // d_lambda: LbpDeviceArgs::lambda or NULL.  checked: the caller has range-checked the evidence already.
 int LbpDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double tol, double damping, int32_t *d_labels,

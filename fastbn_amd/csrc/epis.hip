@@ -12,11 +12,8 @@
 // over the d states, so no per-lane array exists and nothing goes to scratch.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-
 #include "epis_model.h"
 #include "launchers.h"
-#include "sample_device.h"
 
 using fbn::EpisDeviceArgs;
 using fbn::SampleNode;
@@ -40,11 +37,11 @@ __global__ __launch_bounds__(64) void sample_epis_kernel(EpisDeviceArgs A) {
     }
     const long long total = A.ncases * A.S;
     U128 s;
-    int emax = 0;
-    double sumw = 0.0, sumw2 = 0.0;
+    fbn::WeightState ws;
     for (long long s0 = 0; s0 < A.S; s0 += 64) {
         const bool active = s0 + lane < A.S;  // a tail lane samples (in bounds) with weight 0
-        if (s0 == 0)
+        const bool first = s0 == 0;           // this chunk opens the scope of emax and the sums
+        if (first)
             s = fbn::PcgJumpTo(A.state, ((uint64_t)(A.case0 + c) * (uint64_t)A.S + (uint64_t)lane) * (uint64_t)V, A.jump);
         else
             s = fbn::Affine(s, A.jm, A.jc);
@@ -68,43 +65,17 @@ __global__ __launch_bounds__(64) void sample_epis_kernel(EpisDeviceArgs A) {
             vals[nd.v * 64 + lane] = (uint8_t)q;
             if (A.dv && active) A.dv[(long long)nd.v * total + c * A.S + s0 + lane] = (uint8_t)q;
         }
-        if (A.dm && active) {
-            A.dm[c * A.S + s0 + lane] = m;
-            A.de[c * A.S + s0 + lane] = e;
-        }
-        const int cm = fbn::wave_max(active ? e : INT_MIN);
-        double f = 1.0;
-        if (s0 == 0) emax = cm;
-        else if (cm > emax) f = ldexp(1.0, emax - cm), emax = cm;
-        const double w = active ? ldexp(m, e - emax) : 0.0;
-        sumw = sumw * f + fbn::wave_sum(w);
-        sumw2 = sumw2 * f * f + fbn::wave_sum(w * w);
+        double f;
+        const double w = fbn::chunk_weights(ws, m, e, active, first, A.dm, A.de, c * A.S + s0 + lane, &f);
         __syncthreads();
-        fbn::accumulate_marginals(A.M, vals, row, w, f, s0 == 0, lane);
+        fbn::accumulate_marginals(A.M, vals, row, w, f, first, lane);
         __syncthreads();
     }
-    if (sumw > 0.0) {
-        for (int j = lane; j < SD; j += 64) row[j] = ev[A.M.ent[j] >> 8] >= 0 ? 0.0 : row[j] / sumw;
-    } else {
-        for (int j = lane; j < SD; j += 64) row[j] = 0.0;
-    }
-    __syncthreads();  // the row's entries are other lanes' stores
-    if (lane == 0) {
-        int lab = -1;
-        if (sumw > 0.0) {
-            lab = 0;
-            double mp = 0.0;  // ArgMax, strict '>' from 0 (src/Inference.cpp:92-102), as fbn_jt_run
-            for (int q = 0; q < A.M.d0; ++q)
-                if (row[q] > mp) mp = row[q], lab = q;
-        }
-        A.labels[c] = lab;
-        if (A.stats) {
-            double *st = A.stats + 4 * c;
-            st[0] = sumw > 0.0 ? log(sumw / (double)A.S) + (double)emax * 0.6931471805599453 : -INFINITY;
-            st[1] = sumw > 0.0 ? sumw * sumw / sumw2 : 0.0;
-            st[2] = A.lbp_stats ? A.lbp_stats[2 * c] : 0.0;
-            st[3] = A.lbp_stats ? A.lbp_stats[2 * c + 1] : 0.0;
-        }
+    double *st = A.stats ? A.stats + 4 * c : nullptr;
+    fbn::finish_case(A.M, ev, row, ws, A.S, A.labels + c, st, lane);
+    if (lane == 0 && st) {
+        st[2] = A.lbp_stats ? A.lbp_stats[2 * c] : 0.0;
+        st[3] = A.lbp_stats ? A.lbp_stats[2 * c + 1] : 0.0;
     }
 }
 

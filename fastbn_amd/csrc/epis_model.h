@@ -78,4 +78,19 @@ int CheckEpisArgs(const SamplerModel &M, int64_t ncases, int64_t S, int64_t case
 
 }  // namespace fbn
 
+#if defined(__HIPCC__)
+#include "sample_device.h"
+
+namespace fbn {
+
+// sample_epis_kernel's arguments (epis.hip; filled by capi_epis.hip); stats [ncases][4], draws = S
+struct EpisDeviceArgs : SampleCaseArgs {
+    double eps;               // < 0: EpisCutoff's defaults
+    const double *lam;        // [ncases][sum_dom]
+    const double *lbp_stats;  // [ncases][2] or NULL (no pre-propagation: zeros)
+};
+
+}  // namespace fbn
+#endif
+
 #endif

@@ -1,5 +1,5 @@
-// fbn_device.h -- device plumbing shared by the files that own device memory (capi_*.hip, sample.hip):
-// the HIP error macro, the growable buffers, the gfx950 device check, the evidence range check.
+// fbn_device.h -- device plumbing shared by the files that own device memory (capi_*.hip):
+// the HIP error macro, the growable buffers, the table upload, the gfx950 device check, the evidence range check.
 // Internal to libfastbn.
 #ifndef FBN_DEVICE_H
 #define FBN_DEVICE_H
@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "fbn_internal.h"
 #include "launchers.h"
@@ -44,6 +45,14 @@ struct DevBuf {
         return static_cast<T *>(p);
     }
 };
+
+// a host table into b (grown to fit; never empty, so its pointer is always valid)
+template <class T>
+int Upload(DevBuf &b, const std::vector<T> &v) {
+    if (int rc = b.ensure(std::max<size_t>(v.size() * sizeof(T), 16))) return rc;
+    if (!v.empty()) FBN_HIP(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return FBN_OK;
+}
 
 inline int CheckDevice(int device, int *num_cu) {
     int n = 0;

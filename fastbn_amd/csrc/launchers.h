@@ -1,7 +1,7 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits.hip,
-// ci_gram_mfma.hip, lbp.hip, epis.hip, ais.hip) and by every caller (capi_*.hip, sample.hip), so a definition that disagrees with
-// its declaration does not compile.  Internal to libfastbn.  (pc_small.h and param_counts.h carry
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip) and by every caller (capi_*.hip), so a
+// definition that disagrees with its declaration does not compile.  Internal to libfastbn.  (pc_small.h and param_counts.h carry
 // their own kernels' launchers.)
 #ifndef FBN_LAUNCHERS_H
 #define FBN_LAUNCHERS_H
@@ -108,11 +108,17 @@ extern "C" hipError_t fbn_jt_lds_launch(const JtOp *ops, int nops, const int32_t
 // lds != 0: the messages in lds_bytes of LDS per workgroup; else in a->ws, 3 * a->M doubles per workgroup
 extern "C" hipError_t fbn_lbp_launch(const fbn::LbpDeviceArgs *a, int lds, size_t lds_bytes, int grid,
                                      hipStream_t stream);
-// EPIS-BN's sampling kernel (sample_device.h's arguments), one workgroup per case; lds_lambda != 0: the
-// case's lambda row in LDS behind the values.  fbn_epis_fill: p[0 .. n) = x.
+// The sampling engine's kernels (sample_device.h's arguments): forward sampling, 64 samples per one-wave
+// workgroup, and likelihood weighting / logic sampling, one workgroup per case.
 namespace fbn {
+struct ForwardDeviceArgs;
+struct LwDeviceArgs;
 struct EpisDeviceArgs;
 }
+extern "C" hipError_t fbn_sample_forward_launch(const fbn::ForwardDeviceArgs *a, hipStream_t stream);
+extern "C" hipError_t fbn_lw_launch(const fbn::LwDeviceArgs *a, hipStream_t stream);
+// EPIS-BN's sampling kernel (epis_model.h's arguments), one workgroup per case; lds_lambda != 0: the
+// case's lambda row in LDS behind the values.  fbn_epis_fill: p[0 .. n) = x.
 extern "C" hipError_t fbn_epis_launch(const fbn::EpisDeviceArgs *a, int lds_lambda, hipStream_t stream);
 extern "C" hipError_t fbn_epis_fill(double *p, long long n, double x, hipStream_t stream);
 // The adaptive samplers' kernel (ais_model.h's arguments): a persistent grid of `grid` one-wave

@@ -148,6 +148,42 @@ double Butterfly(double *a) {
     return a[0];
 }
 
+double HostChunkWeights(WeightState &ws, const double *m, const int *e, int act, bool first, double *w) {
+    int cm = INT_MIN;
+    for (int l = 0; l < act; ++l) cm = std::max(cm, e[l]);
+    const double f = WeightRescale(ws, cm, first);
+    double a[64], a2[64];
+    for (int l = 0; l < 64; ++l) {
+        w[l] = a[l] = l < act ? ldexp(m[l], e[l] - ws.emax) : 0.0;
+        a2[l] = w[l] * w[l];
+    }
+    const double sw = Butterfly(a);
+    WeightAdd(ws, f, sw, Butterfly(a2));
+    return f;
+}
+
+void HostAccumulateChunk(const SamplerModel &M, const uint8_t *x, const double *w, int act, double f, bool first,
+                         double *row) {
+    for (int j = 0; j < M.sum_dom; ++j) {
+        const int v = M.ent[j] >> 8, q = M.ent[j] & 255;
+        double acc = first ? 0.0 : row[j] * f;
+        const uint8_t *xv = x + (size_t)v * 64;
+        for (int l = 0; l < act; ++l) acc += xv[l] == q ? w[l] : 0.0;
+        row[j] = acc;
+    }
+}
+
+void HostFinishCase(const SamplerModel &M, const int8_t *e_row, double *row, const WeightState &ws, int64_t S,
+                    int32_t *label, double *stats) {
+    if (ws.sumw > 0.0) {
+        for (int j = 0; j < M.sum_dom; ++j) row[j] = e_row[M.ent[j] >> 8] >= 0 ? 0.0 : row[j] / ws.sumw;
+    } else {
+        std::fill(row, row + M.sum_dom, 0.0);
+    }
+    *label = QueryLabel(row, M.dom[0], ws.sumw);
+    if (stats) stats[0] = WeightLogEvidence(ws, S), stats[1] = WeightEss(ws);
+}
+
 int HostForward(const SamplerModel &M, int64_t n, uint64_t seed, uint8_t *cols) {
     if (n == 0) return FBN_OK;
     PcgStream R;
@@ -208,11 +244,10 @@ int HostImportance(const SamplerModel &M, int method, const int8_t *ev, int64_t 
         for (int64_t c = c0; c < c1; ++c) {
             const int8_t *e_row = ev + c * V;
             double *row = marg ? marg + c * SD : own.data();
-            int emax = 0;
-            double sumw = 0.0, sumw2 = 0.0;
+            WeightState ws;
             for (int64_t s0 = 0; s0 < S; s0 += 64) {
                 const int act = (int)std::min<int64_t>(64, S - s0);
-                double m[64], w[64], w2[64];
+                double m[64], w[64];
                 int e[64];
                 for (int l = 0; l < act; ++l) {
                     const uint64_t i = (uint64_t)(case_offset + c) * (uint64_t)S + (uint64_t)(s0 + l);
@@ -246,42 +281,12 @@ int HostImportance(const SamplerModel &M, int method, const int8_t *ev, int64_t 
                     m[l] = mm, e[l] = ee;
                     if (dbg_m) dbg_m[(size_t)c * S + s0 + l] = mm, dbg_e[(size_t)c * S + s0 + l] = ee;
                 }
-                int cm = INT_MIN;
-                for (int l = 0; l < act; ++l) cm = std::max(cm, e[l]);
-                double f = 1.0;
-                if (s0 == 0) emax = cm;
-                else if (cm > emax) f = ldexp(1.0, emax - cm), emax = cm;
-                for (int l = 0; l < 64; ++l) {
-                    w[l] = l < act ? ldexp(m[l], e[l] - emax) : 0.0;
-                    w2[l] = w[l] * w[l];
-                }
-                for (int j = 0; j < SD; ++j) {
-                    const int v = M.ent[j] >> 8, q = M.ent[j] & 255;
-                    double acc = s0 == 0 ? 0.0 : row[j] * f;
-                    const uint8_t *xv = x.data() + (size_t)v * 64;
-                    for (int l = 0; l < act; ++l) acc += xv[l] == q ? w[l] : 0.0;
-                    row[j] = acc;
-                }
-                sumw = sumw * f + Butterfly(w);
-                sumw2 = sumw2 * f * f + Butterfly(w2);
+                const double f = HostChunkWeights(ws, m, e, act, s0 == 0, w);
+                HostAccumulateChunk(M, x.data(), w, act, f, s0 == 0, row);
             }
-            int lab = -1;
-            if (sumw > 0.0) {
-                for (int j = 0; j < SD; ++j) row[j] = e_row[M.ent[j] >> 8] >= 0 ? 0.0 : row[j] / sumw;
-                lab = 0;
-                double mp = 0.0;  // ArgMax, strict '>' from 0 (src/Inference.cpp:92-102), as fbn_jt_run
-                for (int q = 0; q < M.dom[0]; ++q)
-                    if (row[q] > mp) mp = row[q], lab = q;
-            } else {
-                std::fill(row, row + SD, 0.0);
-            }
-            labels[c] = lab;
-            if (stats) {
-                double *st = stats + (lam ? 4 : 2) * c;
-                st[0] = sumw > 0.0 ? log(sumw / (double)S) + (double)emax * 0.6931471805599453 : -INFINITY;
-                st[1] = sumw > 0.0 ? sumw * sumw / sumw2 : 0.0;
-                if (lam) st[2] = lbp_stats ? lbp_stats[2 * c] : 0.0, st[3] = lbp_stats ? lbp_stats[2 * c + 1] : 0.0;
-            }
+            double *st = stats ? stats + (lam ? 4 : 2) * c : nullptr;
+            HostFinishCase(M, e_row, row, ws, S, labels + c, st);
+            if (st && lam) st[2] = lbp_stats ? lbp_stats[2 * c] : 0.0, st[3] = lbp_stats ? lbp_stats[2 * c + 1] : 0.0;
         }
     });
     return FBN_OK;

@@ -1,8 +1,10 @@
 // sample_model.h -- what the sampling engine's host twin (sample_host.cpp) and its kernels
-// (sample.hip) share: the flattened network, numpy's PCG64 in 64-bit halves, the value-selection rule.
+// (sample.hip) share, and with them EPIS-BN's and the adaptive samplers': the flattened network, numpy's
+// PCG64 in 64-bit halves, the value-selection rule, the scaled-weight arithmetic of a case.
 #ifndef FBN_SAMPLE_MODEL_H
 #define FBN_SAMPLE_MODEL_H
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <functional>
@@ -100,6 +102,41 @@ FBN_HD U128 PcgJumpTo(U128 s, uint64_t delta, const uint64_t *jump) {
     return s;
 }
 
+// ---- the scaled weights of one case, the arithmetic every sampling kernel and host twin compiles.  A
+// sample weighs ldexp(m, e); a chunk's weights are taken relative to the largest exponent seen since the
+// scope opened, w = ldexp(m, e - emax), and sumw, sumw2 are the sums of w and w^2 on that scale.
+struct WeightState {
+    int emax = 0;
+    double sumw = 0.0, sumw2 = 0.0;
+};
+// Open or rescale: cm is the chunk's maximum exponent, first says that this chunk opens the scope.  Sets
+// emax and returns the exact power of two f by which everything summed so far is multiplied.
+FBN_HD double WeightRescale(WeightState &ws, int cm, bool first) {
+    double f = 1.0;
+    if (first) ws.emax = cm;
+    else if (cm > ws.emax) f = ldexp(1.0, ws.emax - cm), ws.emax = cm;
+    return f;
+}
+// the chunk's sums of w and w^2 (butterfly order) join the rescaled running sums
+FBN_HD void WeightAdd(WeightState &ws, double f, double sw, double sw2) {
+    ws.sumw = ws.sumw * f + sw;
+    ws.sumw2 = ws.sumw2 * f * f + sw2;
+}
+FBN_HD double WeightLogEvidence(const WeightState &ws, long long S) {
+    return ws.sumw > 0.0 ? log(ws.sumw / (double)S) + (double)ws.emax * 0.6931471805599453 : -INFINITY;
+}
+FBN_HD double WeightEss(const WeightState &ws) { return ws.sumw > 0.0 ? ws.sumw * ws.sumw / ws.sumw2 : 0.0; }
+// the query label from the case's normalised row: ArgMax, strict '>' from 0 (src/Inference.cpp:92-102), as
+// fbn_jt_run; -1 when no sample weighs anything
+FBN_HD int QueryLabel(const double *row, int d0, double sumw) {
+    if (!(sumw > 0.0)) return -1;
+    int lab = 0;
+    double mp = 0.0;
+    for (int q = 0; q < d0; ++q)
+        if (row[q] > mp) mp = row[q], lab = q;
+    return lab;
+}
+
 // what the host twins share (sample_host.cpp, ais_host.cpp): the thread count (at most 16, at most
 // OMP_NUM_THREADS); fn(begin, end) over [0, n) in contiguous ranges of at least `grain`, in parallel; the
 // sum over 64 lanes in the kernels' butterfly order (lane i adds lane i ^ off, off = 32 .. 1; a is
@@ -112,6 +149,17 @@ inline int ParentConfig(const SamplerModel &M, const SampleNode &nd, const uint8
     for (int j = 0; j < nd.npar; ++j) pc = pc * M.par[2 * (nd.poff + j) + 1] + x[(size_t)M.par[2 * (nd.poff + j)] * vs];
     return pc;
 }
+// One 64-sample chunk of a case on the host, as the kernels' chunk tail: from the mantissas and exponents
+// of its act samples, rescale ws (first: the chunk opens the scope), write the weights w[0 .. 64) (0.0 from
+// act on), add their sums to ws, return f.  w stays intact: the butterflies run on copies.
+double HostChunkWeights(WeightState &ws, const double *m, const int *e, int act, bool first, double *w);
+// the chunk's marginal sums by entry into the case's row: samples l < act in ascending order (x: values [V][64])
+void HostAccumulateChunk(const SamplerModel &M, const uint8_t *x, const double *w, int act, double f, bool first,
+                         double *row);
+// the kernels' case tail: normalise the row (observed variables and a weightless case: zeros), the query
+// label, stats[0 .. 2) = log_evidence, ess unless stats is NULL
+void HostFinishCase(const SamplerModel &M, const int8_t *e_row, double *row, const WeightState &ws, int64_t S,
+                    int32_t *label, double *stats);
 
 // the host path (device < 0 samplers, tools/sample_host_check.cpp): the kernels' algorithm, chunk
 // for chunk, on CPU threads.  Arguments are checked by the callers except the evidence codes.
