@@ -30,6 +30,7 @@ from .api import (  # noqa: F401
     FastBNError,
     Network,
     Dataset,
+    JunctionForest,
     JunctionTree,
     IndependenceTest,
     PCStable,
@@ -54,7 +55,7 @@ from .api import (  # noqa: F401
     kernel_options,
 )
 
-__all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
+__all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
            "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -36,6 +36,8 @@ _SIGS = {
     "fbn_dataset_var_name": [_vp, C.c_int, C.c_char_p, C.c_int],
     "fbn_dataset_destroy": [_vp],
     "fbn_jt_plan_create": [_vp, C.c_int, _pp],
+    "fbn_jt_forest_plan_create": [_vp, C.c_int, _pp],
+    "fbn_jt_plan_components": [_vp, _vp, _vp],
     "fbn_jt_plan_info_get": [_vp, _vp],
     "fbn_jt_plan_dump": [_vp, _cstr, _cstr],
     "fbn_jt_run": [_vp, _vp, _i64, _vp, _vp, _vp],
@@ -399,11 +401,12 @@ class JunctionTree(_Handle):
     """Batched JT inference on one device (JunctionTree ctor + PredictUseJTInfer over all cases)."""
 
     _destroy = "fbn_jt_plan_destroy"
+    _create = "fbn_jt_plan_create"
 
     def __init__(self, network, device=0):
         self.network = network
         h = C.c_void_p()
-        lib.fbn_jt_plan_create(network._h, device, C.byref(h))
+        getattr(lib, self._create)(network._h, device, C.byref(h))
         self._h = h
         _register(self)
         self.output_layout = 0
@@ -559,6 +562,21 @@ class JunctionTree(_Handle):
         mse, hd = self.score(marg, golden)
         return acc, mse / len(labels), hd / len(labels)
 
+
+class JunctionForest(JunctionTree):
+    """JunctionTree for any DAG (fbn_jt_forest_plan_create): where the moral graph is disconnected --
+    JunctionTree raises -- one tree per component, none joined to another, so the cost is the sum of
+    the trees' and exact inference stays exact.  On a connected network it is JunctionTree's plan.
+    components: the moral graph's components as sorted node lists, ordered by their lowest node."""
+
+    _create = "fbn_jt_forest_plan_create"
+
+    def __init__(self, network, device=0):
+        super().__init__(network, device)
+        comp = np.zeros(self.info["num_nodes"], np.int32)
+        n = C.c_int32()
+        lib.fbn_jt_plan_components(self._h, _p(comp), C.byref(n))
+        self.components = [np.flatnonzero(comp == k).tolist() for k in range(n.value)]
 
 
 class IndependenceTest(_Handle):

@@ -59,7 +59,8 @@ static int JtUpload(fbn_jt_plan *p) {
     return FBN_OK;
 }
 
-int fbn_jt_plan_create(const fbn_network *net, int device, fbn_jt_plan **out) {
+// forest: a disconnected moral graph gives one tree per component (fbn_jt_forest_plan_create)
+static int JtPlanCreate(const fbn_network *net, int device, bool forest, fbn_jt_plan **out) {
     if (!net || !out) return SetError(FBN_ERR_ARG, "null pointer");
     auto p = std::unique_ptr<fbn_jt_plan>(new (std::nothrow) fbn_jt_plan());
     if (!p) return SetError(FBN_ERR_NOMEM, "out of memory");
@@ -71,7 +72,7 @@ int fbn_jt_plan_create(const fbn_network *net, int device, fbn_jt_plan **out) {
         fprintf(stderr, "plan %s: %.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp0).count());
         tp0 = t;
     };
-    int rc = fbn::BuildJTPlan(net->net, p->host);
+    int rc = fbn::BuildJTPlan(net->net, p->host, forest);
     if (rc) return rc;
     lap("structure");
     rc = fbn::CompileJTProgram(p->host, p->prog);
@@ -104,6 +105,21 @@ int fbn_jt_plan_create(const fbn_network *net, int device, fbn_jt_plan **out) {
         FBN_HIP(hipEventCreate(&p->ev1));
     }
     *out = p.release();
+    return FBN_OK;
+}
+
+int fbn_jt_plan_create(const fbn_network *net, int device, fbn_jt_plan **out) {
+    return JtPlanCreate(net, device, false, out);
+}
+
+int fbn_jt_forest_plan_create(const fbn_network *net, int device, fbn_jt_plan **out) {
+    return JtPlanCreate(net, device, true, out);
+}
+
+int fbn_jt_plan_components(const fbn_jt_plan *p, int32_t *component_of_node, int32_t *num_components) {
+    if (!p || !num_components) return SetError(FBN_ERR_ARG, "null pointer");
+    *num_components = p->host.num_components;
+    if (component_of_node) std::copy(p->host.component_of_node.begin(), p->host.component_of_node.end(), component_of_node);
     return FBN_OK;
 }
 
@@ -191,6 +207,11 @@ int fbn_jt_plan_dump(const fbn_jt_plan *p, const char *plan_path, const char *in
         fprintf(f, " | up %d | down %d\n", h.sep_up[i], h.sep_down[i]);
     }
     fprintf(f, "root %d\n", h.root);
+    if (h.roots.size() > 1) {  // a forest: the roots of all trees, in component order
+        fprintf(f, "roots %zu", h.roots.size());
+        for (int r : h.roots) fprintf(f, " %d", r);
+        fprintf(f, "\n");
+    }
     fprintf(f, "levels %zu\n", h.levels.size());
     for (size_t l = 0; l < h.levels.size(); ++l) {
         fprintf(f, "level %zu %c", l, (l % 2) ? 's' : 'c');

@@ -30,12 +30,17 @@ int TestSet::Load(const std::string &path, int n) {
 JunctionTree::JunctionTree(fbn_network *net, TestSet *tester, int device, int gpus)
     : net_(net), tester_(tester), device_(device), gpus_(gpus) {
     auto t0 = std::chrono::steady_clock::now();
-    if (fbn_jt_plan_create(net, device, &plan_)) Die("JunctionTree");
+    // the forest entry: the same plan on a connected moral graph, one tree per component otherwise
+    if (fbn_jt_forest_plan_create(net, device, &plan_)) Die("JunctionTree");
     fbn_jt_plan_info_get(plan_, &info_);
+    int32_t components = 1;
+    fbn_jt_plan_components(plan_, nullptr, &components);
     double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "Finish FormJunctionTree, number of cliques = " << info_.num_cliques
               << ", number of separators = " << info_.num_separators << std::endl;
     std::cout << "Finish MarkLevel, maximum level of the junction tree = " << info_.num_levels << std::endl;
+    if (components > 1)
+        std::cout << "The moral graph is disconnected: junction forest of " << components << " components" << std::endl;
     std::cout << "==================================================" << std::endl
               << "construct jt: " << s << " s " << std::endl;
 }
@@ -142,7 +147,8 @@ std::string JunctionTree::RunSharded(const std::vector<double> &golden, float *k
         ncclComm_t comm = g.comm(r);
         std::string e;
         fbn_jt_plan *plan = plan_;
-        if (r > 0 && fbn_jt_plan_create(net_, g.device(r), &plan)) return std::string("fbn_jt_plan_create: ") + fbn_last_error();
+        if (r > 0 && fbn_jt_forest_plan_create(net_, g.device(r), &plan))
+            return std::string("fbn_jt_forest_plan_create: ") + fbn_last_error();
         const int64_t c0 = std::min<int64_t>(n, r * chunk), nr = std::min<int64_t>(n, c0 + chunk) - c0;
         void *d_ev = nullptr, *d_lab = nullptr, *d_all = nullptr, *d_marg = nullptr, *d_k = nullptr, *d_gold = nullptr,
              *d_terms = nullptr, *d_tall = nullptr;

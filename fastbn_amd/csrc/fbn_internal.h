@@ -77,13 +77,20 @@ struct JTPlanHost {
     int num_nodes = 0;
     std::vector<int> dom;
     std::vector<Table> cliques, seps;  // initial potentials after ReorganizeTableStorage
-    std::vector<int> clique_up;                 // upstream separator, -1 for the root
+    std::vector<int> clique_up;                 // upstream separator, -1 for a root
     std::vector<std::vector<int>> clique_down;  // downstream separators (MarkLevel order)
     std::vector<int> sep_up, sep_down;          // parent clique, child clique
-    int root = -1;
+    int root = -1;                              // = roots[0]
     std::vector<std::vector<int>> levels;       // even levels: cliques, odd levels: separators
+    // junction forest: one tree per component of the moral graph (components numbered by their
+    // lowest node), never joined -- roots[k] is the root of component k's tree, level i holds level i
+    // of every tree.  A connected network has one component and roots = {root}.
+    std::vector<int> roots;
+    std::vector<int> component_of_node;
+    int num_components = 0;
 };
-int BuildJTPlan(const Network &net, JTPlanHost &plan);
+// forest = false: a disconnected moral graph is an error (FBN_ERR_ARG)
+int BuildJTPlan(const Network &net, JTPlanHost &plan, bool forest = false);
 
 // device program (see jt_program.h) compiled from the host plan
 struct JTProgram {
@@ -104,7 +111,7 @@ struct JTProgramLDS {
     std::vector<int32_t> aux;
     std::vector<double> initv;
     std::vector<uint64_t> dig;
-    int64_t store_entries = 0;  // parked collect tables (all cliques but the root)
+    int64_t store_entries = 0;  // parked collect tables (all cliques but plan.root)
     int64_t sep_entries = 0;    // separator messages
     int64_t max_table = 0;      // largest clique table (LDS rows needed for no spill)
     int num_cliques = 0;

@@ -682,7 +682,7 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
             return r;
         };
         auto early_lb = [&](int c) {
-            const int64_t held = (c != plan.root) ? plan.seps[plan.clique_up[c]].size() : 0;
+            const int64_t held = (plan.clique_up[c] >= 0) ? plan.seps[plan.clique_up[c]].size() : 0;
             return tsize(c) + kids_rows(c) + held <= budget;
         };
         std::vector<int64_t> need(2 * nc + 1, 0);
@@ -717,14 +717,14 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
                 if (md_reg[s]) need[t] += plan.seps[s].size();
             }
             need[t] += std::min<int64_t>(tsize(c), kRegEntries) + (early ? kids_rows(c) : kmax);
-            if (c != plan.root) {
+            if (up >= 0) {
                 need[t] += plan.seps[up].size();
                 touch[t].push_back(2 * up + 1);
                 if (md_reg[up]) pend += plan.seps[up].size();
             }
             if (k + 1 < nc) {
-                const int nx = pre[k + 1], nup = plan.clique_up[nx];
-                const bool ld_next = !md_reg[nup] && plan.sep_up[nup] != c;
+                const int nx = pre[k + 1], nup = plan.clique_up[nx];  // (nup < 0: the next tree's root)
+                const bool ld_next = nup >= 0 && !md_reg[nup] && plan.sep_up[nup] != c;
                 const int64_t nrows = (early_lb(nx) ? kids_rows(nx) : 0) + (ld_next ? plan.seps[nup].size() : 0);
                 if (tsize(c) + pend + nrows <= budget) {
                     need[t] += nrows;
@@ -925,7 +925,7 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
             for (int s : plan.clique_down[c]) weight[c] += w(child(s));
             return weight[c];
         };
-        w(plan.root);
+        for (int r : plan.roots) w(r);
     }
     // visit: 0 = plan order, 1 = heaviest subtree first, 2 = heaviest subtree last
     auto dfs = [&](bool collect, int visit, std::vector<int> &post_o, std::vector<int> &pre_o) {
@@ -942,8 +942,14 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
                     return visit == 1 ? weight[child(x)] > weight[child(y)] : weight[child(x)] < weight[child(y)];
                 });
         }
-        std::vector<std::pair<int, size_t>> st{{plan.root, 0}};
-        while (!st.empty()) {  // iterative DFS
+        // a forest: tree after tree -- Collect in component order, Distribute in the reverse, so the
+        // root collected last is the one distributed first (it continues from its Collect registers)
+        std::vector<int> roots = plan.roots;
+        if (!collect) std::reverse(roots.begin(), roots.end());
+        std::vector<std::pair<int, size_t>> st;
+        size_t next_root = 0;
+        while (!st.empty() || next_root < roots.size()) {  // iterative DFS
+            if (st.empty()) st.push_back({roots[next_root++], 0});
             auto &top = st.back();
             const int c = top.first;
             if (top.second == 0) pre_o.push_back(c);
@@ -1170,15 +1176,21 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
         for (int s : ls) r += plan.seps[s].size();
         return r;
     };
+    // The root collected last stays in registers for its Distribute.  Every other root of a forest
+    // sends no message, so its Collect is left out; its Distribute recomputes the table like any
+    // clique's, from the initial potential and the children's stored messages.
+    const int cont_root = post.back() == pre.front() ? pre.front() : -1;
     std::vector<bool> loaded_a(ns, false);
     for (size_t k = 0; k < post.size(); ++k) {
         const int c = post[k];
+        if (plan.clique_up[c] < 0 && c != cont_root) continue;
         std::vector<int> mine, next;
         collect_loads(k, mine);
         o << "        // ---- collect clique " << c << " (" << tsize(c) << " entries)\n";
         for (int s : mine)
             if (!loaded_a[s]) Load("la", s), loaded_a[s] = true;
-        if (k + 1 < post.size()) {  // prefetch for the next clique
+        const bool next_runs = k + 1 < post.size() && (plan.clique_up[post[k + 1]] >= 0 || post[k + 1] == cont_root);
+        if (next_runs) {  // prefetch for the next clique
             collect_loads(k + 1, next);
             int64_t pend = 0;
             for (int s : mine) pend += plan.seps[s].size();
@@ -1201,8 +1213,8 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
             }
         }
         // merge the message's sums with the next clique's product when both are small
-        in_merged = fast && (merge & 2) && c != plan.root && k + 1 < post.size() && tsize(c) + tsize(post[k + 1]) <= 96;
-        if (c != plan.root) SepCol("t", c, plan.clique_up[c], col_store[plan.clique_up[c]]);
+        in_merged = fast && (merge & 2) && c != cont_root && k + 1 < post.size() && tsize(c) + tsize(post[k + 1]) <= 96;
+        if (c != cont_root) SepCol("t", c, plan.clique_up[c], col_store[plan.clique_up[c]]);
     }
     in_merged = false;
     // ---------------- Distribute, DFS pre-order (root continues from its Collect registers)
@@ -1219,7 +1231,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
     };
     auto early_lb = [&](int c) {
         const int up = plan.clique_up[c];
-        const int64_t held = (c != plan.root) ? plan.seps[up].size() : 0;  // in registers at DMul either way
+        const int64_t held = (up >= 0) ? plan.seps[up].size() : 0;  // in registers at DMul either way
         return tsize(c) + kids_rows(c) + held <= kBudget;
     };
     std::vector<bool> loaded_b(ns, false), loaded_d(ns, false);
@@ -1234,11 +1246,12 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
                 if (!loaded_b[s]) LoadCol("lb", s), loaded_b[s] = true;
                 pend += plan.seps[s].size();
             }
-        if (c != plan.root && md_reg[up]) pend += plan.seps[up].size();
+        if (up >= 0 && md_reg[up]) pend += plan.seps[up].size();
         if (k + 1 < pre.size()) {  // prefetch for the next clique (before this clique's stores)
             const int nx = pre[k + 1], nup = plan.clique_up[nx];
-            // its parent message, unless still in registers or produced by this clique
-            const bool ld_next = !md_reg[nup] && plan.sep_up[nup] != c;
+            // its parent message, unless still in registers or produced by this clique (or it has
+            // none: the next tree's root)
+            const bool ld_next = nup >= 0 && !md_reg[nup] && plan.sep_up[nup] != c;
             const int64_t nrows = (early_lb(nx) ? kids_rows(nx) : 0) + (ld_next ? plan.seps[nup].size() : 0);
             if (tsize(c) + pend + nrows + reg_extra[nc + k] <= kBudget) {
                 if (early_lb(nx))
@@ -1249,21 +1262,23 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
         }
         o << B(1);
         std::string P = "t";
-        if (c != plan.root && fast && early) {  // all messages in registers: one fused op
+        if (c != cont_root && fast && early) {  // all messages in registers: one fused op
             P = "u";
-            if (!md_reg[up] && !loaded_d[up]) Load("ld", up), loaded_d[up] = true, o << B(1);
+            if (up >= 0 && !md_reg[up] && !loaded_d[up]) Load("ld", up), loaded_d[up] = true, o << B(1);
             std::vector<std::pair<int, std::string>> kids;
             for (int s : plan.clique_down[c]) kids.push_back({s, "lb"});
-            InitProd(P, c, kids, up, md_reg[up] ? "md" : "ld");
-        } else if (c != plan.root) {
+            InitProd(P, c, kids, up, up < 0 ? "" : md_reg[up] ? "md" : "ld");
+        } else if (c != cont_root) {
             P = "u";  // recompute the Collect table (same ops, same order -> same bits)
             Init(P, c);
             for (int s : plan.clique_down[c]) {
                 if (!early) LoadCol("lb", s), o << B(1);
                 Mul(P, c, s, "lb");
             }
-            if (!md_reg[up] && !loaded_d[up]) Load("ld", up), loaded_d[up] = true, o << B(1);
-            DMul(P, c, up, md_reg[up] ? "md" : "ld");
+            if (up >= 0) {
+                if (!md_reg[up] && !loaded_d[up]) Load("ld", up), loaded_d[up] = true, o << B(1);
+                DMul(P, c, up, md_reg[up] ? "md" : "ld");
+            }
         }
         const auto &down = plan.clique_down[c];
         // consumers of the normalized table: one SepDis per child, one marginal per variable

@@ -7,6 +7,12 @@
 // order of the reference's std::set<Separator*>), root = first clique with the fewest BFS levels,
 // MarkLevel order, CPT factors multiplied into the first containing clique in node order, and
 // ReorganizeTableStorage putting each clique's upstream separator variables last.
+//
+// A disconnected moral graph (forest = true) gives a junction forest: one tree per component, each
+// exactly the tree BuildJTPlan builds for that component alone.  The trees are not joined: a root
+// per component (clique_up = -1), level i of the plan = level i of every tree in component order.
+// No separator crosses components, so no compiler sees an empty separator, a forest costs the sum
+// of its trees, and the product of the components' evidence likelihoods is never formed.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -51,7 +57,7 @@ int LocOf(const Table &t, int v) {
 
 }  // namespace
 
-int BuildJTPlan(const Network &net, JTPlanHost &plan) {
+int BuildJTPlan(const Network &net, JTPlanHost &plan, bool forest) {
     const int n = net.n();
     plan = JTPlanHost();
     plan.num_nodes = n;
@@ -73,7 +79,25 @@ int BuildJTPlan(const Network &net, JTPlanHost &plan) {
             }
     }
 
-    // triangulation by repeated min-neighbour elimination (src/JunctionTreeStructure.cpp:128-222)
+    // components of the moral graph, numbered by their lowest node
+    plan.component_of_node.assign(n, -1);
+    plan.num_components = 0;
+    for (int r = 0; r < n; ++r) {
+        if (plan.component_of_node[r] >= 0) continue;
+        std::vector<int> stack{r};
+        plan.component_of_node[r] = plan.num_components;
+        while (!stack.empty()) {
+            const int i = stack.back();
+            stack.pop_back();
+            for (int j = 0; j < n; ++j)
+                if (g.get(i, j) && plan.component_of_node[j] < 0) plan.component_of_node[j] = plan.num_components, stack.push_back(j);
+        }
+        ++plan.num_components;
+    }
+
+    // triangulation by repeated min-neighbour elimination (src/JunctionTreeStructure.cpp:128-222).
+    // A node's neighbours lie in its own component and ties go to the lowest index, so the global
+    // order restricted to one component is that component's standalone order, and so are its cliques.
     std::vector<std::vector<int>> cliques;  // sorted variable lists, creation = container order
     std::vector<bool> done(n, false);
     for (int step = 0; step < n; ++step) {
@@ -133,7 +157,18 @@ int BuildJTPlan(const Network &net, JTPlanHost &plan) {
             if (in_tree[cand[k].a] == in_tree[cand[k].b]) continue;
             if (best < 0 || best_w < cand[k].vars.size()) best = k, best_w = cand[k].vars.size();
         }
-        if (best < 0) return SetError(FBN_ERR_ARG, "moral graph is disconnected: junction forest unsupported");
+        if (best < 0) {
+            if (!forest) return SetError(FBN_ERR_ARG, "moral graph is disconnected: junction forest unsupported");
+            // the tree of the components so far is complete: restart at the lowest clique left, which is
+            // where the standalone Prim of its component starts (every candidate that crosses the tree's
+            // edge from here on lies in that component, in the standalone creation order)
+            for (int c = 0; c < nc; ++c)
+                if (!in_tree[c]) {
+                    in_tree[c] = 1, ++n_in;
+                    break;
+                }
+            continue;
+        }
         chosen.push_back(best);
         for (int c : {cand[best].a, cand[best].b})
             if (!in_tree[c]) in_tree[c] = 1, ++n_in;
@@ -208,16 +243,17 @@ int BuildJTPlan(const Network &net, JTPlanHost &plan) {
     }
 
     // root selection and levelling (src/JunctionTree.cpp:15-24, 137-225)
+    // (a BFS stays in the component of its start: a forest is levelled one tree at a time)
+    plan.clique_down.assign(nc, {});
+    plan.sep_down.assign(ns, -1);
+    plan.clique_up.assign(nc, -2);
+    plan.sep_up.assign(ns, -2);
     auto bfs = [&](int r, bool record) {
         std::vector<int> up_c(nc, -2), up_s(ns, -2);
         up_c[r] = -1;
         std::vector<int> cur{r};
         std::vector<std::vector<int>> lv{cur};
         bool sep_level = false;
-        if (record) {
-            plan.clique_down.assign(nc, {});
-            plan.sep_down.assign(ns, -1);
-        }
         while (!cur.empty()) {
             std::vector<int> nxt;
             for (int x : cur) {
@@ -243,19 +279,27 @@ int BuildJTPlan(const Network &net, JTPlanHost &plan) {
         }
         lv.pop_back();
         if (record) {
-            plan.levels = lv;
-            plan.clique_up = up_c;
-            plan.sep_up = up_s;
+            if (plan.levels.size() < lv.size()) plan.levels.resize(lv.size());
+            for (size_t i = 0; i < lv.size(); ++i) plan.levels[i].insert(plan.levels[i].end(), lv[i].begin(), lv[i].end());
+            for (int c = 0; c < nc; ++c)
+                if (up_c[c] != -2) plan.clique_up[c] = up_c[c];
+            for (int s = 0; s < ns; ++s)
+                if (up_s[s] != -2) plan.sep_up[s] = up_s[s];
         }
         return (int)lv.size();
     };
-    int root = 0, min_lv = bfs(0, false);
-    for (int c = 1; c < nc; ++c) {
-        int l = bfs(c, false);
-        if (l < min_lv) min_lv = l, root = c;
+    // per component (in component order): root = its first clique with the fewest levels
+    for (int k = 0; k < plan.num_components; ++k) {
+        int root = -1, min_lv = 0;
+        for (int c = 0; c < nc; ++c) {
+            if (plan.component_of_node[cliques[c][0]] != k) continue;
+            int l = bfs(c, false);
+            if (root < 0 || l < min_lv) min_lv = l, root = c;
+        }
+        plan.roots.push_back(root);
+        bfs(root, true);
     }
-    plan.root = root;
-    bfs(root, true);
+    plan.root = plan.roots.empty() ? -1 : plan.roots[0];
 
     // ReorganizeTableStorage (src/JunctionTree.cpp:235-281, TableReorganizationPre/Main/Post
     // src/PotentialTable.cpp:215-292)
@@ -432,7 +476,9 @@ int CompileJTProgramLDS(const JTPlanHost &plan, JTProgramLDS &prog) {
     std::vector<int64_t> store_off(nc, -1), sep_off(ns);
     for (int c = 0; c < nc; ++c) {
         prog.max_table = std::max<int64_t>(prog.max_table, plan.cliques[c].size());
-        if (c == plan.root) continue;  // the root never leaves LDS between the two phases
+        // the root never leaves LDS between the two phases (a forest: the first tree's root; the
+        // other roots are parked like any clique, without a message either way)
+        if (c == plan.root) continue;
         store_off[c] = prog.store_entries;
         prog.store_entries += plan.cliques[c].size();
     }
@@ -494,7 +540,9 @@ int CompileJTProgramLDS(const JTPlanHost &plan, JTProgramLDS &prog) {
     const int L = (int)plan.levels.size();
     // Collect: clique levels deepest first (src/JunctionTree.cpp:1240-1306)
     for (int i = ((L - 1) / 2) * 2; i >= 0; i -= 2) {
-        for (int c : plan.levels[i]) {
+        std::vector<int> lv = plan.levels[i];
+        if (i == 0) std::reverse(lv.begin(), lv.end());  // roots: plan.root last, Distribute starts with it
+        for (int c : lv) {
             const Table &t = plan.cliques[c];
             int rc = emit_init(c);
             if (rc) return rc;
@@ -511,7 +559,7 @@ int CompileJTProgramLDS(const JTPlanHost &plan, JTProgramLDS &prog) {
             }
             if (c != plan.root) {
                 int s = plan.clique_up[c];
-                op(JT_L_SEPCOL, sep_off[s], plan.seps[s].size(), t.size(), 0, 0);
+                if (s >= 0) op(JT_L_SEPCOL, sep_off[s], plan.seps[s].size(), t.size(), 0, 0);
                 op(JT_L_STORE, store_off[c], t.size(), c, 0, 0);
             }
         }
@@ -523,7 +571,7 @@ int CompileJTProgramLDS(const JTPlanHost &plan, JTProgramLDS &prog) {
             if (c != plan.root) {
                 int s = plan.clique_up[c];
                 op(JT_L_LOAD, store_off[c], t.size(), c, 0, 0);
-                op(JT_L_DMUL, 0, t.size(), 0, sep_off[s], plan.seps[s].size());
+                if (s >= 0) op(JT_L_DMUL, 0, t.size(), 0, sep_off[s], plan.seps[s].size());
             }
             for (int s : plan.clique_down[c]) {
                 const int64_t Ts = plan.seps[s].size(), per = t.size() / Ts;

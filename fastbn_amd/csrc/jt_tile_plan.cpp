@@ -140,8 +140,11 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
     // DFS orders
     std::vector<int> post, pre;
     {
-        std::vector<std::pair<int, size_t>> st{{plan.root, 0}};
-        while (!st.empty()) {
+        // (a forest: tree after tree, in component order)
+        std::vector<std::pair<int, size_t>> st;
+        size_t next_root = 0;
+        while (!st.empty() || next_root < plan.roots.size()) {
+            if (st.empty()) st.push_back({plan.roots[next_root++], 0});
             auto &top = st.back();
             const int c = top.first;
             if (top.second == 0) pre.push_back(c);
@@ -642,9 +645,9 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
     };
 
     int rc;
-    // ---- Collect (post-order, the root has no upstream separator)
+    // ---- Collect (post-order, a root has no upstream separator)
     for (int c : post) {
-        if (c == plan.root) continue;
+        if (plan.clique_up[c] < 0) continue;
         std::vector<Factor> fac;
         for (int s : plan.clique_down[c]) fac.push_back({&plan.seps[s], col[s], col_sc[s], -1});
         int nst;
@@ -663,7 +666,7 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
         const Table &t = plan.cliques[c];
         std::vector<Factor> fac;
         for (int s : plan.clique_down[c]) fac.push_back({&plan.seps[s], col[s], col_sc[s], -1});
-        const bool has_parent = c != plan.root;
+        const bool has_parent = plan.clique_up[c] >= 0;
         if (has_parent)
             fac.push_back({&plan.seps[plan.clique_up[c]], dis[plan.clique_up[c]], dis_sc[plan.clique_up[c]], -1});
         int nst;

@@ -72,8 +72,11 @@ int CompileJTProgramV(const JTPlanHost &plan, JTProgramV &prog) {
     // DFS orders (iterative)
     std::vector<int> post, pre;
     {
-        std::vector<std::pair<int, size_t>> st{{plan.root, 0}};
-        while (!st.empty()) {
+        // (a forest: tree after tree, in component order)
+        std::vector<std::pair<int, size_t>> st;
+        size_t next_root = 0;
+        while (!st.empty() || next_root < plan.roots.size()) {
+            if (st.empty()) st.push_back({plan.roots[next_root++], 0});
             auto &top = st.back();
             const int c = top.first;
             if (top.second == 0) pre.push_back(c);
@@ -99,8 +102,10 @@ int CompileJTProgramV(const JTPlanHost &plan, JTProgramV &prog) {
             sub[c] = cost[c];
             for (int s : plan.clique_down[c]) sub[c] += sub[plan.sep_down[s]];
         }
-        const int64_t total = sub[plan.root];
-        std::vector<int> cand{plan.root};
+        // (a forest starts from every tree's root: whole trees go to the waves, no top needed)
+        int64_t total = 0;
+        for (int r : plan.roots) total += sub[r];
+        std::vector<int> cand = plan.roots;
         std::vector<char> top(nc, 0);
         while (JT_V_WAVES > 1) {
             size_t bi = 0;
@@ -179,7 +184,7 @@ int CompileJTProgramV(const JTPlanHost &plan, JTProgramV &prog) {
         const int64_t T = t.size();
         const int nv = (int)t.vars.size();
         const int k = (int)plan.clique_down[c].size();
-        const bool root = c == plan.root;
+        const bool root = plan.clique_up[c] < 0;
         JtVClique &q = prog.cl[c];
         q.T = (int32_t)T;
         q.nv = nv;

@@ -47,21 +47,46 @@ def fixture_xmls(dirname):
     return out
 
 
+def _load_tests_module(name):
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location(name, os.path.join(REPO, "tests", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    keep, sys.dont_write_bytecode = sys.dont_write_bytecode, True  # (leave tests/ as it is)
+    try:
+        spec.loader.exec_module(mod)
+    finally:
+        sys.dont_write_bytecode = keep
+    return mod
+
+
 def count_map_nets():
     """The eligible count-map networks of the GPU tests (tests/test_gpu_jt_range.py,
     tests/test_gpu_jt_counts.py), from the tests' own generators (tests/jt_nets.py, plain Python):
     [(namespace with dims / parents / counts, output layouts)]."""
-    import importlib.util
-    import sys
-    spec = importlib.util.spec_from_file_location("jt_nets", os.path.join(REPO, "tests", "jt_nets.py"))
-    J = importlib.util.module_from_spec(spec)
-    keep, sys.dont_write_bytecode = sys.dont_write_bytecode, True  # (leave tests/ as it is)
-    try:
-        spec.loader.exec_module(J)
-    finally:
-        sys.dont_write_bytecode = keep
+    J = _load_tests_module("jt_nets")
     return [(J.conflict_net(*J.CONFLICT_FORMS["xmlbif"]), (0,)), (J.conflict_net(*J.CONFLICT_FORMS["counts"]), (0, 1)),
             (J.counts_net(J.COUNTS_SEED, "small"), (0,)), (J.counts_net(J.COUNTS_SEED, "dom32"), (0,))]
+
+
+def prebuild_forests(dirname):
+    """The junction forests of the GPU tests (tests/test_gpu_jt_forest.py, networks from
+    tests/jt_forest_nets.py): the small disconnected network in both orders and layouts, the random
+    disconnected network and the 60-component network in the default order."""
+    N = _load_tests_module("jt_forest_nets")
+    out = []
+    jf = api.JunctionForest(api.Network.from_counts(*N.disconnected()), device=-1)
+    for layout in (0, 1):
+        jf.set_output_layout(layout)
+        for exact in (None, True):
+            jf.set_exact(exact)
+            out.append(jf.build_kernel())
+    star = N.star_net()
+    path = os.path.join(dirname, "forest.xml")
+    synth.random_network(path=path, **N.RANDOM)
+    for net in (api.Network.from_counts(star.dims, star.parents, star.counts), api.Network(path)):
+        out.append(api.JunctionForest(net, device=-1).build_kernel())
+    return out
 
 
 def prebuild_count_maps():
@@ -104,6 +129,7 @@ def prebuild_default(clean=True):
     generator versions)."""
     with tempfile.TemporaryDirectory() as d:
         built = prebuild([ALARM_XML], layouts=(0, 1)) + prebuild([synth_small_xml(d)] + fixture_xmls(d))
+        built += prebuild_forests(d)
     built += prebuild_options(ALARM_XML, ALARM_TEST_OPTIONS)
     # (tests/test_gpu_jt_regpool.py compares the register pool on / off in both output layouts)
     built += prebuild_options(ALARM_XML, ({"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"}), layout=1)

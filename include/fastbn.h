@@ -123,6 +123,19 @@ typedef struct {
  * :137-281), compile it to a device program and upload it to `device`.  device < 0 builds a
  * host-only plan (info / dump; runs return FBN_ERR_NODEV). */
 int fbn_jt_plan_create(const fbn_network *net, int device, fbn_jt_plan **out);
+/* The same plan for any DAG: where the moral graph is disconnected (fbn_jt_plan_create: FBN_ERR_ARG)
+ * this builds a junction FOREST -- per component exactly the tree fbn_jt_plan_create builds for that
+ * component alone (an isolated node: one clique of one variable), one root per component, nothing
+ * passed between the trees (a message across components would be the constant 1).  Its cost is the
+ * sum of its trees'; the product of the components' evidence likelihoods is never formed.  The
+ * result is an ordinary plan: every fbn_jt_* call takes it, in every kernel variant whose limits the
+ * trees meet.  On a connected network the plan is fbn_jt_plan_create's, byte for byte in
+ * fbn_jt_plan_dump (a forest's dump adds one line, "roots <n> <clique> ...", after "root"). */
+int fbn_jt_forest_plan_create(const fbn_network *net, int device, fbn_jt_plan **out);
+/* Components of the plan's moral graph, numbered by their lowest node: component_of_node
+ * [num_nodes] (NULL: the count alone).  A plan from fbn_jt_plan_create has one. */
+int fbn_jt_plan_components(const fbn_jt_plan *p, int32_t *component_of_node /* [num_nodes] or NULL */,
+                           int32_t *num_components);
 int fbn_jt_plan_info_get(const fbn_jt_plan *p, fbn_jt_plan_info *info);
 /* Text dump in the same format as the reference harness (tests/golden/alarm_1k.plan/.init). */
 int fbn_jt_plan_dump(const fbn_jt_plan *p, const char *plan_path, const char *init_path);
