@@ -26,7 +26,7 @@ namespace fbn {
 int CiBand(fbn_ci_ctx *c, double alpha, hipStream_t s, const double **out, int *nband, int want_df) {
     *out = nullptr;
     *nband = 0;
-    if (!(alpha > 0.0 && alpha < 1.0) || getenv("FBN_CI_NO_BAND")) return FBN_OK;
+    if (!(alpha > 0.0 && alpha < 1.0) || fbn::KnobSet("FBN_CI_NO_BAND")) return FBN_OK;
     const int want = std::min(kBandDfMax, std::max(kBandDf, want_df));
     if (c->band_alpha != alpha || c->band_n < want) {
         const double delta = alpha / 1024;
@@ -236,7 +236,7 @@ constexpr int64_t kGram0MaxBytes = (int64_t)1 << 30;
 static bool CiGram0Eligible(const fbn_ci_ctx *c) {
     int64_t R = 0;
     for (int v = 0; v < c->nvars; ++v) R += c->dims[v] - 1;
-    return R > 0 && R * R * 4 <= kGram0MaxBytes && !getenv("FBN_CI_NO_GRAM");
+    return R > 0 && R * R * 4 <= kGram0MaxBytes && !fbn::KnobSet("FBN_CI_NO_GRAM");
 }
 
 // 8 x 8 tiles (i-block <= j-block) of the leading-row Gram holding a pair (x < y) of [t0, t1): row
@@ -307,7 +307,7 @@ static int CiGram0Mfma(fbn_ci_ctx *c, int64_t t0, int64_t n, hipStream_t s, bool
     *done = false;
     const int64_t R = (int64_t)c->leadrows_host.size(), T = fbn_ci_gram4_tile(), KT = fbn_ci_gram4_stage();
     const int64_t Rp = (R + T - 1) / T * T, KS = (c->N + KT - 1) / KT, Kb = KS * KT / 2;
-    if (getenv("FBN_CI_GRAM_NO_MFMA") || (double)R * R * c->N < 1e10 || Rp * Kb > kOnehot4MaxBytes || KS > INT32_MAX)
+    if (fbn::KnobSet("FBN_CI_GRAM_NO_MFMA") || (double)R * R * c->N < 1e10 || Rp * Kb > kOnehot4MaxBytes || KS > INT32_MAX)
         return FBN_OK;
     int rc;
     if (!c->onehot4_ready) {
@@ -338,7 +338,7 @@ static int CiGram0Mfma(fbn_ci_ctx *c, int64_t t0, int64_t n, hipStream_t s, bool
     }
     // split-K: about one block per CU; uint16 partials need every slice <= 65535 samples
     const int nt = c->g4_nt;
-    int64_t S = std::max<int64_t>(1, EnvOr0("FBN_CI_GRAM4_SPLITS", c->num_cu / nt));
+    int64_t S = std::max<int64_t>(1, fbn::KnobOr("FBN_CI_GRAM4_SPLITS", c->num_cu / nt));
     S = std::max<int64_t>(S, (KS + 510) / 511);  // slices of <= 511 stages x 128 samples
     S = std::min<int64_t>(S, KS);
     // slice `split` covers stages [split * KS / S, (split + 1) * KS / S): floor or ceil of KS / S
@@ -442,8 +442,8 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
     // bit-sliced columns (ci_bits.hip).  From 4096 samples up (ALARM-5000 included: 0.46 -> 0.40 ms
     // per PC run with the pair-table level 1); below, the byte-column kernel (untuned regime).
     const int64_t kBitsMinSamples = 4096;
-    const bool bits_path = d <= 1 && maxdim <= 4 && !getenv("FBN_CI_NO_BITS") &&
-                           (c->N >= kBitsMinSamples || getenv("FBN_CI_FORCE_BITS"));
+    const bool bits_path = d <= 1 && maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_BITS") &&
+                           (c->N >= kBitsMinSamples || fbn::KnobSet("FBN_CI_FORCE_BITS"));
     if (bits_path) {
         if ((rc = CiBitsEnsure(c, s))) return rc;
         if (!all_pairs && (rc = S.items.ensure((size_t)n * w * 4))) return rc;
@@ -483,7 +483,7 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
         if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
         // all pairs of a range: register-blocked count kernel (ci_bits_pairs_tiled), then phase 2
         const bool gram0 = all_pairs && d == 0 && CiGram0Eligible(c);
-        const bool tiled = all_pairs && d == 0 && !gram0 && !getenv("FBN_CI_NO_TILED");
+        const bool tiled = all_pairs && d == 0 && !gram0;
         if (tiled && (rc = CiPairTasks(c, pair0, pair0 + n, s))) return rc;
         if (all_pairs && d == 0) {  // fbn_ci_level0_info (the Gram branches below fill in theirs)
             std::fill(c->l0_info, c->l0_info + 8, 0);
@@ -500,7 +500,7 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
                 if ((rc = CiGram0Tasks(c, pair0, pair0 + n, s))) return rc;
                 c->l0_info[0] = 1, c->l0_info[1] = R, c->l0_info[4] = c->g0_ntasks;
                 e = fbn_ci_gram(c->bits.as<uint32_t>(), c->bits_W, c->leadrows.as<int32_t>(),
-                                c->g0tasks.as<int32_t>(), c->g0_ntasks, 0, c->gram0.as<int32_t>(), c->num_cu, s);
+                                c->g0tasks.as<int32_t>(), c->g0_ntasks, c->gram0.as<int32_t>(), c->num_cu, s);
             }
             if (e == hipSuccess)
                 e = fbn_ci_gram_pairs(c->gram0.as<int32_t>(), R, c->lead0.as<int32_t>(), c->ddims.as<int32_t>(),
@@ -508,15 +508,6 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
                                       S.bcounts.as<int32_t>(), pmode == 1 ? c->pairtab.as<int32_t>() : nullptr,
                                       c->num_cu, s);
             if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci gram level 0: %s", hipGetErrorString(e));
-        }
-        // level 1 with the per-variable Grams prepared (CiTriplePrepare): tables gathered from them
-        const bool gram1 = d == 1 && pmode == 2 && c->triples_ready && pre;  // driver batches only
-        if (gram1) {
-            e = fbn_ci_gram_triples(c->g1.as<int32_t>(), c->g1goff.as<long long>(), c->g1R.as<int32_t>(),
-                                    c->g1adj.as<int32_t>(), c->g1adjoff.as<int32_t>(), c->g1loff.as<int32_t>(),
-                                    c->ddims.as<int32_t>(), ditems, n, S.bcounts.as<int32_t>(),
-                                    c->pairtab.as<int32_t>(), c->nvars, c->num_cu, s);
-            if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci gram level 1: %s", hipGetErrorString(e));
         }
         if (tiled) {
             e = fbn_ci_bits_pairs_tiled(c->bits.as<uint32_t>(), c->brow.as<int32_t>(), c->browcnt.as<int32_t>(),
@@ -532,7 +523,7 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
                                           zc_indep ? zc_indep : S.indep.as<uint8_t>(),
                                           S.bcounts.as<int32_t>(), counts_dev, c->stats.as<unsigned long long>(),
                                           c->browcnt.as<int32_t>(), c->pairtab.as<int32_t>(), pmode, c->nvars,
-                                          c->num_cu, (long long)pair0, (tiled || gram0 || gram1) ? 1 : 0, band,
+                                          c->num_cu, (long long)pair0, (tiled || gram0) ? 1 : 0, band,
                                           nband, s);
         if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci bits kernel launch: %s", hipGetErrorString(e));
         if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
@@ -574,12 +565,12 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
     // (ci_kernels.hip) when it is built.  Opt-in: every z-configuration re-reads the x / y value rows,
     // so config 5 level 2 moves more bytes than the byte columns (0.79 vs 0.76 ms) and levels 3-5
     // are several times slower (up to 4^5 configurations per test)
-    const bool bitsn0 = d >= 2 && c->bits_ready && maxdim <= 4 && getenv("FBN_CI_BITSN");
+    const bool bitsn0 = d >= 2 && c->bits_ready && maxdim <= 4 && fbn::KnobSet("FBN_CI_BITSN");
     // d = 2 within a PC run (level-0 pair tables recorded), every state count <= 4, the bit-sliced
     // store built: derived counting of the leading cells (ci_kernels.hip MODE 3; FBN_CI_NO_DER2 = 1
     // takes the 2-bit packed histogram kernel instead)
     const bool der2 = d == 2 && c->bits_ready && maxdim <= 4 && c->pair_mode == 2 && c->pairs_recorded &&
-                      !global_tables && !getenv("FBN_CI_NO_DER2");
+                      !global_tables && !fbn::KnobSet("FBN_CI_NO_DER2");
     const bool bitsn = bitsn0 || der2;
     // decisions only: the decision band up to this batch's largest df ((maxdim-1)^2 maxdim^d)
     const double *hband = nullptr;
@@ -594,8 +585,8 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
     // context, 25 MB for config 5).  Config-5 level 2: 0.614 -> 0.589 ms (the kernel's binning, not
     // its column reads, bounds it); below 64k samples (ALARM-5000) the byte columns measured faster.
     // FBN_CI_PACK2 = 1 forces it at any size, FBN_CI_NO_PACK2 = 1 disables it.
-    const bool pk = !bitsn && maxdim <= 4 && !getenv("FBN_CI_NO_PACK2") &&
-                    (c->N >= 65536 || getenv("FBN_CI_PACK2"));
+    const bool pk = !bitsn && maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_PACK2") &&
+                    (c->N >= 65536 || fbn::KnobSet("FBN_CI_PACK2"));
     if (pk && (rc = CiPack2Ensure(c, s))) return rc;
     S.last_bytes = bitsn ? mask_rows * c->bits_W * 4  // the mask rows each z-configuration reads
                    : pk  ? n * c->pack2_W * 4 * (2 + d)  // the 2-bit columns x, y, z_1..z_d
@@ -606,10 +597,9 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
     int split = 1, split_grid = 0;
     int64_t tstride = 0;
     int32_t *tab = nullptr;
-    static const int split_env = getenv("FBN_CI_SPLIT") ? atoi(getenv("FBN_CI_SPLIT")) : -1;  // (tuning knob)
     if (pk && !bitsn && !global_tables) {
         const int64_t want = 4 * (int64_t)c->num_cu;  // counting workgroups to aim for
-        split = split_env >= 0 ? std::max(1, split_env) : (int)std::min<int64_t>(16, want / std::max<int64_t>(n, 1));
+        split = (int)std::min<int64_t>(16, want / std::max<int64_t>(n, 1));
         if (split > 1) {
             int64_t cmax = 1;
             for (int64_t i = 0; i < n; ++i) {
@@ -688,8 +678,8 @@ namespace {
 struct PairModeGuard {
     fbn_ci_ctx *c;
     int mode;
-    bool recorded, triples;
-    ~PairModeGuard() { c->pair_mode = mode, c->pairs_recorded = recorded, c->triples_ready = triples; }
+    bool recorded;
+    ~PairModeGuard() { c->pair_mode = mode, c->pairs_recorded = recorded; }
 };
 }  // namespace
 
@@ -709,7 +699,7 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
     int rc;
     const int nv = c->nvars;
     fbn::PCResultHost scratch;
-    PairModeGuard guard{c, c->pair_mode, c->pairs_recorded, c->triples_ready};
+    PairModeGuard guard{c, c->pair_mode, c->pairs_recorded};
     auto level0 = [&]() -> int {  // the PC run's level 0, pair tables recorded
         fbn::CiBatchStats st{0, 0};
         for (int v = 0; v < nv; ++v) st.dim_rows += (int64_t)(nv - 1) * c->dims[v], st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
@@ -794,7 +784,7 @@ int fbn_ci_debug_level0_range(fbn_ci_ctx *c, int64_t pair0, int64_t n, int32_t *
                         (long long)(pair0 + n), (long long)P);
     if (n == 0) return FBN_OK;
     FBN_HIP(hipSetDevice(c->device));
-    PairModeGuard guard{c, c->pair_mode, c->pairs_recorded, c->triples_ready};
+    PairModeGuard guard{c, c->pair_mode, c->pairs_recorded};
     fbn::CiBatchStats st{0, 0};
     int64_t R = 0;
     for (int v = 0; v < nv; ++v) {

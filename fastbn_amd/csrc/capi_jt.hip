@@ -64,7 +64,7 @@ static int JtPlanCreate(const fbn_network *net, int device, bool forest, fbn_jt_
     if (!net || !out) return SetError(FBN_ERR_ARG, "null pointer");
     auto p = std::unique_ptr<fbn_jt_plan>(new (std::nothrow) fbn_jt_plan());
     if (!p) return SetError(FBN_ERR_NOMEM, "out of memory");
-    static const bool ptime = getenv("FBN_PLAN_TIMING") != nullptr;  // diagnostic: plan phases
+    static const bool ptime = fbn::KnobSet("FBN_PLAN_TIMING");  // diagnostic: plan phases
     auto tp0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
         if (!ptime) return;
@@ -86,10 +86,10 @@ static int JtPlanCreate(const fbn_network *net, int device, bool forest, fbn_jt_
     if (!p->v_ok) p->vprog = fbn::JTProgramV();
     lap("streamed program");
     // tiled variant: factors of a clique phase staged in LDS up to this many bytes per wave
-    // LDS factor budget per workgroup (tuning knob): 6016 B + the bin and total rows = 10 KB, so 16
-    // one-wave workgroups fit a CU's 160 KB
-    static const int t_lds = getenv("FBN_JT_TLDS") ? atoi(getenv("FBN_JT_TLDS")) : 6016;
-    rc = fbn::CompileJTProgramT(p->host, p->tprog, t_lds);
+    // LDS factor budget per workgroup: 6016 B + the bin and total rows = 10 KB, so 16 one-wave
+    // workgroups fit a CU's 160 KB
+    constexpr int kTileLdsBytes = 6016;
+    rc = fbn::CompileJTProgramT(p->host, p->tprog, kTileLdsBytes);
     if (rc && rc != FBN_ERR_LIMIT) return rc;
     p->t_ok = rc == FBN_OK;
     if (!p->t_ok) p->tprog = fbn::JTProgramT();
@@ -400,9 +400,8 @@ static int LaunchLds(fbn_jt_plan *p, DevBuf &ws, const int8_t *d_evidence, int64
     const bool spill = cap < l.max_table;
     // fixup mode: flagged blocks are rare; one wave per CU scans the flags 64 at a time (the launch
     // follows every specialized / tiled launch: ~3 us per call on ALARM, grids of 4 / 16 / 256 waves
-    // measured alike; FBN_JT_FIX_GRID: tuning)
-    static const int fix_grid = getenv("FBN_JT_FIX_GRID") ? std::max(1, atoi(getenv("FBN_JT_FIX_GRID"))) : 0;
-    int grid = (int)std::min<int64_t>(nblk, flags ? (int64_t)(fix_grid > 0 ? fix_grid : p->num_cu) : (int64_t)p->num_cu * wpc);
+    // measured alike)
+    int grid = (int)std::min<int64_t>(nblk, flags ? (int64_t)p->num_cu : (int64_t)p->num_cu * wpc);
     const int64_t store_off = 0, den_off = l.store_entries, sep_off = den_off + nc, spill_off = sep_off + l.sep_entries;
     const int64_t wave_entries = spill_off + (spill ? l.max_table - cap : 0);
     if (flags)  // fixup mode: at most ~2 GiB of workspace (large trees need ~100 MB per wave)
@@ -554,19 +553,20 @@ static int JtRunDevice(fbn_jt_plan *p, const int8_t *d_evidence, int64_t ncases,
         if ((rc = p->ws.ensure(ws_d + (size_t)grid * per_blk_i))) return rc;
         if ((rc = p->flags.ensure((size_t)nblk * 4))) return rc;
         if (p->ktiming) FBN_HIP(hipEventRecord(p->ev0, s));
+        const char *vdebug_env = fbn::KnobValue("FBN_JT_VDEBUG");
+        const int vdebug = vdebug_env ? atoi(vdebug_env) : 0;
         hipError_t e = fbn_jt_virt_launch(p->vcl.as<JtVClique>(), p->vaux.as<int32_t>(), p->viv.as<double>(),
                                           p->vdig.as<uint64_t>(), p->vorder.as<int32_t>(), p->vsched.as<int32_t>(),
                                           p->vsel.as<int32_t>(), d_evidence, marg, labels, p->ws.as<double>(),
                                           reinterpret_cast<int32_t *>(p->ws.as<char>() + ws_d), p->flags.as<int>(),
                                           ncases, v.store_rows, v.scratch_row, v.scratch_rows, nc, V, SD, grid,
                                           // diagnostic ablation only (tools/): skip pass types, wrong results
-                                          (getenv("FBN_JT_VDEBUG") ? atoi(getenv("FBN_JT_VDEBUG")) : 0) |
-                                              (JtFast(p) ? kJtVFast : 0),
+                                          vdebug | (JtFast(p) ? kJtVFast : 0),
                                           s);
         if (e != hipSuccess) return SetError(FBN_ERR_HIP, "jt kernel launch: %s", hipGetErrorString(e));
         if (p->force_fixup) FBN_HIP(hipMemsetAsync(p->flags.p, 1, (size_t)nblk * 4, s));  // testing only
         // exact recomputation of the blocks whose denominators left the fast-division range
-        if (!getenv("FBN_JT_VDEBUG") &&
+        if (!vdebug_env &&
             (rc = LaunchLds(p, p->ws_fix, d_evidence, ncases, labels, marg, p->flags.as<int>(), false, s)))
             return rc;
     } else if (variant == 5) {
@@ -600,9 +600,7 @@ static int JtRunDevice(fbn_jt_plan *p, const int8_t *d_evidence, int64_t ncases,
         if (e != hipSuccess) return SetError(FBN_ERR_HIP, "jt kernel launch: %s", hipGetErrorString(e));
         if (p->force_fixup) FBN_HIP(hipMemsetAsync(p->flags.p, 1, (size_t)nblk * 4, s));  // testing only
         // exact recomputation of the blocks holding a case group whose pass totals left the checked range
-        // (FBN_JT_NO_FIXUP: diagnostic only -- flagged blocks keep the tiled kernel's values)
-        static const bool no_fix = getenv("FBN_JT_NO_FIXUP") != nullptr;
-        if (!no_fix && (rc = LaunchLds(p, p->ws_fix, d_evidence, ncases, labels, marg, p->flags.as<int>(), false, s)))
+        if ((rc = LaunchLds(p, p->ws_fix, d_evidence, ncases, labels, marg, p->flags.as<int>(), false, s)))
             return rc;
     } else if (variant == 3) {
         // one wave (64 cases) per SIMD: the clique in flight occupies the register file (+ LDS tail)
@@ -631,9 +629,7 @@ static int JtRunDevice(fbn_jt_plan *p, const int8_t *d_evidence, int64_t ncases,
         FBN_HIP(hipModuleLaunchKernel(gk.fn, grid, 1, 1, 64, 1, 1, (unsigned)gk.lds, s, args, nullptr));
         if (p->force_fixup) FBN_HIP(hipMemsetAsync(p->flags.p, 1, (size_t)nblk * 4, s));  // testing only
         // exact recomputation of the blocks whose denominators left the fast-division range
-        // (FBN_JT_NO_FIXUP: diagnostic only, as above)
-        static const bool no_fix3 = getenv("FBN_JT_NO_FIXUP") != nullptr;
-        if (!no_fix3 && (rc = LaunchLds(p, p->ws_fix, d_evidence, ncases, labels, marg, p->flags.as<int>(), false, s, vm_direct)))
+        if ((rc = LaunchLds(p, p->ws_fix, d_evidence, ncases, labels, marg, p->flags.as<int>(), false, s, vm_direct)))
             return rc;
     } else {
         if (p->ktiming) FBN_HIP(hipEventRecord(p->ev0, s));

@@ -24,21 +24,6 @@
 
 using fbn::SetError;
 
-namespace fbn {
-
-// Wait for a PC round's event: hipEventSynchronize, or with FBN_CI_SPIN = 1 by polling it from
-// this thread (measured on ALARM-5000 / config 5: no faster than HIP's own wait, so off)
-static hipError_t EventWaitSpin(hipEvent_t ev) {
-    static const bool spin = EnvOr0("FBN_CI_SPIN", 0) != 0;
-    if (!spin) return hipEventSynchronize(ev);
-    hipError_t e;
-    while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
-    }
-    return e;
-}
-
-}  // namespace fbn
-
 extern "C" {
 
 // ------------------------------------------------------------------ PC-stable
@@ -47,7 +32,7 @@ int fbn_pc_stable(fbn_ci_ctx *c, double alpha, int depth, int group_size, fbn_pc
     auto r = std::unique_ptr<fbn_pc_result>(new (std::nothrow) fbn_pc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
     FBN_HIP(hipSetDevice(c->device));
-    static const bool timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool timing = fbn::PcTiming();  // diagnostic
     auto t0 = std::chrono::steady_clock::now();
     int rc;
     // the device-resident search (small graphs) sets the ctx's margin log itself (and resets it when
@@ -269,7 +254,6 @@ const int32_t *CiCtxDims(const fbn_ci_ctx *c) { return c->dims.data(); }
 void CiSetPairMode(fbn_ci_ctx *c, int mode) {
     c->pair_mode = mode;
     if (mode == 1) c->l1mi_covered = 0;  // a new level 0 records from pair 0
-    c->triples_ready = false;
     if (mode != 2) c->pairs_recorded = false;
 }
 int CiBatchLaunch(fbn_ci_ctx *c, int k, const int32_t *items, int64_t n, int d, double alpha, bool want_df,
@@ -290,7 +274,7 @@ int CiBatchLaunch(fbn_ci_ctx *c, int k, const int32_t *items, int64_t n, int d, 
     // small rounds (the latency-bound ones): the kernel reads the items from and writes the
     // decisions to the pinned buffers directly (one launch + one sync per round); large rounds
     // stage through device memory with DMA copies
-    S.zc = ib <= kZeroCopyBytes && !getenv("FBN_CI_NO_ZEROCOPY");
+    S.zc = ib <= kZeroCopyBytes && !fbn::KnobSet("FBN_CI_NO_ZEROCOPY");
     if (S.zc) {
         rc = CiLaunchDevice(c, hi, n, d, alpha, false, nullptr, c->stream, k, hi, h_ind, want_df ? h_df : nullptr, pre);
         if (rc) return rc;
@@ -304,7 +288,7 @@ int CiBatchLaunch(fbn_ci_ctx *c, int k, const int32_t *items, int64_t n, int d, 
     return FBN_OK;
 }
 bool CiAllPairsEligible(const fbn_ci_ctx *c, const CiBatchStats &st) {
-    return st.maxdim <= 4 && !getenv("FBN_CI_NO_BITS") && (c->N >= 4096 || getenv("FBN_CI_FORCE_BITS"));
+    return st.maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_BITS") && (c->N >= 4096 || fbn::KnobSet("FBN_CI_FORCE_BITS"));
 }
 int CiBatchLaunchAllPairs(fbn_ci_ctx *c, double alpha, const CiBatchStats *pre, int64_t t0, int64_t n,
                           bool copy_flags) {
@@ -329,11 +313,11 @@ bool CiPairsReady(const fbn_ci_ctx *c) { return c->pair_mode == 2 && c->pairs_re
 // here when the dataset qualifies for it (the same test as CiLaunchDevice's bits path): a fresh ctx
 // -- every one-shot CLI run -- takes the device path from its first PC run on.
 bool CiL0L1DeviceEligible(fbn_ci_ctx *c, int group_size) {
-    if (group_size != 1 || getenv("FBN_PC_HOST_L1") || getenv("FBN_PC_HOST_L0L1") || c->nvars < 2) return false;
+    if (group_size != 1 || fbn::KnobSet("FBN_PC_HOST_L1") || fbn::KnobSet("FBN_PC_HOST_L0L1") || c->nvars < 2) return false;
     for (int v = 0; v < c->nvars; ++v)
         if (c->dims[v] > 4) return false;
     if (!c->bits_ready) {
-        const bool bits_path = !getenv("FBN_CI_NO_BITS") && (c->N >= 4096 || getenv("FBN_CI_FORCE_BITS"));
+        const bool bits_path = !fbn::KnobSet("FBN_CI_NO_BITS") && (c->N >= 4096 || fbn::KnobSet("FBN_CI_FORCE_BITS"));
         if (!bits_path || CiBitsEnsure(c, c->stream) != FBN_OK) return false;
     }
     return true;
@@ -369,7 +353,7 @@ int CiL0L1Device(fbn_ci_ctx *c, int64_t P, int *E, int64_t *cands, PCResultHost 
     long long *hk = reinterpret_cast<long long *>(c->h_kept);
     FBN_HIP(hipMemcpyAsync(hk, c->kscal.p, 16, hipMemcpyDeviceToHost, s));
     FBN_HIP(hipEventRecord(c->main_ev, s));
-    FBN_HIP(EventWaitSpin(c->main_ev));
+    FBN_HIP(hipEventSynchronize(c->main_ev));
     *E = (int)hk[0];
     *cands = hk[1];
     // the edge list to the host on the side stream (the CSR kernels are done: main_ev)
@@ -388,7 +372,7 @@ int CiL0L1Device(fbn_ci_ctx *c, int64_t P, int *E, int64_t *cands, PCResultHost 
 
 int CiL0L1Host(fbn_ci_ctx *c, int64_t P, int E, std::vector<char> &removed, std::vector<std::pair<int, int>> &edges,
                std::vector<std::vector<int>> &adj) {
-    FBN_HIP(EventWaitSpin(c->side_ev));
+    FBN_HIP(hipEventSynchronize(c->side_ev));
     removed.resize((size_t)P);
     memcpy(removed.data(), c->slot[0].h_res, (size_t)P);
     static_assert(sizeof(std::pair<int, int>) == 8, "pair layout");
@@ -448,7 +432,7 @@ int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<in
                    const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, LevelOut &out,
                    PCResultHost &res, bool *done) {
     *done = false;
-    if (c->pair_mode != 2 || !c->pairs_recorded || !c->bits_ready || getenv("FBN_PC_HOST_L1")) return FBN_OK;
+    if (c->pair_mode != 2 || !c->pairs_recorded || !c->bits_ready || fbn::KnobSet("FBN_PC_HOST_L1")) return FBN_OK;
     const int nv = c->nvars;
     for (int v = 0; v < nv; ++v)
         if (c->dims[v] > 4) return FBN_OK;
@@ -457,13 +441,13 @@ int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<in
     for (size_t e = e_begin; e < e_end; ++e) cands += adj[edges[e].first].size() + adj[edges[e].second].size() - 2;
     // a level the host driver takes in one round (full speculation, ALARM-size) stays there: one
     // launch instead of a round's seven
-    if (cands <= EnvOr0("FBN_PC_FULLSPEC", 16384)) return FBN_OK;
+    if (cands <= fbn::KnobOr("FBN_PC_FULLSPEC", 16384)) return FBN_OK;
     if (E == 0) {
         out.removed.clear(), out.sep.clear(), out.d = 1, out.counted = out.launched = 0;
         *done = true;
         return FBN_OK;
     }
-    static const bool ptiming = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool ptiming = fbn::PcTiming();  // diagnostic
     auto tq0 = std::chrono::steady_clock::now();
     FBN_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -503,7 +487,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     FBN_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     int rc;
-    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(cands, EnvOr0("FBN_PC_L1CAP", 1 << 19)));
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(cands, fbn::KnobOr("FBN_PC_L1CAP", 1 << 19)));
     if ((rc = c->l1ed.ensure((size_t)E * fbn_ci_l1_edge_bytes())) ||
         (rc = c->l1pos.ensure((size_t)E * 4)) || (rc = c->l1st.ensure((size_t)E)) ||
         (rc = c->l1sep.ensure((size_t)E * 4)) || (rc = c->l1cnt.ensure((size_t)E * 8)) ||
@@ -529,7 +513,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     // decision threshold per df) and the level-0 pair tables of the complete graph
     double *mi = nullptr;
     const bool mi_from_tables = c->l1mi_covered != (int64_t)nv * (nv - 1) / 2;
-    if (band && !getenv("FBN_PC_NO_MISCREEN")) {
+    if (band && !fbn::KnobSet("FBN_PC_NO_MISCREEN")) {
         const long long P = (long long)nv * (nv - 1) / 2;
         if ((rc = c->l1mi.ensure((size_t)std::max<long long>(P, 1) * 8)) ||
             (rc = c->l1plist.ensure((size_t)std::max<int64_t>(cands, 1) * 4)) ||
@@ -541,13 +525,13 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     CiSlot &S = c->slot[0];
     if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
     long long *scal = c->l1scal.as<long long>();  // total, launched, rows read, scan flag, tickets
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(32, EnvOr0("FBN_PC_ROUND0", 8192) / E));
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(32, fbn::KnobOr("FBN_PC_ROUND0", 8192) / E));
     // chunk x2 per round: rounds here cost a few launches, speculation costs counted tests (config 5:
     // x4 launches 430k tests for 294k counted, x2 345k)
-    const int64_t growth = std::max<int64_t>(2, EnvOr0("FBN_PC_GROWTH", 2));
+    const int64_t growth = std::max<int64_t>(2, fbn::KnobOr("FBN_PC_GROWTH", 2));
     // (FBN_PC_L1_MAXCHUNK: tuning -- a cap on the per-edge chunk trades speculative tests for rounds)
     const int64_t max_chunk = std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>(1 << 16, EnvOr0("FBN_PC_L1_MAXCHUNK", 1 << 16)), (int64_t)INT32_MAX / E));
+        1, std::min<int64_t>(std::min<int64_t>(1 << 16, fbn::KnobOr("FBN_PC_L1_MAXCHUNK", 1 << 16)), (int64_t)INT32_MAX / E));
     chunk = std::min(chunk, max_chunk);
     // the setup writes round 0's lengths and zeroes the open-count ring; each round's resolve writes
     // the next round's lengths and zeroes the other ring slot (no length kernel or memset per round)
@@ -560,7 +544,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
                                    2.0 * (double)c->N, c->l1pcnt.as<int32_t>(), c->l1plist.as<int32_t>(),
                                    c->l1sstat2.as<unsigned long long>(), scal + 8, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci level-1 setup: %s", hipGetErrorString(e));
-    static const bool l1timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool l1timing = fbn::PcTiming();  // diagnostic
     const auto tl0 = std::chrono::steady_clock::now();
     int rounds = 0;
     for (int r = 0;; ++r) {
@@ -581,7 +565,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
         if (r == 0 && host_work)  // (while the first round runs)
             if ((rc = host_work())) return rc;
         if (r >= 1) {  // round r - 1's open count, while round r runs
-            FBN_HIP(EventWaitSpin(c->l1ev[(r - 1) & 1]));
+            FBN_HIP(hipEventSynchronize(c->l1ev[(r - 1) & 1]));
             if (c->h_open[(r - 1) & 1] == 0) break;  // round r found nothing to do
         }
         chunk = next_chunk;
@@ -618,82 +602,6 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     return FBN_OK;
 }
 
-// per-variable masked Grams of a PC run's level 1: for every endpoint u of the edges [e_begin,
-// e_end), G_u[a] = popcount(u_a & r_i & r_j) over u's neighbours' leading rows (upper 8 x 8 tiles),
-// enqueued on the ctx stream ahead of the level's batches; their tests then gather the leading
-// cells instead of counting (ci_bits_gram_triples).  Only with recorded pair tables (the rest of
-// each table is derived from them) and the bit-sliced store; skipped when the Grams exceed the
-// budget.
-constexpr int64_t kGram1MaxBytes = (int64_t)1 << 30;
-int CiTriplePrepare(fbn_ci_ctx *c, const std::vector<std::vector<int>> &adj,
-                    const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, bool *ready) {
-    *ready = c->triples_ready = false;
-    if (c->pair_mode != 2 || !c->pairs_recorded || !c->bits_ready || getenv("FBN_CI_NO_GRAM")) return FBN_OK;
-    const int nv = c->nvars;
-    for (int v = 0; v < nv; ++v)
-        if (c->dims[v] > 4) return FBN_OK;
-    FBN_HIP(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc;
-    if ((rc = CiLeadEnsure(c, s))) return rc;
-    std::vector<char> need(nv, 0);
-    for (size_t e = e_begin; e < e_end; ++e) need[edges[e].first] = need[edges[e].second] = 1;
-    std::vector<int32_t> adjf, adj_off(nv + 1, 0), loff, R(nv, 0), rl;
-    std::vector<long long> goff(nv, 0);
-    long long gtot = 0;
-    for (int u = 0; u < nv; ++u) {
-        adj_off[u] = (int32_t)adjf.size();
-        int r = 0;
-        for (int v : adj[u]) adjf.push_back(v), loff.push_back(r), r += c->dims[v] - 1;
-        R[u] = r;
-        goff[u] = gtot;
-        if (need[u] && adj[u].size() >= 2) gtot += (long long)(c->dims[u] - 1) * r * r;
-    }
-    adj_off[nv] = (int32_t)adjf.size();
-    if (gtot * 4 > kGram1MaxBytes) return FBN_OK;
-    const int TI = fbn_ci_gram_task_ints();
-    std::vector<int32_t> tasks;
-    for (int u = 0; u < nv; ++u) {
-        if (!need[u] || adj[u].size() < 2 || c->dims[u] < 2 || R[u] == 0) continue;
-        const int64_t base = (int64_t)rl.size(), Ru = R[u], nb = (Ru + 7) / 8;
-        for (int v : adj[u])
-            for (int a = 0; a + 1 < c->dims[v]; ++a) rl.push_back(c->row0_host[v] + a);
-        for (int a = 0; a + 1 < c->dims[u]; ++a)
-            for (int64_t bi = 0; bi < nb; ++bi)
-                for (int64_t bj = bi; bj < nb; ++bj) {
-                    const int64_t off = goff[u] + (a * Ru + 8 * bi) * Ru + 8 * bj;
-                    const int32_t t[8] = {c->row0_host[u] + a, (int32_t)(base + 8 * bi),
-                                          (int32_t)std::min<int64_t>(8, Ru - 8 * bi), (int32_t)(base + 8 * bj),
-                                          (int32_t)std::min<int64_t>(8, Ru - 8 * bj),
-                                          (int32_t)(uint32_t)(off & 0xffffffff), (int32_t)(off >> 32), (int32_t)Ru};
-                    tasks.insert(tasks.end(), t, t + TI);
-                }
-    }
-    if ((rc = c->g1.ensure(std::max<size_t>((size_t)gtot, 1) * 4))) return rc;
-    if ((rc = c->g1tasks.ensure(std::max<size_t>(tasks.size(), 1) * 4))) return rc;
-    if ((rc = c->g1rl.ensure(std::max<size_t>(rl.size(), 1) * 4))) return rc;
-    if ((rc = c->g1goff.ensure((size_t)nv * 8))) return rc;
-    if ((rc = c->g1R.ensure((size_t)nv * 4))) return rc;
-    if ((rc = c->g1adj.ensure(std::max<size_t>(adjf.size(), 1) * 4))) return rc;
-    if ((rc = c->g1adjoff.ensure((size_t)(nv + 1) * 4))) return rc;
-    if ((rc = c->g1loff.ensure(std::max<size_t>(loff.size(), 1) * 4))) return rc;
-    auto up = [&](DevBuf &b, const void *h, size_t bytes) -> int {
-        if (bytes) FBN_HIP(hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, s));
-        return FBN_OK;
-    };
-    if ((rc = up(c->g1tasks, tasks.data(), tasks.size() * 4)) || (rc = up(c->g1rl, rl.data(), rl.size() * 4)) ||
-        (rc = up(c->g1goff, goff.data(), (size_t)nv * 8)) || (rc = up(c->g1R, R.data(), (size_t)nv * 4)) ||
-        (rc = up(c->g1adj, adjf.data(), adjf.size() * 4)) ||
-        (rc = up(c->g1adjoff, adj_off.data(), (size_t)(nv + 1) * 4)) ||
-        (rc = up(c->g1loff, loff.data(), loff.size() * 4)))
-        return rc;
-    hipError_t e = fbn_ci_gram(c->bits.as<uint32_t>(), c->bits_W, c->g1rl.as<int32_t>(), c->g1tasks.as<int32_t>(),
-                               (long long)(tasks.size() / TI), 1, c->g1.as<int32_t>(), c->num_cu, s);
-    if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci gram level 1: %s", hipGetErrorString(e));
-    FBN_HIP(hipStreamSynchronize(s));  // the host vectors go out of scope
-    *ready = c->triples_ready = true;
-    return FBN_OK;
-}
 struct FlagIsZero {
     __host__ __device__ bool operator()(uint8_t f) const { return f == 0; }
 };
@@ -743,9 +651,9 @@ int CiBatchWait(fbn_ci_ctx *c, int k, uint8_t *indep, int32_t *df, PCResultHost 
     CiSlot &S = c->slot[k];
     const int64_t n = S.n;
     if (n == 0) return FBN_OK;
-    static const bool timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool timing = fbn::PcTiming();  // diagnostic
     auto t1 = std::chrono::steady_clock::now();
-    FBN_HIP(EventWaitSpin(S.done));
+    FBN_HIP(hipEventSynchronize(S.done));
     auto t2 = std::chrono::steady_clock::now();
     const uint8_t *h_ind = static_cast<const uint8_t *>(S.h_res);
     memcpy(indep, h_ind, (size_t)n);
@@ -770,7 +678,7 @@ int CiRunBatch(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double alp
 // the device-resident search's domain: <= 64 variables of <= 4 states, group size 1.  N cap: one
 // test's samples bound the workgroups' skew at a grid barrier (its spin limit is 2 s)
 bool PCSmallShape(int nvars, int64_t N, const int32_t *dims, int group_size) {
-    if (group_size != 1 || nvars < 2 || nvars > kSmallMaxVars || N < 1 || N > (1ll << 24) || getenv("FBN_PC_NO_SMALL"))
+    if (group_size != 1 || nvars < 2 || nvars > kSmallMaxVars || N < 1 || N > (1ll << 24) || fbn::KnobSet("FBN_PC_NO_SMALL"))
         return false;
     for (int v = 0; v < nvars; ++v)
         if (dims[v] < 1 || dims[v] > 4) return false;
@@ -785,7 +693,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
     *levels = 0;
     *handoff = false;
     *fellback = false;
-    static const bool htime = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic: host phases of the call
+    const bool htime = fbn::PcTiming();  // diagnostic: host phases of the call
     const auto h0 = std::chrono::steady_clock::now();
     FBN_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -798,7 +706,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
     // zeroed again before the next launch, and the margin log starts over for the host levels
     auto fall_back = [&](const char *why) {
         c->small_zeroed = nullptr;
-        const bool quiet = getenv("FBN_PC_SMALL_FAIL") != nullptr;  // (the test knob expects it)
+        const bool quiet = fbn::KnobSet("FBN_PC_SMALL_FAIL");  // (the test knob expects it)
         if (!quiet) fprintf(stderr, "fastbn: device-resident PC search %s; host-driven levels instead\n", why);
         *fellback = true;
         return CiResetMargin(c);
@@ -846,8 +754,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
     a.band = band;
     a.nband = nband;
     a.depth = depth;
-    static const int spec_a = getenv("FBN_PC_SPEC_A") ? std::max(1, atoi(getenv("FBN_PC_SPEC_A"))) : 8;  // (tuning)
-    a.spec_a = spec_a;
+    a.spec_a = 8;
     a.bar = reinterpret_cast<unsigned *>(scr);
     a.first = reinterpret_cast<unsigned long long *>(scr + (size_t)kSmallBarWords * 4);
     a.epoch = c->small_epoch;
@@ -855,11 +762,11 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
     a.acc = reinterpret_cast<unsigned long long *>(scr + acc_off);
     a.pairtab = reinterpret_cast<int32_t *>(scr + pt_off);
     // the level-1 information screen (exact, see ci_bits.hip; FBN_PC_NO_MISCREEN=1: off)
-    a.pg2 = band && !getenv("FBN_PC_NO_MISCREEN") ? reinterpret_cast<unsigned long long *>(scr + pg_off) : nullptr;
+    a.pg2 = band && !fbn::KnobSet("FBN_PC_NO_MISCREEN") ? reinterpret_cast<unsigned long long *>(scr + pg_off) : nullptr;
     a.ctx_stats = c->stats.as<unsigned long long>();
     a.dout = reinterpret_cast<PcSmallOut *>(scr + dout_off);
     a.out = out;
-    static const bool trace = getenv("FBN_PC_SMALL_TRACE") != nullptr;  // diagnostic
+    static const bool trace = fbn::KnobSet("FBN_PC_SMALL_TRACE");  // diagnostic
     std::vector<unsigned long long> trace_host;
     unsigned long long *h_trace = nullptr;
     DevBuf trace_dev;
@@ -875,12 +782,12 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
     if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
     // FBN_PC_SMALL_FAIL (test knob): "launch" = treat the launch as refused, "timeout" = a barrier
     // limit of one tick, so the first level's barrier times out in the kernel itself
-    const char *force = getenv("FBN_PC_SMALL_FAIL");  // (read per call: tests set it)
+    const char *force = fbn::KnobValue("FBN_PC_SMALL_FAIL");  // (read per call: tests set it)
     // launch: plain by default -- the grid (one workgroup per CU, occupancy checked above) is resident
     // unless other work holds CUs, and then a barrier times out (bounded spin) and the host driver
     // takes over; hipLaunchCooperativeKernel (FBN_PC_SMALL_COOP=1, read per call) refuses such a grid
     // up front but measured 12-15 us more kernel time per call (0.140 vs 0.126 ms on ALARM-5000)
-    const char *coop_env = getenv("FBN_PC_SMALL_COOP");
+    const char *coop_env = fbn::KnobValue("FBN_PC_SMALL_COOP");
     const bool plain = !(coop_env && atoi(coop_env) != 0);
     const bool force_launch = force && !strcmp(force, "launch");
     const long long spin = (force && !strcmp(force, "timeout")) ? 1 : 0;

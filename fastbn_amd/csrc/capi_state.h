@@ -124,10 +124,6 @@ struct fbn_ci_ctx {
     // pair range [g0_t0, g0_t1)
     DevBuf gram0, g0tasks;
     int64_t g0_t0 = -1, g0_t1 = -1, g0_ntasks = 0;
-    // level 1: per-variable masked Grams over the neighbours' leading rows (CiTriplePrepare), used
-    // by the next d = 1 batches while triples_ready
-    DevBuf g1, g1tasks, g1rl, g1goff, g1R, g1adj, g1adjoff, g1loff;
-    bool triples_ready = false;
     // device-resident level-1 search (CiLevel1Device): edge state, round buffers, per-round open
     // counts (pinned mirror), round events
     DevBuf l1pairs, l1adj, l1adjoff, l1ed, l1pos, l1st, l1sep, l1cnt, l1len, l1off, l1scal, l1open;

@@ -544,12 +544,11 @@ __global__ __launch_bounds__(256) void ci_bits_count_derived(const uint32_t *__r
 
 
 
-// ---- row Gram matrices (levels 0 and 1 of a PC run on the bit-sliced store)
+// ---- row Gram matrix (level 0 of a PC run on the bit-sliced store)
 // A PC run's level 0 needs popcount(r_i & r_j) for every pair of leading mask rows (values 0..d-2
-// of every variable; the last value is derived), and level 1 needs popcount(x_a & r_i & r_j) for
-// the rows of every pair of x's neighbours: both are Gram matrices of mask rows over the sample
-// bits.  One wave per task = an 8 x 8 tile of (i, j) row pairs (optionally every row ANDed with a
-// mask row x_a): per 4-word step 16 (17) 16-byte loads feed 256 popcounts, counters in registers,
+// of every variable; the last value is derived): a Gram matrix of mask rows over the sample bits.
+// One wave per task = an 8 x 8 tile of (i, j) row pairs (MASKED, not instantiated: every row ANDed
+// with a mask row x_a): per 4-word step 16 (17) 16-byte loads feed 256 popcounts, counters in registers,
 // then a butterfly reduction that leaves counter l's wave total in lane l (63 shuffles instead of
 // 64 x 6).  Tasks are built on the host (capi_ci.hip CiGram*): one block of one wave per task so the
 // task fields and row pointers are wave-uniform (scalar registers).
@@ -679,87 +678,6 @@ __device__ __forceinline__ int find_sorted(const int32_t *__restrict__ a, int n,
         else hi = mid;
     }
     return lo < n && a[lo] == v ? lo : -1;
-}
-
-// level 1 from the per-variable masked Grams: item (x, y, z) reads its (dx-1)(dy-1)(dz-1) leading
-// cells popcount(x_a & y_b & z_c) from G_u, u = x if z is x's neighbour, else y (then x and z are
-// y's neighbours); G_u[a] is R_u x R_u over u's neighbours' leading rows (upper tiles only: the
-// entry is read as (row of the earlier neighbour, row of the later one)).  The rest of the table
-// is derived from the pair tables exactly as count_test_derived; every value is an integer.
-__global__ __launch_bounds__(256) void ci_bits_gram_triples(
-    const int32_t *__restrict__ G, const long long *__restrict__ goff, const int32_t *__restrict__ gR,
-    const int32_t *__restrict__ adj, const int32_t *__restrict__ adj_off, const int32_t *__restrict__ loff,
-    const int32_t *__restrict__ dims, const int32_t *__restrict__ items, long long n, int32_t *__restrict__ counts,
-    const int32_t *__restrict__ pairtab, int nvars) {
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
-        const int x = items[3 * t], y = items[3 * t + 1], z = items[3 * t + 2];
-        const int DX = dims[x], DY = dims[y], DZ = dims[z], MX = DX - 1, MY = DY - 1, MZ = DZ - 1;
-        int pzx = find_sorted(adj + adj_off[x], adj_off[x + 1] - adj_off[x], z);
-        const bool ux = pzx >= 0;
-        const int u = ux ? x : y, o = ux ? y : x;
-        const int32_t *au = adj + adj_off[u];
-        const int nu = adj_off[u + 1] - adj_off[u];
-        const int po = find_sorted(au, nu, o), pz = ux ? pzx : find_sorted(au, nu, z);
-        if (po < 0 || pz < 0) continue;  // not a level-1 item of this skeleton (never generated)
-        const int32_t *lu = loff + adj_off[u];
-        const int Ru = gR[u], ro = lu[po], rz = lu[pz];
-        const bool oz = po < pz;
-        const int32_t *Gu = G + goff[u];
-        // leading cells cnt[c][a][b] (a: value of x, b: value of y, c: value of z)
-        int32_t cnt[3][3][3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = 0; b < 3; ++b) {
-                    int32_t v = 0;
-                    if (c < MZ && a < MX && b < MY) {
-                        const int ua = ux ? a : b, ob = ux ? b : a;  // u's value, the other's value
-                        const long long ri = ro + ob, rj = rz + c;
-                        v = Gu[((long long)ua * Ru + (oz ? ri : rj)) * Ru + (oz ? rj : ri)];
-                    }
-                    cnt[c][a][b] = v;
-                }
-        const int32_t *Txy = pair_table(pairtab, nvars, x, y), *Txz = pair_table(pairtab, nvars, x, z),
-                      *Tyz = pair_table(pairtab, nvars, y, z);
-        const bool txy = x > y, txz = x > z, tyz = y > z;
-        auto nxy = [&](int a, int b) { return txy ? Txy[b * DX + a] : Txy[a * DY + b]; };
-        auto nxz = [&](int a, int c) { return txz ? Txz[c * DX + a] : Txz[a * DZ + c]; };
-        auto nyz = [&](int b, int c) { return tyz ? Tyz[c * DY + b] : Tyz[b * DZ + c]; };
-        // N[c][a][b] for c < MZ: leading cells, then the last y value, then the last x value
-        auto fz = [&](int c, int a, int b) {
-            auto row_last = [&](int aa) {  // N[c][aa][MY], aa < MX
-                int32_t r = nxz(aa, c);
-#pragma unroll
-                for (int bb = 0; bb < 3; ++bb)
-                    if (bb < MY) r -= cnt[c][aa][bb];
-                return r;
-            };
-            if (a < MX) return b < MY ? cnt[c][a][b] : row_last(a);
-            int32_t r = nyz(b, c);
-#pragma unroll
-            for (int aa = 0; aa < 3; ++aa)
-                if (aa < MX) r -= b < MY ? cnt[c][aa][b] : row_last(aa);
-            return r;
-        };
-        int32_t *out = counts + t * kBitsCells;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (a >= DX || b >= DY) continue;
-                int32_t last = nxy(a, b);
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    if (c < MZ) {
-                        const int32_t v = fz(c, a, b);
-                        out[(c * DX + a) * DY + b] = v;
-                        last -= v;
-                    }
-                out[(MZ * DX + a) * DY + b] = last;
-            }
-    }
 }
 
 // phase 2, large launches (ci_bits_g2): one lane per test -- per z: marginals, adjusted df; G^2 as one running sum in the
@@ -1651,11 +1569,9 @@ extern "C" hipError_t fbn_ci_l1_round(const uint32_t *bits, const int32_t *dims,
                        counts, pairtab, nvars, 1, total);
     // four lanes per test: the screened rounds are small (a few thousand to ~27k tests on config 5),
     // where the lane-per-test kernel's single latency chain per test dominated (config 5: 0.22 ->
-    // 0.13 ms of G^2 per run; FBN_PC_L1_G2Q=0: lane per test)
-    static const bool quad = !(getenv("FBN_PC_L1_G2Q") && atoi(getenv("FBN_PC_L1_G2Q")) == 0);
+    // 0.13 ms of G^2 per run)
     const long long gq = (cap + kG2TestsPerBlock - 1) / kG2TestsPerBlock;
-    hipLaunchKernelGGL((quad ? ci_bits_g2q<1> : ci_bits_g2<1>), quad ? dim3((unsigned)(gq < gcap ? gq : gcap)) : gT,
-                       dim3(256), 0, s, (const int32_t *)counts, dims, (const int32_t *)items, cap, alpha,
+    hipLaunchKernelGGL(ci_bits_g2q<1>, dim3((unsigned)(gq < gcap ? gq : gcap)), dim3(256), 0, s, (const int32_t *)counts, dims, (const int32_t *)items, cap, alpha,
                        (double *)nullptr, df, (double *)nullptr, indep, (int32_t *)nullptr, stats, nvars, 0ll, band,
                        nband, total);
     hipLaunchKernelGGL(ci_l1_resolve, dim3((unsigned)std::min(ntiles, num_cu * 4)), dim3(256), 0, s, ed, pos, len,
@@ -1667,13 +1583,11 @@ extern "C" hipError_t fbn_ci_l1_round(const uint32_t *bits, const int32_t *dims,
 extern "C" int fbn_ci_gram_task_ints(void) { return kGramTaskInts; }
 
 extern "C" hipError_t fbn_ci_gram(const uint32_t *bits, long long W, const int32_t *rl, const int32_t *tasks,
-                                  long long ntasks, int masked, int32_t *out, int num_cu, hipStream_t s) {
+                                  long long ntasks, int32_t *out, int num_cu, hipStream_t s) {
     const long long cap = (long long)num_cu * 32;
     const dim3 g((unsigned)(ntasks < cap ? ntasks : cap));
     if (ntasks <= 0) return hipSuccess;
-    static const int xcd = getenv("FBN_CI_GRAM_XCD") ? atoi(getenv("FBN_CI_GRAM_XCD")) : 1;
-    if (masked) hipLaunchKernelGGL(ci_bits_gram<true>, g, dim3(64), 0, s, bits, W, rl, tasks, ntasks, out, xcd);
-    else hipLaunchKernelGGL(ci_bits_gram<false>, g, dim3(64), 0, s, bits, W, rl, tasks, ntasks, out, xcd);
+    hipLaunchKernelGGL(ci_bits_gram<false>, g, dim3(64), 0, s, bits, W, rl, tasks, ntasks, out, /*xcd*/ 1);
     return hipGetLastError();
 }
 
@@ -1684,17 +1598,6 @@ extern "C" hipError_t fbn_ci_gram_pairs(const int32_t *G, long long ld, const in
     if (n > 0)
         hipLaunchKernelGGL(ci_bits_gram_pairs, dim3((unsigned)(g < cap ? g : cap)), dim3(256), 0, s, G, ld, lead0,
                            dims, row0, rowcnt, t0, n, nvars, counts, pairtab);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fbn_ci_gram_triples(const int32_t *G, const long long *goff, const int32_t *gR,
-                                          const int32_t *adj, const int32_t *adj_off, const int32_t *loff,
-                                          const int32_t *dims, const int32_t *items, long long n, int32_t *counts,
-                                          const int32_t *pairtab, int nvars, int num_cu, hipStream_t s) {
-    const long long g = (n + 255) / 256, cap = (long long)num_cu * 8;
-    if (n > 0)
-        hipLaunchKernelGGL(ci_bits_gram_triples, dim3((unsigned)(g < cap ? g : cap)), dim3(256), 0, s, G, goff, gR,
-                           adj, adj_off, loff, dims, items, n, counts, pairtab, nvars);
     return hipGetLastError();
 }
 
@@ -1717,14 +1620,9 @@ extern "C" hipError_t fbn_ci_bits_launch(const uint32_t *bits, const int32_t *di
         hipLaunchKernelGGL((quad ? ci_bits_g2q<0> : ci_bits_g2<0>), b2, dim3(256), 0, s, counts, dims, items, n,
                            alpha, g2, df, p, indep, counts0, stats, nvars, t0, band, nband, (const long long *)nullptr);
     } else if (d == 1) {
-        // FBN_CI_L1MODE = 0: plain grid stride instead of the XCD-contiguous split
-        static const int l1mode = getenv("FBN_CI_L1MODE") ? atoi(getenv("FBN_CI_L1MODE")) : 1;
-        if (counted) {
-            // the counts are already in place (ci_bits_gram_triples)
-        } else if (pmode == 2) {
+        if (pmode == 2)  // (xcd = 1: the XCD-contiguous split of the items)
             hipLaunchKernelGGL(ci_bits_count_derived, b1, dim3(256), 0, s, bits, dims, row0, items, W, n, counts,
-                               (const int32_t *)pairtab, nvars, l1mode == 1 ? 1 : 0, (const long long *)nullptr);
-        }
+                               (const int32_t *)pairtab, nvars, 1, (const long long *)nullptr);
         else
             hipLaunchKernelGGL(ci_bits_count<1>, b1, dim3(256), 0, s, bits, dims, row0, items, W, n, counts, rowcnt,
                                nullptr, nvars, 0ll);

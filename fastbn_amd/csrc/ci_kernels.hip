@@ -29,8 +29,8 @@ constexpr int kTermChunk = 1024;
 constexpr long long kWideTests = 512;  // batches up to this size: 1024-thread workgroups
 constexpr long long kPackedLaneMax = 65520;  // packed 16-bit counters: samples per thread (see `packed`)
 constexpr int kDerivedInts = 256;      // MODE 3: the four full 3-way tables (4 x 64 ints) after the terms
-// MODE 3 / 4: the derived d = 2 counting with the register allocation unconstrained (2 waves per
-// SIMD) / allowing 3 waves per SIMD (the default; only the widest state-count instantiations spill)
+// MODE 4: the derived d = 2 counting ("MODE 3" below) with registers for 3 waves per SIMD (only the
+// widest state-count instantiations spill); MODE 3 itself, unconstrained, is not instantiated
 __host__ __device__ constexpr int der2_waves(int mode) { return mode == 4 ? 3 : 1; }
 
 // sub-histogram copies per wave for a table of `cells` > 16 cells (0: one shared table, beyond
@@ -82,7 +82,7 @@ struct CiArgs {
     // of the nvars variables, [value of u][value of v], ci_bits.hip pair_table)
     const int32_t *pairtab;
     int nvars;
-    int dbg;  // diagnostic ablations (FBN_CI_DER2_DBG): bit 0 = MODE 3 skips its counting
+    int dbg;  // diagnostic ablations, 0 from every launcher: bit 0 = MODE 3 skips its counting
 };
 
 // ---- MODE 3: tests with two conditioning variables (z1, z2), every state count <= 4, from the
@@ -792,35 +792,32 @@ extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, co
                                     hipStream_t stream) {
     CiArgs a{cols, dims, items, N, n, alpha, g2, df, p, indep, counts, gscratch, (long long)(lds_bytes / 4 + 1) & ~1ll,
              stats, bits, row0, W, band, nband, pk, PW, cstride, tab, tstride, split, pairtab, nvars,
-             getenv("FBN_CI_DER2_DBG") ? atoi(getenv("FBN_CI_DER2_DBG")) : 0};
+             /*debug word*/ 0};
     if (gscratch) lds_bytes = 0;
     if (pairtab && bits && d == 2) {  // MODE 3: derived bit-sliced counting (every state count <= 4)
-        // registers for 3 waves per SIMD (config-5 level 2: 0.47 / 0.42 / 0.49 ms at 2 / 3 / 4 waves;
-        // FBN_CI_DER2_WAVES = 2 selects the unconstrained allocation)
-        static const int w = getenv("FBN_CI_DER2_WAVES") ? atoi(getenv("FBN_CI_DER2_WAVES")) : 3;
-        if (w == 2) hipLaunchKernelGGL((ci_g2_kernel<2, true, false, 256, 3>), dim3(grid), dim3(256), lds_bytes, stream, a);
-        else hipLaunchKernelGGL((ci_g2_kernel<2, true, false, 256, 4>), dim3(grid), dim3(256), lds_bytes, stream, a);
+        // registers for 3 waves per SIMD (config-5 level 2: 0.47 / 0.42 / 0.49 ms at 2 / 3 / 4 waves)
+        hipLaunchKernelGGL((ci_g2_kernel<2, true, false, 256, 4>), dim3(grid), dim3(256), lds_bytes, stream, a);
         return hipGetLastError();
     }
     if (split > 1 && pk && !bits && !gscratch) {  // small batch: count in parts, then decide
         hipError_t e = hipMemsetAsync(tab, 0, (size_t)n * tstride * 4, stream);
         if (e != hipSuccess) return e;
         switch (d) {
-#define FBN_CI_SPLIT(DD)                                                                                      \
+#define FBN_CI_SPLIT_CASE(DD)                                                                                 \
     case DD:                                                                                                  \
         hipLaunchKernelGGL((ci_g2_kernel<DD, false, true, 256, 1>), dim3(split_grid), dim3(256), lds_bytes, stream, a); \
         hipLaunchKernelGGL((ci_g2_kernel<DD, false, true, 1024, 2>), dim3(grid), dim3(1024), lds_bytes, stream, a); \
         break;
-            FBN_CI_SPLIT(0)
-            FBN_CI_SPLIT(1)
-            FBN_CI_SPLIT(2)
-            FBN_CI_SPLIT(3)
-            FBN_CI_SPLIT(4)
-            FBN_CI_SPLIT(5)
-            FBN_CI_SPLIT(6)
-            FBN_CI_SPLIT(7)
-            FBN_CI_SPLIT(8)
-#undef FBN_CI_SPLIT
+            FBN_CI_SPLIT_CASE(0)
+            FBN_CI_SPLIT_CASE(1)
+            FBN_CI_SPLIT_CASE(2)
+            FBN_CI_SPLIT_CASE(3)
+            FBN_CI_SPLIT_CASE(4)
+            FBN_CI_SPLIT_CASE(5)
+            FBN_CI_SPLIT_CASE(6)
+            FBN_CI_SPLIT_CASE(7)
+            FBN_CI_SPLIT_CASE(8)
+#undef FBN_CI_SPLIT_CASE
         default:
             return hipErrorInvalidValue;
         }
@@ -828,9 +825,8 @@ extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, co
     }
     // batches of at most kWideTests tests (deep PC levels: a few hundred tests or fewer, one
     // workgroup per test on part of the chip): 16 waves per test instead of 4, so each test's
-    // sample loop and epilogue have 4x the waves to hide latency (FBN_CI_NO_WIDE: always 4)
-    static const bool no_wide = getenv("FBN_CI_NO_WIDE") != nullptr;
-    const bool wide = n <= kWideTests && !no_wide;
+    // sample loop and epilogue have 4x the waves to hide latency
+    const bool wide = n <= kWideTests;
     switch (d) {
 #define FBN_CI_CASE(DD)                                                                              \
     case DD:                                                                                         \

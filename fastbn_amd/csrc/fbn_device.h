@@ -79,11 +79,6 @@ inline int PinnedEnsure(void *&ptr, size_t &have, size_t want) {
     return FBN_OK;
 }
 
-inline int64_t EnvOr0(const char *name, int64_t dflt) {
-    const char *v = getenv(name);
-    return v ? atoll(v) : dflt;
-}
-
 // out-of-domain evidence has no reference meaning (a code >= the node's state count would shift
 // bits into the neighbouring digit fields of the kernels' evidence masks): checked on the device
 // before any kernel indexes with it; one stream sync (the host loop cost ~1 ns per value).

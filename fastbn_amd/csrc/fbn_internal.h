@@ -10,6 +10,7 @@
 
 #include "../../include/fastbn.h"
 #include "jt_program.h"
+#include "knobs.h"
 
 namespace fbn {
 

@@ -291,13 +291,6 @@ namespace {
 
 constexpr size_t kBlock = 64u << 20;
 
-int NumThreads() {
-    const unsigned hc = std::thread::hardware_concurrency();
-    int t = (int)std::max(1u, std::min(16u, hc ? hc : 1u));  // the GPU box's CPU share is 16
-    if (const char *e = getenv("OMP_NUM_THREADS")) t = std::max(1, std::min(t, atoi(e)));
-    return t;
-}
-
 // calls fn(lines_begin, lines_end, is_last_block) for consecutive blocks of complete lines; the
 // final unterminated line (if any) is passed as the last block's tail
 template <class F>
@@ -373,7 +366,7 @@ inline void TrimRight(const char *b, const char *&e) {
 // has extra fields (they are ignored); a row with fewer fields is an error.
 int LoadCsv(const std::string &path, Dataset &ds) {
     ds = Dataset();
-    const int T = NumThreads();
+    const int T = HostThreads();
     bool header_done = false;
     std::vector<std::vector<std::string>> gdict;     // global first-appearance dictionaries
     std::vector<std::vector<uint8_t>> colv;          // per-column codes, file order
@@ -493,7 +486,7 @@ int LoadCsv(const std::string &path, Dataset &ds) {
 // >= num_nodes are ignored (src/JunctionTree.cpp:326-331).  ev == nullptr: count the rows only;
 // otherwise the first min(rows, cap) rows are written to ev [row][num_nodes] / labels.
 int LoadLibsvm(const std::string &path, int num_nodes, int8_t *ev, int32_t *labels, int64_t cap, int64_t *nrows) {
-    const int T = NumThreads();
+    const int T = HostThreads();
     int64_t row = 0;
     int rc = ForEachBlock(path, [&](const char *b, const char *e, bool last) -> int {
         if (last) {  // drop an unterminated final line

@@ -4,7 +4,7 @@
 // straight-line code: every table entry of the clique in flight is a named fp64 register value
 // (lane = evidence case), every index map / digit / stride and every initial potential is a
 // compile-time constant; the initial potentials are read with wave-uniform scalar loads from a
-// constant buffer (or, FBN_JT_IV_LDS=1, from an LDS copy per wave).  No op dispatch, no index arrays;
+// constant buffer (iv_lds, off: from an LDS copy per wave).  No op dispatch, no index arrays;
 // LDS holds the entries of a large clique past the register-resident ones and a pool of message
 // rows (PlaceMessages).
 //
@@ -69,8 +69,6 @@ bool JTCodegenEligible(const JTPlanHost &plan, int64_t *entry_ops) {
 
 namespace {
 
-constexpr int kDefaultMerge = 1;  // FBN_JT_MERGE default (fast order; round 5 sweep: -1..3 %)
-
 class JTGen {
   public:
     JTGen(const JTPlanHost &p, bool fast_order, bool var_major) : plan(p), fast(fast_order), vmajor(var_major) {}
@@ -104,26 +102,19 @@ class JTGen {
     std::vector<int> msep;
     // fast order: the clique a variable's marginal is summed in when msep[v] < 0 (default: home[v])
     std::vector<int> mclq;
-    // FBN_JT_MARG_SRC (tuning): 0 = the smallest holder (default), 1 = the holder whose Distribute
-    // op comes last, 2 = first -- the marginal stores of neighbouring output offsets then land
-    // closer together in time (fewer partial write-backs of the case-major output lines).  ALARM:
-    // 0.128 / 0.155 / 0.144 ms for 0 / 1 / 2 (gpurun_out/r05an): larger holders cost more terms
-    void ChooseMarginalSources(const std::vector<int> &pre);
     // fast order: a marginal (and the label of variable 0) from the terms of each value
     void MargTerms(int v, const std::vector<std::vector<std::string>> &terms);
     int nobs = 0;
     // op boundary (+ diagnostic cycle stamp of op category k when FBN_JT_PROFILE is set)
     bool profile = false;
-    // fast order, op regions merged (FBN_JT_MERGE bits): 1 = a clique's SepDis ops and marginals in
-    // one region (independent of each other: their latencies overlap), 2 = a Collect message's
-    // sums in one region with the next clique's product (small cliques)
-    int merge = 0;
-    int64_t init_batch = 16;  // fast order: entries per software-pipelined batch of the fused product
-    bool in_merged = false;  // the current op's closing boundary is left out
+    static constexpr int64_t kInitBatch = 16;  // fast order: entries per software-pipelined batch of the fused product
+    // fast order: a clique's SepDis ops and marginals share one op region (independent of each
+    // other: their latencies overlap); inside it an op's closing boundary is left out
+    bool in_merged = false;
     int min_waves = 1;
-    // fast order: unbranched marginals with observed lanes stored as 0.0 (FBN_JT_MARG_V2, default 1)
-    // and 16-byte stores of adjacent values (FBN_JT_MARG_PAIR, default 1)
-    bool marg_v2 = true, marg_pair = true;
+    // fast order: unbranched marginals with observed lanes stored as 0.0 and 16-byte stores of
+    // adjacent values (FBN_JT_MARG_V2, default 1)
+    bool marg_v2 = true;
     // where each stored message lives, per separator entry: "W(row)" (the per-wave workspace in
     // global memory) or "LP(row)" (the LDS message pool); the Collect message (child -> parent) and
     // the Distribute message (parent -> child) of a separator are placed separately
@@ -216,7 +207,7 @@ class JTGen {
     // (round 5: 144 -- with the initial potentials as scalar loads, the LDS this frees holds the
     // message pool: ALARM 0.165 -> 0.138 ms per 100k cases; 96 / 112 / 128 / 136 / 144 measured
     // 0.151 / 0.142 / 0.141 / 0.140 / 0.138 ms, gpurun_out/r05l, r05m)
-    int64_t kRegEntries = 144;
+    static constexpr int64_t kRegEntries = 144;
     std::string N(const std::string &P, int c, int64_t e) const {
         if (e >= kRegEntries) return "L(" + std::to_string(e - kRegEntries) + ")";
         return P + std::to_string(c) + "_" + std::to_string(e);
@@ -318,7 +309,7 @@ void JTGen::InitProd(const std::string &P, int c, const std::vector<std::pair<in
         for (int64_t e = 0; e < t.size(); ++e) kidx[i].push_back(SepIndex(t, sp, e));
     }
     const int64_t Tup = up >= 0 ? plan.seps[up].size() : 0;
-    const int64_t kB = init_batch, T = t.size();  // (FBN_JT_INIT_BATCH: tuning)
+    const int64_t kB = kInitBatch, T = t.size();
     auto loads = [&](int64_t b0) {
         if (b0 >= T) return;
         o << "       ";
@@ -486,7 +477,7 @@ void JTGen::MargTerms(int v, const std::vector<std::vector<std::string>> &terms)
         }
         for (int d = 0; d < dim; ++d) {
             const int64_t k = out_off[v] + d;
-            if (marg_pair && d + 1 < dim) {
+            if (marg_v2 && d + 1 < dim) {
                 o << "          if (ACT) OUTS2(" << k << ", ob ? 0.0 : dv(p" << d << ", tot, yt), ob ? 0.0 : dv(p" << d + 1 << ", tot, yt));\n";
                 ++d;
             } else {
@@ -583,30 +574,6 @@ void JTGen::Marg(const std::string &P, int c) {
     }
 }
 
-void JTGen::ChooseMarginalSources(const std::vector<int> &pre) {
-    const int mode = getenv("FBN_JT_MARG_SRC") ? atoi(getenv("FBN_JT_MARG_SRC")) : 0;
-    if (mode == 0 || getenv("FBN_JT_NO_SEPMARG")) return;
-    const int nc = (int)plan.cliques.size(), ns = (int)plan.seps.size(), V = (int)plan.dom.size();
-    std::vector<int> pi(nc);
-    for (int k = 0; k < nc; ++k) pi[pre[k]] = k;
-    for (int v = 0; v < V; ++v) {
-        // candidates: every clique holding v (its Marg, at its Distribute) and every separator
-        // holding v (its parent's SepDis); time = the pre-order position of that op
-        int best_t = -1, bc = -1, bs = -1;
-        int64_t best_sz = 0;
-        auto consider = [&](int t, int64_t sz, int c, int sp) {
-            const bool better = best_t < 0 || (mode == 1 ? t > best_t : t < best_t) || (t == best_t && sz < best_sz);
-            if (better) best_t = t, best_sz = sz, bc = c, bs = sp;
-        };
-        for (int c : cand[v]) consider(pi[c], plan.cliques[c].size(), c, -1);
-        for (int sp = 0; sp < ns; ++sp)
-            for (int u : plan.seps[sp].vars)
-                if (u == v) consider(pi[plan.sep_up[sp]], plan.seps[sp].size(), -1, sp);
-        if (bs >= 0) msep[v] = bs;
-        else msep[v] = -1, mclq[v] = bc;
-    }
-}
-
 // Message placement.  Every stored message has a live interval on the schedule's clock (Collect
 // clique k of the post-order at time k, Distribute clique k of the pre-order at time nc + k): the
 // Collect message of separator s from its child's Collect to its parent's Distribute, the
@@ -636,7 +603,7 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
             for (int s2 : plan.clique_down[q]) mk = std::max<int64_t>(mk, plan.seps[s2].size());
             md_reg[s] = tsize(q) + plan.seps[s].size() + mk <= budget;
         }
-    const bool no_leaf_rc = !getenv("FBN_JT_LEAF_RC") || atoi(getenv("FBN_JT_LEAF_RC")) == 0;  // (tuning)
+    const bool no_leaf_rc = KnobOr("FBN_JT_LEAF_RC", 0) == 0;
     leaf_rc.assign(ns, false);
     col_store.assign(ns, true);
     for (int s = 0; s < ns; ++s) {
@@ -751,7 +718,7 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
             for (int t = it.a; t <= it.b; ++t) live[t] += room;
             for (int t : pay) reg_extra[t] += room;
         }
-        if (!quiet && getenv("FBN_JT_PLACE_DEBUG")) {
+        if (!quiet && KnobSet("FBN_JT_PLACE_DEBUG")) {
             std::string u;
             for (int t = 0; t < 2 * nc; ++t)
                 u += std::to_string(need[t]) + "+" + std::to_string(reg_extra[t]) + (t == nc - 1 ? " | " : " ");
@@ -763,7 +730,7 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
     int64_t ivn = 0;
     for (const auto &t : plan.cliques) ivn += t.size();
     int64_t cap = std::max<int64_t>(0, (per_wave - lds_rows * 64 - (iv_lds ? ivn : 0)) / 64);
-    if (const char *e = getenv("FBN_JT_LDS_POOL")) cap = std::min<int64_t>(cap, std::max(0, atoi(e)));
+    if (const char *e = KnobValue("FBN_JT_LDS_POOL")) cap = std::min<int64_t>(cap, std::max(0, atoi(e)));
     std::vector<int64_t> use(2 * nc + 1, 0);
     std::vector<bool> in_lds(items.size(), false);
     for (int i : order) {
@@ -842,7 +809,7 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
         if (dis_loc[s].empty()) dis_loc[s].assign(plan.seps[s].size(), "0.0");  // (in registers: never read)
         if (col_loc[s].empty()) col_loc[s].assign(plan.seps[s].size(), "0.0");  // (recomputed: never read)
     }
-    if (!quiet && getenv("FBN_JT_PLACE_DEBUG")) {  // diagnostic: the placement's summary
+    if (!quiet && KnobSet("FBN_JT_PLACE_DEBUG")) {  // diagnostic: the placement's summary
         int64_t leaf = 0;
         for (int s = 0; s < ns; ++s)
             if (plan.clique_down[plan.sep_down[s]].empty()) leaf += plan.seps[s].size();
@@ -869,16 +836,8 @@ void JTGen::PlaceMessages(const std::vector<int> &post, const std::vector<int> &
 
 int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &initv) {
     const int nc = (int)plan.cliques.size(), ns = (int)plan.seps.size(), V = plan.num_nodes;
-    if (const char *e = getenv("FBN_JT_REG_ENTRIES")) kRegEntries = std::max<int64_t>(1, atoll(e));  // tuning
-    profile = getenv("FBN_JT_PROFILE") && atoi(getenv("FBN_JT_PROFILE")) != 0;  // diagnostic build
-    merge = fast ? (getenv("FBN_JT_MERGE") ? atoi(getenv("FBN_JT_MERGE")) : kDefaultMerge) : 0;  // (tuning)
-    init_batch = getenv("FBN_JT_INIT_BATCH") ? std::max<int64_t>(1, atoll(getenv("FBN_JT_INIT_BATCH"))) : 16;
-    marg_v2 = fast && (!getenv("FBN_JT_MARG_V2") || atoi(getenv("FBN_JT_MARG_V2")) != 0);  // (tuning)
-    marg_pair = marg_v2 && (!getenv("FBN_JT_MARG_PAIR") || atoi(getenv("FBN_JT_MARG_PAIR")) != 0);  // (tuning)
-    // occupancy: waves per SIMD the register allocation must allow (1: up to 512 registers)
-    min_waves = getenv("FBN_JT_MIN_WAVES") ? std::max(1, atoi(getenv("FBN_JT_MIN_WAVES"))) : min_waves;
-    // initial potentials: LDS copy per wave (1) or scalar loads from the constant buffer (0)
-    iv_lds = getenv("FBN_JT_IV_LDS") ? atoi(getenv("FBN_JT_IV_LDS")) != 0 : iv_lds;
+    profile = KnobOr("FBN_JT_PROFILE", 0) != 0;  // diagnostic build
+    marg_v2 = fast && KnobOr("FBN_JT_MARG_V2", 1) != 0;
     lds_rows = 0;
     for (const auto &t : plan.cliques) lds_rows = std::max<int64_t>(lds_rows, t.size() - kRegEntries);
     // initial potentials: one constant buffer, read with wave-uniform (scalar) loads
@@ -899,7 +858,7 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
         for (int q : cand[v])
             if (home[v] < 0 || plan.cliques[q].size() < plan.cliques[home[v]].size()) home[v] = q;
     msep.assign(V, -1);
-    if (fast && !getenv("FBN_JT_NO_SEPMARG"))  // (diagnostic: marginals from cliques only)
+    if (fast)
         for (int sp = 0; sp < ns; ++sp)
             for (int v : plan.seps[sp].vars) {
                 const int64_t have = msep[v] >= 0 ? plan.seps[msep[v]].size() : plan.cliques[home[v]].size();
@@ -907,13 +866,7 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
             }
     mclq = home;
     // traversal orders: Collect in post-order, Distribute in pre-order of a DFS.  Any child order
-    // gives the same values (schedule freedom, section 4 of DESIGN.md); the fast order may pick one
-    // per phase (FBN_JT_CHILD_ORDER bits, tuning): 1 = Collect visits children by ascending
-    // separator size (a big message is produced last, so it is parked for less of the schedule),
-    // 2 = Distribute visits them by descending size (a big message is consumed first).  ALARM: 1
-    // changes nothing, 2 moves 85 message rows to registers and measured slower (0.127 -> 0.132 ms,
-    // gpurun_out/r05y), so the default keeps the plan's order
-    const int child_order = fast && getenv("FBN_JT_CHILD_ORDER") ? atoi(getenv("FBN_JT_CHILD_ORDER")) : 0;
+    // gives the same values (schedule freedom, section 4 of DESIGN.md).
     // With the register pool on, the child order of each phase is chosen by the placement itself:
     // the plan's, heaviest subtree (sum of clique entries) first, or heaviest last -- whichever
     // leaves the fewest message rows in global memory (a tie keeps the earlier candidate, the
@@ -932,12 +885,7 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
         std::vector<std::vector<int>> kids(nc);
         for (int c = 0; c < nc; ++c) {
             kids[c] = plan.clique_down[c];
-            const bool asc = collect && (child_order & 1), desc = !collect && (child_order & 2);
-            if (asc || desc)
-                std::stable_sort(kids[c].begin(), kids[c].end(), [&](int x, int y) {
-                    return asc ? plan.seps[x].size() < plan.seps[y].size() : plan.seps[x].size() > plan.seps[y].size();
-                });
-            else if (visit)
+            if (visit)
                 std::stable_sort(kids[c].begin(), kids[c].end(), [&](int x, int y) {
                     return visit == 1 ? weight[child(x)] > weight[child(y)] : weight[child(x)] < weight[child(y)];
                 });
@@ -967,14 +915,14 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
     unused.clear();
     dfs(false, 0, unused, pre);
     if ((int)post.size() != nc) return SetError(FBN_ERR_LIMIT, "codegen: tree traversal covers %zu of %d cliques", post.size(), nc);
-    // fp64 values per lane: table in flight + prefetched rows (FBN_JT_PREFETCH_BUDGET: tuning)
+    // fp64 values per lane: table in flight + prefetched rows
     // (fast order: 260 -- round 5 sweep 150 / 200 / 260 / 320: 0.171 / 0.169 / 0.165 / 0.166 ms)
-    const int64_t kBudget = getenv("FBN_JT_PREFETCH_BUDGET") ? atoll(getenv("FBN_JT_PREFETCH_BUDGET")) : fast ? 260 : 200;
+    const int64_t kBudget = fast ? 260 : 200;
     // register pool: fast order only (the exact order's source is pinned); on by default for the
     // variable-major kernel only (the case-major one is faster with it too, but spills more SGPRs)
     int64_t reg_cap = fast && vmajor ? kDefaultRegPool : 0;
-    if (const char *e = getenv("FBN_JT_REG_POOL")) reg_cap = fast ? std::max(0, atoi(e)) : 0;
-    if (reg_cap > 0 && child_order == 0) {
+    if (const char *e = KnobValue("FBN_JT_REG_POOL")) reg_cap = fast ? std::max(0, atoi(e)) : 0;
+    if (reg_cap > 0) {
         int64_t best = -1, plan_peak = 0;
         int bvc = 0, bvd = 0;
         std::vector<int> bpost = post, bpre = pre;
@@ -993,10 +941,9 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
                 if (best < 0 || g < best) best = g, bpost = po, bpre = pr, bvc = vc, bvd = vd;
             }
         post = bpost, pre = bpre;
-        if (getenv("FBN_JT_PLACE_DEBUG"))
+        if (KnobSet("FBN_JT_PLACE_DEBUG"))
             fprintf(stderr, "child order (0 plan, 1 heaviest subtree first, 2 last): Collect %d, Distribute %d\n", bvc, bvd);
     }
-    if (fast) ChooseMarginalSources(pre);
     PlaceMessages(post, pre, kBudget, reg_cap, false);
     int64_t rows = 0;
     for (int s = 0; s < ns; ++s) rows = std::max<int64_t>(rows, sep_row[s] + plan.seps[s].size());
@@ -1008,11 +955,10 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
     o << "#define FBN_LP_BASE " << lds_rows << "\n";
     o << "#define FBN_IV_BASE " << (lds_rows + pool_rows) * 64 << "\n#define FBN_NIV " << initv.size() << "\n";
     o << "#define FBN_IV_LDS " << (iv_lds ? 1 : 0) << "\n#define FBN_MIN_WAVES " << min_waves << "\n";
-    // diagnostic only (FBN_JT_WS_FOLD=K, wrong results): K workspaces shared by all waves, so the
-    // workspace stays in L2 -- times the kernel without its workspace's fabric traffic
-    if (const char *e = getenv("FBN_JT_WS_FOLD")) o << "#define FBN_WS_FOLD " << atoi(e) << "\n";
-    if (getenv("FBN_JT_NO_OUT") && atoi(getenv("FBN_JT_NO_OUT")) != 0) o << "#define FBN_NO_OUT 1\n";
     if (vmajor) o << "#define FBN_VMAJOR 1\n";
+    // (FBN_NO_OUT and FBN_WS_FOLD below are never defined: two retired diagnostic builds whose
+    // inert text stays, because the code-object cache key is a hash of this source and
+    // tests/test_jt_regpool_codegen.py pins the keys)
     o << R"FBN(typedef signed char i8;
 __device__ __forceinline__ double dv(double x, double den, double y) {  // x / den (Markstein, see jt_kernels.hip)
     const double q = x * y;
@@ -1198,8 +1144,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
                 for (int s : next)
                     if (!loaded_a[s]) Load("la", s), loaded_a[s] = true;
         }
-        if (!in_merged) o << B(1);
-        in_merged = false;
+        o << B(1);
         const auto &down = plan.clique_down[c];
         if (fast) {
             std::vector<std::pair<int, std::string>> kids;
@@ -1212,11 +1157,8 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
                 Mul("t", c, s, loaded_a[s] ? "la" : "mc");
             }
         }
-        // merge the message's sums with the next clique's product when both are small
-        in_merged = fast && (merge & 2) && c != cont_root && k + 1 < post.size() && tsize(c) + tsize(post[k + 1]) <= 96;
         if (c != cont_root) SepCol("t", c, plan.clique_up[c], col_store[plan.clique_up[c]]);
     }
-    in_merged = false;
     // ---------------- Distribute, DFS pre-order (root continues from its Collect registers)
     // Register policy (kBudget fp64 values per lane):
     //  * the message to a first child stays in registers if that child's table, the message and
@@ -1284,7 +1226,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
         // consumers of the normalized table: one SepDis per child, one marginal per variable
         // (fast order: each SepDis takes the clique total from its own bin sums)
         if (!fast && down.size() + plan.cliques[c].vars.size() >= 2) Normalize(P, c);
-        in_merged = fast && (merge & 1) && early;
+        in_merged = fast && early;
         for (size_t i = 0; i < down.size(); ++i) {
             if (!early) LoadCol("lc", down[i]), o << B(1);
             SepDis(P, c, down[i], early ? "lb" : "lc", !md_reg[down[i]]);

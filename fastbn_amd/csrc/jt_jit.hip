@@ -62,7 +62,7 @@ uint64_t Fnv1a(const std::string &s, uint64_t h = 1469598103934665603ull) {
 }
 
 std::string CacheDir() {
-    if (const char *e = getenv("FBN_KERNEL_CACHE")) return e;
+    if (const char *e = KnobValue("FBN_KERNEL_CACHE")) return e;
     Dl_info info;
     if (dladdr((void *)&CacheDir, &info) && info.dli_fname) {
         std::string p = info.dli_fname;

@@ -65,11 +65,7 @@ __device__ __forceinline__ bool den_fast_all(double den) {
     return __ballot(!(den >= 0x1p-600 && den <= 0x1p+600)) == 0ull;
 }
 
-
-
-#ifndef FBN_G_UNROLL
-#define FBN_G_UNROLL 8
-#endif
+constexpr int kGUnroll = 8;  // unroll of the global variant's inner sums
 // global-variant op bodies, instantiated for the fast (Markstein) and the exact division
 // Separator sweeps keep up to kGJ results in registers and store them together, so the loads of a
 // chunk of separator entries are not serialized behind per-entry stores (vmcnt is in issue order).
@@ -86,7 +82,7 @@ __device__ __forceinline__ void g_sepcol(double *__restrict__ S, const JtOp &op,
             if (jj >= nj) continue;
             const int j = j0 + jj;
             double acc = 0.0;
-#pragma unroll FBN_G_UNROLL
+#pragma unroll kGUnroll
             for (int q = 0; q < Q; ++q) acc += dv<EXACT>(AT(op.c + q * Ts + j), D);
             const double old = AT(op.a + j);
             res[jj] = (old == 0.0) ? 0.0 : acc / old;
@@ -147,7 +143,7 @@ __device__ __forceinline__ void g_sepdis(double *__restrict__ S, const JtOp &op,
             if (jj >= nj) continue;
             const int j = j0 + jj;
             double acc = 0.0;
-#pragma unroll FBN_G_UNROLL
+#pragma unroll kGUnroll
             for (int q = 0; q < per; ++q) acc += dv<EXACT>(AT(op.c + ls[j * per + q]), D);
             const double old = AT(op.a + j);
             res[jj] = (old == 0.0) ? 0.0 : acc / old;
@@ -197,7 +193,7 @@ __device__ __forceinline__ double g_marg(double *__restrict__ S, int toff, int d
     for (int d = 0; d < dim; ++d) {
         double acc = 0.0;
         for (int hi = 0; hi < nhi; ++hi)
-#pragma unroll FBN_G_UNROLL
+#pragma unroll kGUnroll
             for (int lo = 0; lo < cum; ++lo) acc += dv<EXACT>(AT(toff + hi * bw + d * cum + lo), D);
         if (act) o[d] = acc;
         tot += acc;

@@ -29,6 +29,9 @@ namespace fbn {
 
 namespace {
 
+constexpr int64_t kCacheRows = 64;   // rows of a wave's share of L2, as the R-order and tiling models take it
+constexpr int64_t kLruSteps = 1024;  // steps of the R stream the LRU model replays (the stream is periodic)
+
 int PosIn(const std::vector<int> &vars, int v) {
     for (size_t i = 0; i < vars.size(); ++i)
         if (vars[i] == v) return (int)i;
@@ -184,7 +187,7 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
     // waves per workgroup sharing a case group (1 .. JT_T_W; FBN_JT_TW: tuning knob).  Default 1:
     // on the Munin-like tree 2 / 4 waves per case group measured 235 / 291 ms against 211 ms --
     // the passes' per-pass latency chain and imbalance outweigh the larger shared LDS stage
-    const int TW = std::max(1, std::min(JT_T_W, getenv("FBN_JT_TW") ? atoi(getenv("FBN_JT_TW")) : 1));
+    const int TW = std::max(1, std::min(JT_T_W, (int)KnobOr("FBN_JT_TW", 1)));
     prog.waves = TW;
     int64_t max_x = 1, max_bins = 1;
 
@@ -249,7 +252,6 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
         {
             // weight of a row change: an LDS factor 1/8; a wave-store factor that stays in the
             // wave's share of L2 (<= kCacheRows rows) 1/4; a larger one (its next row misses) 1
-            static const int64_t kCacheRows = getenv("FBN_JT_ORDER_ROWS") ? atoll(getenv("FBN_JT_ORDER_ROWS")) : 64;
             auto wgt = [&](int j) {
                 return j < P.nl ? 0.125 : fac[j].sep->size() <= kCacheRows ? 0.25 : 1.0;
             };
@@ -296,12 +298,11 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
             // (kCacheRows rows): round 0's row stream (every slot's rows of every wave-store factor,
             // reused rows skipped as the kernel does) through a kCacheRows-row LRU, for candidate
             // orders -- all when few, else the order above, its adjacent swaps and seeded random
-            // ones; the fewest misses wins (ties keep the order above).  FBN_JT_NO_LRU_ORDER: off.
+            // ones; the fewest misses wins (ties keep the order above).
             int64_t glob_rows = 0;
             for (int j = P.nl; j < nf; ++j) glob_rows += fac[j].sep->size();
             const int64_t nR_ = Prod(t, RO) * Prod(t, RI);
-            static const bool no_lru = getenv("FBN_JT_NO_LRU_ORDER") != nullptr;
-            if (!no_lru && nf > P.nl && glob_rows > kCacheRows && nR_ * P.rounds * (nf - P.nl) >= 8192) {
+            if (nf > P.nl && glob_rows > kCacheRows && nR_ * P.rounds * (nf - P.nl) >= 8192) {
                 std::vector<std::vector<int>> gd;
                 ForEachConfig(t, G, [&](const std::vector<int> &d) {
                     if (gd.size() < (size_t)JT_T_L) gd.push_back(d);
@@ -312,7 +313,6 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
                     for (size_t sl = 0; sl < gd.size(); ++sl)
                         for (size_t i = 0; i < G.size(); ++i) gpart[j][sl] += gd[sl][i] * fs[j][G[i]];
                 const int K = (int)std::min<int64_t>(256, kCacheRows);
-                static const int64_t kLruSteps = getenv("FBN_JT_LRU_STEPS") ? atoll(getenv("FBN_JT_LRU_STEPS")) : 1024;
                 auto misses = [&](const std::vector<int> &ord) -> int64_t {
                     const int nr = (int)ord.size();
                     std::vector<int> d(nr, 0);
@@ -479,16 +479,15 @@ int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget) 
             // LRU the model assumes.
             int64_t chunk = nRi_;
             {
-                const bool no_tiling = !getenv("FBN_JT_TILING") || atoi(getenv("FBN_JT_TILING")) == 0;
-                static const int64_t kCacheRowsT = getenv("FBN_JT_ORDER_ROWS") ? atoll(getenv("FBN_JT_ORDER_ROWS")) : 64;
+                const bool no_tiling = KnobOr("FBN_JT_TILING", 0) == 0;
                 int64_t glob = 0;
                 for (int j = P.nl; j < nf; ++j) glob += fac[j].sep->size();
-                if (!no_tiling && TW == 1 && nf > P.nl && nRi_ >= 4 && nRo_ >= 2 && glob > kCacheRowsT) {
+                if (!no_tiling && TW == 1 && nf > P.nl && nRi_ >= 4 && nRo_ >= 2 && glob > kCacheRows) {
                     std::vector<std::vector<int64_t>> gp(nf);  // round 0's G parts (slot) of each factor
                     for (int j = P.nl; j < nf; ++j)
                         for (int64_t sl = 0; sl < std::min<int64_t>(nG, JT_T_L); ++sl)
                             gp[j].push_back(prog.tab[P.g_off + sl * (4 + nf) + 4 + j]);
-                    const int K = (int)std::min<int64_t>(256, kCacheRowsT);
+                    const int K = (int)std::min<int64_t>(256, kCacheRows);
                     const int64_t kSteps = std::min<int64_t>(nRo_ * nRi_, 16384);
                     auto seq_misses = [&](int64_t q) -> int64_t {
                         std::vector<int64_t> prev(nf, -1), keys(K);

@@ -843,18 +843,9 @@ extern "C" hipError_t fbn_jt_virt_launch(const JtVClique *cls, const int32_t *au
                                          double *ws, int32_t *wsi, int *flags, long long ncases, long long store_rows,
                                          long long scratch_row, long long scratch_rows, int nc, int V, int SD,
                                          int grid, int dbg, hipStream_t stream) {
-    // scratch-table cache policy (diagnostic override FBN_JT_VPOL; results do not depend on it)
-    static const int pol = getenv("FBN_JT_VPOL") ? atoi(getenv("FBN_JT_VPOL")) : 1;
-#define FBN_VLAUNCH(SPv)                                                                                          \
-    hipLaunchKernelGGL(jt_virt_kernel<SPv>, dim3(grid), dim3(64 * JT_V_WAVES), 0, stream, cls, aux, initv, dig, \
-                       order, sched, vsel, evid, marg, labels, ws, wsi, flags, ncases, store_rows, scratch_row,  \
-                       scratch_rows, nc, V, SD, dbg)
-    switch (pol) {
-    case 1: FBN_VLAUNCH(2 | (2 << 8)); break;     // nt stores, nt loads
-    case 2: FBN_VLAUNCH(16 | (2 << 8)); break;    // sc1 stores (line dropped from L2), nt loads
-    case 3: FBN_VLAUNCH(18 | (18 << 8)); break;   // sc1|nt both ways
-    default: FBN_VLAUNCH(0); break;
-    }
-#undef FBN_VLAUNCH
+    constexpr int kScratchPolicy = 2 | (2 << 8);  // scratch tables: nt stores, nt loads
+    hipLaunchKernelGGL(jt_virt_kernel<kScratchPolicy>, dim3(grid), dim3(64 * JT_V_WAVES), 0, stream, cls, aux, initv,
+                       dig, order, sched, vsel, evid, marg, labels, ws, wsi, flags, ncases, store_rows, scratch_row,
+                       scratch_rows, nc, V, SD, dbg);
     return hipGetLastError();
 }

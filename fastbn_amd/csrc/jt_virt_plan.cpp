@@ -195,10 +195,9 @@ int CompileJTProgramV(const JTPlanHost &plan, JTProgramV &prog) {
         // >= 2 children; with one child its two passes recompute the entries from the messages
         // (3 reads of L2-friendly message rows per entry instead of a scratch write + 2 reads that
         // reach HBM): 369 -> 364 ms per 125k Munin-like cases (FBN_JT_VDEBUG bit 512 measured it)
-        static const int mat_min = getenv("FBN_JT_VMATK") ? atoi(getenv("FBN_JT_VMATK")) : 2;  // (tuning knob)
-        q.mat = (!root && k >= mat_min) ? 1 : 0;
-        static const int cmat_min = getenv("FBN_JT_VCMATK") ? atoi(getenv("FBN_JT_VCMATK")) : 2;  // (tuning knob)
-        q.cmat = (!root && k >= cmat_min) ? 1 : 0;
+        constexpr int kMatMinChildren = 2;
+        q.mat = (!root && k >= kMatMinChildren) ? 1 : 0;
+        q.cmat = (!root && k >= kMatMinChildren) ? 1 : 0;
         q.iv_off = (int32_t)prog.initv.size();
         prog.initv.insert(prog.initv.end(), t.pot.begin(), t.pot.end());
         // digits of every entry for the evidence test: packed into one 32-bit word with the

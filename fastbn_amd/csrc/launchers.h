@@ -75,14 +75,10 @@ extern "C" hipError_t fbn_ci_l1_round(const uint32_t *bits, const int32_t *dims,
                                       unsigned *open_next, int next_chunk, unsigned long long *sstat, unsigned epoch,
                                       const int32_t *plist, hipStream_t s);
 extern "C" hipError_t fbn_ci_gram(const uint32_t *bits, long long W, const int32_t *rl, const int32_t *tasks,
-                                  long long ntasks, int masked, int32_t *out, int num_cu, hipStream_t s);
+                                  long long ntasks, int32_t *out, int num_cu, hipStream_t s);
 extern "C" hipError_t fbn_ci_gram_pairs(const int32_t *G, long long ld, const int32_t *lead0, const int32_t *dims,
                                         const int32_t *row0, const int32_t *rowcnt, long long t0, long long n,
                                         int nvars, int32_t *counts, int32_t *pairtab, int num_cu, hipStream_t s);
-extern "C" hipError_t fbn_ci_gram_triples(const int32_t *G, const long long *goff, const int32_t *gR,
-                                          const int32_t *adj, const int32_t *adj_off, const int32_t *loff,
-                                          const int32_t *dims, const int32_t *items, long long n, int32_t *counts,
-                                          const int32_t *pairtab, int nvars, int num_cu, hipStream_t s);
 extern "C" hipError_t fbn_ci_bits_pairs_tiled(const uint32_t *bits, const int32_t *row0, const int32_t *rowcnt,
                                               long long W, const int32_t *tasks, long long ntasks, int nvars,
                                               long long t0, long long t1, int32_t *counts, int32_t *pairtab,

@@ -136,17 +136,6 @@ int CheckLbpEvidence(const LbpModel &M, const int8_t *ev, int64_t ncases) {
     return FBN_OK;
 }
 
-namespace {
-
-int Threads() {
-    const unsigned hc = std::thread::hardware_concurrency();
-    int t = (int)std::max(1u, std::min(16u, hc ? hc : 1u));
-    if (const char *e = getenv("OMP_NUM_THREADS")) t = std::max(1, std::min(t, atoi(e)));
-    return t;
-}
-
-}  // namespace
-
 int HostLbp(const LbpModel &M, const int8_t *ev, int64_t ncases, int iters, double tol, double damping,
             int32_t *labels, double *marg, double *stats, double *messages, double *lambda) {
     if (ncases == 0) return FBN_OK;
@@ -231,7 +220,7 @@ int HostLbp(const LbpModel &M, const int8_t *ev, int64_t ncases, int iters, doub
                 }
         }
     };
-    const int T = (int)std::min<int64_t>(Threads(), ncases);
+    const int T = (int)std::min<int64_t>(HostThreads(), ncases);
     std::vector<std::thread> th;
     for (int t = 1; t < T; ++t) th.emplace_back(run, ncases * t / T, ncases * (t + 1) / T);
     run(0, ncases / T);

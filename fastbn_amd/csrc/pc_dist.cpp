@@ -214,7 +214,7 @@ int fbn_pc_dist_create(int nvars, double alpha, int depth, int group_size, fbn_p
     s->alpha = alpha;
     s->depth = depth;
     s->group_size = group_size;
-    s->pairs = !getenv("FBN_CI_NO_PAIRS");
+    s->pairs = !fbn::KnobSet("FBN_CI_NO_PAIRS");
     s->adj.assign(nvars, {});
     *out = s.release();
     return FBN_OK;
@@ -280,9 +280,9 @@ int fbn_pc_dist_run(fbn_pc_dist *s, fbn_ci_ctx *c, int32_t *record) {
         const int32_t *dims = fbn::CiCtxDims(c);
         fbn::CiBatchStats st{0, 0};
         for (int v = 0; v < nv; ++v) st.dim_rows += (int64_t)(nv - 1) * dims[v], st.maxdim = std::max(st.maxdim, (int)dims[v]);
-        if (fbn::CiAllPairsEligible(c, st) && !getenv("FBN_CI_NO_IMPLICIT")) {
+        if (fbn::CiAllPairsEligible(c, st)) {
             std::vector<uint8_t> rm(e - b);
-            const int64_t chunk = getenv("FBN_PC_L0CHUNK") ? std::max(1ll, atoll(getenv("FBN_PC_L0CHUNK"))) : (1ll << 22);
+            const int64_t chunk = std::max<int64_t>(1, fbn::KnobOr("FBN_PC_L0CHUNK", (int64_t)1 << 22));
             for (int64_t t0 = (int64_t)b; t0 < (int64_t)e; t0 += chunk) {
                 const int64_t m = std::min<int64_t>(chunk, (int64_t)e - t0);
                 if ((rc = fbn::CiBatchLaunchAllPairs(c, s->alpha, &st, t0, m))) return rc;
@@ -413,7 +413,7 @@ int fbn_pc_dist_apply(fbn_pc_dist *s, const int32_t *records, int *more) {
             p += 1 + d;
         }
     }
-    static const bool timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool timing = fbn::PcTiming();
     auto ta = std::chrono::steady_clock::now();
     FlushSepsets(s);
     if (d == 0) s->res.sepset.set_level0(s->nvars, std::move(rm));  // edges = the complete graph (flags taken over)

@@ -82,12 +82,12 @@ void Advance(EdgeState &e, int d) {  // ChoiceGenerator::Next (src/ChoiceGenerat
 // levels whose candidate sets number at most this many run in a single round; levels with fewer
 // open edges than kPipelineEdges run as one half (FBN_PC_FULLSPEC / FBN_PC_PIPELINE_EDGES: test and
 // diagnostic overrides, read per level)
-int64_t EnvOr(const char *name, int64_t dflt) {
-    const char *v = getenv(name);
-    return v ? atoll(v) : dflt;
-}
-int64_t FullSpeculation() { return EnvOr("FBN_PC_FULLSPEC", 16384); }
+int64_t FullSpeculation() { return KnobOr("FBN_PC_FULLSPEC", 16384); }
 constexpr int64_t kPipelineEdges = 2048;
+// a single-round level splits into two halves from this many candidate sets; the first half takes
+// this share of them
+constexpr int64_t kPipelineFull = 4096;
+constexpr double kFirstHalfShare = 0.20;
 
 int64_t binom(int64_t m, int k) {  // C(m, k), saturating at 2^40
     if (k < 0 || m < k) return 0;
@@ -144,7 +144,7 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
         // the complete graph (a PC run's level 0): edge index = pair index, the kernels decode the
         // pairs of the range themselves
         const bool all_pairs = (int64_t)edges.size() == (int64_t)nv * (nv - 1) / 2 &&
-                               CiAllPairsEligible(ctx, st0) && !getenv("FBN_CI_NO_IMPLICIT");
+                               CiAllPairsEligible(ctx, st0);
         int rc = all_pairs ? CiBatchLaunchAllPairs(ctx, alpha, &st0, (int64_t)e_begin, (int64_t)E)
                            : CiBatchLaunch(ctx, 0, pairs, (int64_t)E, 0, alpha, false, &st0);
         if (rc) return rc;
@@ -161,13 +161,6 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
         if (int rc = CiLevel1Device(ctx, alpha, adj, edges, e_begin, e_end, out, res, &done)) return rc;
         if (done) return FBN_OK;
     }
-    // level 1 on the bit-sliced store, FBN_CI_GRAM1 = 1: per-variable Grams make every candidate
-    // set's table a gather (a test then costs about its G^2 pass; FBN_PC_FULLSPEC1 = speculation
-    // cap).  Off by default: config 5's Grams cover all 3.46M candidate sets (45.9 G popcount words,
-    // 4.6 ms) where the rounds launch 0.39M sets (1.9 ms of derived counting).
-    bool gram = false;
-    if (d == 1 && getenv("FBN_CI_GRAM1") && !getenv("FBN_CI_NO_GRAM"))
-        if (int rc = CiTriplePrepare(ctx, adj, edges, e_begin, e_end, &gram)) return rc;
     std::vector<EdgeState> st(E);
     for (size_t e = 0; e < E; ++e) {
         st[e].x = edges[e_begin + e].first;
@@ -180,13 +173,13 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
     int64_t open_edges = 0;
     for (auto &s : st) open_edges += !s.resolved;
     int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>(32, EnvOr("FBN_PC_ROUND0", 8192) / std::max<int64_t>(1, open_edges)));
-    const int64_t growth = std::max<int64_t>(2, EnvOr("FBN_PC_GROWTH", 4));  // chunk factor per round
+        1, std::min<int64_t>(32, KnobOr("FBN_PC_ROUND0", 8192) / std::max<int64_t>(1, open_edges)));
+    const int64_t growth = std::max<int64_t>(2, KnobOr("FBN_PC_GROWTH", 4));  // chunk factor per round
     bool full = false;
     // small levels: every candidate set of every edge in one round (one host round trip per level;
     // the extra speculative tests cost less than the round trips they save)
     {
-        const int64_t cap = gram ? EnvOr("FBN_PC_FULLSPEC1", 16384) : FullSpeculation();
+        const int64_t cap = FullSpeculation();
         int64_t all = 0;
         for (auto &s : st) {
             if (s.resolved) continue;
@@ -195,7 +188,7 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
         }
         if (all <= cap) chunk = all, full = true;
     }
-    static const bool timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool timing = PcTiming();
     // Two halves of the edge range, each with its own rounds, alternate on the device: while one
     // half's batch runs, the host resolves the other's results and generates its next round (the
     // device stays busy through the host work).  One half when a single round covers the level or
@@ -211,8 +204,8 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
     };
     // (a single-round level of many candidate sets -- config-5 level 2, 8.7k -- also splits in two:
     // the second half is generated on the host while the first half's batch runs)
-    const int nh = full ? (chunk >= EnvOr("FBN_PC_PIPELINE_FULL", (int64_t)4096) ? 2 : 1)
-                        : (open_edges < EnvOr("FBN_PC_PIPELINE_EDGES", kPipelineEdges) ? 1 : 2);
+    const int nh = full ? (chunk >= kPipelineFull ? 2 : 1)
+                        : (open_edges < KnobOr("FBN_PC_PIPELINE_EDGES", kPipelineEdges) ? 1 : 2);
     Half H[2];
     for (int h = 0; h < nh; ++h) H[h].e0 = E * h / nh, H[h].e1 = E * (h + 1) / nh, H[h].chunk = chunk;
     if (nh == 2) {  // cut where the candidate-set counts of the open edges reach a fraction (the
@@ -226,8 +219,7 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
         double acc = 0.0;
         size_t cut = 0;
         // (config 5 level 2, driver median: 50 % 3.55 ms, 25 % 3.51, 15 % 3.51, 10 % 3.49)
-        static const double first = EnvOr("FBN_PC_SPLIT_PCT", 20) / 100.0;  // (tuning)
-        while (cut < E && acc + cost[cut] <= tot * first) acc += cost[cut++];
+        while (cut < E && acc + cost[cut] <= tot * kFirstHalfShare) acc += cost[cut++];
         H[0].e1 = H[1].e0 = std::max<size_t>(1, std::min(cut, E - 1));
     }
     const int32_t *dims = CiCtxDims(ctx);
@@ -235,7 +227,7 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
         hf.items.clear();
         hf.pend.clear();
         hf.stats = CiBatchStats{0, 0};
-        if (d == 1 && group_size == 1 && !getenv("FBN_PC_GEN_GENERAL")) {
+        if (d == 1 && group_size == 1 && !KnobSet("FBN_PC_GEN_GENERAL")) {
             // one conditioning variable, no groups: an edge's next chunk is a contiguous slice of
             // its candidate list (with full speculation: both sides whole) -- written into arrays
             // sized up front, without per-test bookkeeping (the same tests and state transitions
@@ -437,14 +429,14 @@ int RunPCStable(fbn_ci_ctx *ctx, double alpha, int depth, int group_size, PCResu
     for (auto &a : adj) a.clear();
     adj.resize(n);
     std::function<void()> deferred;  // host work that waits for the next level's first batches
-    const bool timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic: host phase times per level
+    const bool timing = PcTiming();  // diagnostic: host phase times per level
     // level 0 tests every pair: its tables are recorded for the level-1 kernel (derived counting)
     // and dropped when this run ends, however it ends
     struct PairModeGuard {
         fbn_ci_ctx *c;
         ~PairModeGuard() { CiSetPairMode(c, 0); }
     } pair_guard{ctx};
-    const bool pairs = !getenv("FBN_CI_NO_PAIRS");
+    const bool pairs = !KnobSet("FBN_CI_NO_PAIRS");
     CiSetPairMode(ctx, pairs ? 1 : 0);
     // level 0 over the implicit complete graph (the kernels decode pair indices): no edge list or
     // adjacency of the complete graph is built; the kept pairs become the skeleton directly
@@ -477,14 +469,14 @@ int RunPCStable(fbn_ci_ctx *ctx, double alpha, int depth, int group_size, PCResu
         }
         CiSetPairMode(ctx, 0);  // the ctx recorded no pair tables: the host levels count in full
         d0 = small_levels;
-    } else if (n >= 2 && CiAllPairsEligible(ctx, st_all) && !getenv("FBN_CI_NO_IMPLICIT")) {
+    } else if (n >= 2 && CiAllPairsEligible(ctx, st_all)) {
         auto ta = std::chrono::steady_clock::now();
         const double k0 = res.kernel_s;
         std::vector<char> removed;  // (sized below on the host path only)
         static_assert(sizeof(char) == sizeof(uint8_t), "flag layout");
         // batches of at most FBN_PC_L0CHUNK pairs (per-test count records: 256 B each; a
         // 10k-variable graph has 5e7 pairs), kept pairs compacted per batch
-        const int64_t chunk = std::max<int64_t>(1, EnvOr("FBN_PC_L0CHUNK", (int64_t)1 << 22));
+        const int64_t chunk = std::max<int64_t>(1, KnobOr("FBN_PC_L0CHUNK", (int64_t)1 << 22));
         int rc = FBN_OK;
         double t_wait = 0, t_kept = 0;
         bool P_done = false;
@@ -510,7 +502,7 @@ int RunPCStable(fbn_ci_ctx *ctx, double alpha, int depth, int group_size, PCResu
                 return FBN_OK;
             };
             auto tb = std::chrono::steady_clock::now();
-            if (E > 0 && CiPairsReady(ctx) && cands > EnvOr("FBN_PC_FULLSPEC", 16384)) {
+            if (E > 0 && CiPairsReady(ctx) && cands > FullSpeculation()) {
                 LevelOut out;
                 const double k1 = res.kernel_s;
                 if ((rc = CiLevel1Run(ctx, alpha, E, cands, out, res, host_side))) return rc;

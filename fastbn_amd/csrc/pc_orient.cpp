@@ -387,7 +387,7 @@ struct Orienter {
         auto tq = std::chrono::steady_clock::now();
         sepset.find_many(keys.data(), keys.size(), z.data(), found.data());
         auto tr = std::chrono::steady_clock::now();
-        if (getenv("FBN_PC_TIMING"))
+        if (PcTiming())
             fprintf(stderr, "orient: %zu unshielded triples, sepset lookups %.3f ms\n", tri.size(),
                     std::chrono::duration<double, std::milli>(tr - tq).count());
         for (size_t t = 0; t < tri.size(); ++t) {
@@ -481,7 +481,7 @@ std::string Trim(const std::string &s) {
 }  // namespace
 
 int OrientPC(int nvars, PCResultHost &r) {
-    static const bool timing = getenv("FBN_PC_TIMING") != nullptr;  // diagnostic
+    const bool timing = PcTiming();
     auto t0 = std::chrono::steady_clock::now();
     Orienter o(nvars, r.edges, r.sepset);
     auto t1 = std::chrono::steady_clock::now();

@@ -124,13 +124,6 @@ void PcgJump(const PcgStream &R, uint64_t delta, U128 *mult, U128 *plus) {
     *mult = am, *plus = ap;
 }
 
-int HostThreads() {
-    const unsigned hc = std::thread::hardware_concurrency();
-    int t = (int)std::max(1u, std::min(16u, hc ? hc : 1u));
-    if (const char *e = getenv("OMP_NUM_THREADS")) t = std::max(1, std::min(t, atoi(e)));
-    return t;
-}
-
 void ParallelRanges(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)> &fn) {
     const int T = (int)std::min<int64_t>(HostThreads(), std::max<int64_t>(1, n / grain));
     std::vector<std::thread> th;

@@ -137,11 +137,9 @@ FBN_HD int QueryLabel(const double *row, int d0, double sumw) {
     return lab;
 }
 
-// what the host twins share (sample_host.cpp, ais_host.cpp): the thread count (at most 16, at most
-// OMP_NUM_THREADS); fn(begin, end) over [0, n) in contiguous ranges of at least `grain`, in parallel; the
-// sum over 64 lanes in the kernels' butterfly order (lane i adds lane i ^ off, off = 32 .. 1; a is
+// what the host twins share (sample_host.cpp, ais_host.cpp): fn(begin, end) over [0, n) in contiguous
+// ranges of at least `grain`, in parallel on HostThreads() threads (knobs.h); the sum over 64 lanes in the kernels' butterfly order (lane i adds lane i ^ off, off = 32 .. 1; a is
 // overwritten); the parent configuration of node nd from one sample's values (stride between variables: vs)
-int HostThreads();
 void ParallelRanges(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)> &fn);
 double Butterfly(double *a);
 inline int ParentConfig(const SamplerModel &M, const SampleNode &nd, const uint8_t *x, size_t vs) {

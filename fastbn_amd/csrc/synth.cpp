@@ -139,17 +139,10 @@ std::vector<int> TopoOrder(const Network &net) {
 
 namespace {
 
-int GenThreads() {
-    const unsigned hc = std::thread::hardware_concurrency();
-    int t = (int)std::max(1u, std::min(16u, hc ? hc : 1u));
-    if (const char *e = getenv("OMP_NUM_THREADS")) t = std::max(1, std::min(t, atoi(e)));
-    return t;
-}
-
 // fn(t, begin, end) over [0, n) in T contiguous ranges, in parallel
 template <class F>
 void ParallelRanges(int64_t n, F fn) {
-    const int T = (int)std::min<int64_t>(GenThreads(), std::max<int64_t>(1, n / 4096));
+    const int T = (int)std::min<int64_t>(HostThreads(), std::max<int64_t>(1, n / 4096));
     std::vector<std::thread> th;
     for (int t = 1; t < T; ++t) th.emplace_back(fn, t, n * t / T, n * (t + 1) / T);
     fn(0, 0, n / T);

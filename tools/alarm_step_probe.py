@@ -1,6 +1,6 @@
 """ALARM headline step as bench.py times it (100k cases, back-to-back steps on one stream, torch
 events around each step, wall clock over the steps): ms per step and event ms per step, for
-comparing launch-level variants (e.g. FBN_JT_NO_FIXUP=1, diagnostic).  alarm_step_probe.py [steps] [timing 0/1]"""
+comparing launch-level variants.  alarm_step_probe.py [steps] [timing 0/1]"""
 import os
 import sys
 import time

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Round-6 PMC of the Munin-like tiled kernel after the branch-free factor loads (jt_tile.hip
-# FBN_TILE_REUSE=0): FETCH_SIZE / WRITE_SIZE (+ the copy8 calibration) and one SQ pass, one counter
+# Round-6 PMC of the Munin-like tiled kernel after the branch-free factor loads (jt_tile.hip):
+# FETCH_SIZE / WRITE_SIZE (+ the copy8 calibration) and one SQ pass, one counter
 # group per rocprofv3 pass, each its own process under its own time limit; then
 # tools/r06_munin_json.py writes profiles/r06/munin_traffic.json and the "munin" entry of
 # profiles/r06/jt_valu.json (the summaries bench.py reads).  usage: tools/profile_r06_munin.sh <outdir>
