@@ -155,17 +155,7 @@ static int CiPairTasks(fbn_ci_ctx *c, int64_t t0, int64_t t1, hipStream_t s) {
     if (c->ptask_t0 == t0 && c->ptask_t1 == t1) return FBN_OK;
     const int nv = c->nvars;
     const int64_t P = (int64_t)nv * (nv - 1) / 2;
-    auto row_of = [&](int64_t t) {  // u of pair t
-        int64_t lo = 0, hi = nv - 2;
-        while (lo < hi) {
-            const int64_t m = (lo + hi + 1) / 2;
-            if (m * nv - m * (m + 1) / 2 <= t) lo = m;
-            else hi = m - 1;
-        }
-        return (int)lo;
-    };
-    auto idx = [&](int64_t u, int64_t v) { return u * nv - u * (u + 1) / 2 + (v - u - 1); };
-    const int u0 = t1 > t0 ? row_of(t0) : 0, u1 = t1 > t0 ? row_of(t1 - 1) : -1;
+    const int u0 = t1 > t0 ? PairRow(t0, nv) : 0, u1 = t1 > t0 ? PairRow(t1 - 1, nv) : -1;
     const bool full = t0 == 0 && t1 == P;
     std::vector<int> cls[5], ucls[5];
     for (int v = 0; v < nv; ++v) {
@@ -189,7 +179,7 @@ static int CiPairTasks(fbn_ci_ctx *c, int64_t t0, int64_t t1, hipStream_t s) {
                         for (int b = 0; b < nys && !any; ++b) {
                             const int x = X[i + a], y = Y[j + b];
                             if (x < y) {
-                                const int64_t t = idx(x, y);
+                                const int64_t t = PairIndex(x, y, nv);
                                 any = t >= t0 && t < t1;
                             }
                         }
@@ -249,7 +239,6 @@ static int CiGram0Tasks(fbn_ci_ctx *c, int64_t t0, int64_t t1, hipStream_t s) {
     std::vector<int32_t> var_of(R);
     for (int v = 0; v < nv; ++v)
         for (int a = 0; a + 1 < c->dims[v]; ++a) var_of[c->lead0_host[v] + a] = v;
-    auto idx = [&](int64_t u, int64_t v) { return u * nv - u * (u + 1) / 2 + (v - u - 1); };
     const int TI = fbn_ci_gram_task_ints();
     std::vector<int32_t> tasks;
     // tiles in 16 x 16-tile super-blocks (128 + 128 rows = 3.2 MB at 100k samples: one XCD's L2),
@@ -264,7 +253,8 @@ static int CiGram0Tasks(fbn_ci_ctx *c, int64_t t0, int64_t t1, hipStream_t s) {
             const int64_t c0 = 8 * bj, c1 = std::min(R, c0 + 8);
             const int vj0 = var_of[c0], vj1 = var_of[c1 - 1];
             if (vi0 >= vj1) continue;  // no x < y in the tile
-            const int64_t tmin = idx(vi0, std::max(vj0, vi0 + 1)), tmax = idx(std::min(vi1, vj1 - 1), vj1);
+            const int64_t tmin = PairIndex(vi0, std::max(vj0, vi0 + 1), nv),
+                          tmax = PairIndex(std::min(vi1, vj1 - 1), vj1, nv);
             if (tmax < t0 || tmin >= t1) continue;
             const int64_t off = r0 * R + c0;
             const int32_t t[8] = {-1, (int32_t)r0, (int32_t)(r1 - r0), (int32_t)c0, (int32_t)(c1 - c0),
@@ -283,16 +273,7 @@ static int CiGram0Tasks(fbn_ci_ctx *c, int64_t t0, int64_t t1, hipStream_t s) {
 // x-variable row range [r0, r1) of the leading rows that the pairs [t0, t0 + n) read as rows of G
 static void CiPairRowRange(const fbn_ci_ctx *c, int64_t t0, int64_t n, int64_t *r0, int64_t *r1) {
     const int nv = c->nvars;
-    auto row_of = [&](int64_t t) {
-        int64_t lo = 0, hi = nv - 2;
-        while (lo < hi) {
-            const int64_t m = (lo + hi + 1) / 2;
-            if (m * nv - m * (m + 1) / 2 <= t) lo = m;
-            else hi = m - 1;
-        }
-        return (int)lo;
-    };
-    const int u0 = row_of(t0), u1 = row_of(t0 + n - 1);
+    const int u0 = PairRow(t0, nv), u1 = PairRow(t0 + n - 1, nv);
     *r0 = c->lead0_host[u0];
     *r1 = u1 + 1 < nv ? c->lead0_host[u1 + 1] : (int64_t)c->leadrows_host.size();
 }
@@ -351,9 +332,6 @@ static int CiGram0Mfma(fbn_ci_ctx *c, int64_t t0, int64_t n, hipStream_t s, bool
     return FBN_OK;
 }
 
-// items: host copy (validated here).  zc_items / zc_indep / zc_df: optional device-visible
-// (pinned, mapped) host buffers the kernels read the items from and write the decisions to
-// directly -- no staging copies for the small batches of a latency-bound driver round.
 // the bit-sliced store (one mask row per value, W words per row padded to a multiple of 4 for
 // 16-byte loads) and the per-row sample counts, built once per ctx on stream s
 int CiBitsEnsure(fbn_ci_ctx *c, hipStream_t s) {
@@ -415,121 +393,128 @@ static int CiTableCheck(const fbn_ci_ctx *c, const int32_t *it, int d, long long
     return FBN_OK;
 }
 
-int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double alpha, bool want_g2p,
-                   int32_t *counts_dev, hipStream_t s, int k, const int32_t *zc_items, uint8_t *zc_indep,
-                   int32_t *zc_df, const fbn::CiBatchStats *pre, bool all_pairs, int64_t pair0) {
-    CiSlot &S = c->slot[k];
-    if (d < 0 || d > 8) return SetError(FBN_ERR_LIMIT, "conditioning set size %d (supported 0..8)", d);
-    const int w = 2 + d;
-    // one validation pass: variable ranges and the largest state count (bit-sliced eligibility)
-    // (skipped for batches generated by the driver from the skeleton, which pass the same figures)
-    int maxdim = 0;
-    int64_t dim_rows = 0;  // sum of the items' state counts (bit-sliced input bytes)
-    const int *dims = c->dims.data();
-    if (pre) {
-        maxdim = pre->maxdim, dim_rows = pre->dim_rows;
-    } else {
-        for (int64_t i = 0; i < n * w; ++i) {
-            const int v = items[i];
-            if ((unsigned)v >= (unsigned)c->nvars)
-                return SetError(FBN_ERR_ARG, "test %lld: variable %d out of range", (long long)(i / w), v);
-            maxdim = std::max(maxdim, dims[v]);
-            dim_rows += dims[v];
-        }
-    }
+// tests with <= 1 conditioning variable over variables with <= 4 states: popcounts of bit-sliced
+// columns (ci_bits.hip).  From kCiBitsMinSamples samples up (ALARM-5000 included: 0.46 -> 0.40 ms per
+// PC run with the pair-table level 1); below, the byte-column kernel (untuned regime).
+bool CiBitsEligible(const fbn_ci_ctx *c, int maxdim) {
+    return maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_BITS") &&
+           (c->N >= kCiBitsMinSamples || fbn::KnobSet("FBN_CI_FORCE_BITS"));
+}
+
+// the slot's item and decision buffers and, for want_g2p, the ctx's G^2 / p buffers, for n tests
+static int CiOutputsEnsure(fbn_ci_ctx *c, CiSlot &S, const CiBatchReq &q) {
     int rc;
-    // tests with <= 1 conditioning variable over variables with <= 4 states: popcounts of
-    // bit-sliced columns (ci_bits.hip).  From 4096 samples up (ALARM-5000 included: 0.46 -> 0.40 ms
-    // per PC run with the pair-table level 1); below, the byte-column kernel (untuned regime).
-    const int64_t kBitsMinSamples = 4096;
-    const bool bits_path = d <= 1 && maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_BITS") &&
-                           (c->N >= kBitsMinSamples || fbn::KnobSet("FBN_CI_FORCE_BITS"));
-    if (bits_path) {
-        if ((rc = CiBitsEnsure(c, s))) return rc;
-        if (!all_pairs && (rc = S.items.ensure((size_t)n * w * 4))) return rc;
-        if ((rc = S.indep.ensure((size_t)n))) return rc;
-        if ((rc = S.df.ensure((size_t)n * 4))) return rc;
-        if ((rc = S.bcounts.ensure((size_t)n * 64 * 4))) return rc;
-        if (want_g2p) {
-            if ((rc = c->g2.ensure((size_t)n * 8))) return rc;
-            if ((rc = c->p.ensure((size_t)n * 8))) return rc;
-        }
-        if (!zc_items && !all_pairs)
-            FBN_HIP(hipMemcpyAsync(S.items.p, items, (size_t)n * w * 4, hipMemcpyHostToDevice, s));
-        // all pairs of the complete graph: the kernels decode test t into its pair (no item array)
-        const int32_t *ditems = all_pairs ? nullptr : zc_items ? zc_items : S.items.as<int32_t>();
-        int pmode = 0;
-        double *g2rec = nullptr;  // level 0's G^2 per pair, kept for the level-1 screen
-        if (c->pair_mode == 1 && d == 0) {
-            const size_t np = (size_t)c->nvars * (c->nvars - 1) / 2;
-            if ((rc = c->pairtab.ensure(std::max<size_t>(np, 1) * 16 * 4))) return rc;
-            pmode = 1;
-            c->pairs_recorded = true;
-            if (all_pairs && !want_g2p && pair0 == c->l1mi_covered) {
-                if ((rc = c->l1mi.ensure(std::max<size_t>(np, 1) * 8))) return rc;
-                g2rec = c->l1mi.as<double>() + pair0;
-                c->l1mi_covered = pair0 + n;
-            }
-        } else if (c->pair_mode == 2 && d == 1 && c->pairs_recorded) {
-            pmode = 2;
-        }
-        // mask rows the count kernel reads: the last value of x and y (and z with pair tables)
-        // is derived, not read (ci_bits.hip)
-        const int64_t skipped = d == 0 ? 2 : (pmode == 2 ? 3 : 0);
-        S.last_bytes = (dim_rows - skipped * n) * c->bits_W * 4;
-        const double *band = nullptr;  // decisions only: p evaluated inside the band
-        int nband = 0;
-        if (!want_g2p && (rc = CiBand(c, alpha, s, &band, &nband))) return rc;
-        if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
-        // all pairs of a range: register-blocked count kernel (ci_bits_pairs_tiled), then phase 2
-        const bool gram0 = all_pairs && d == 0 && CiGram0Eligible(c);
-        const bool tiled = all_pairs && d == 0 && !gram0;
-        if (tiled && (rc = CiPairTasks(c, pair0, pair0 + n, s))) return rc;
-        if (all_pairs && d == 0) {  // fbn_ci_level0_info (the Gram branches below fill in theirs)
-            std::fill(c->l0_info, c->l0_info + 8, 0);
-            c->l0_info[0] = tiled ? 3 : 0;
-        }
-        hipError_t e = hipSuccess;
-        if (gram0) {  // Gram of the leading rows, then every pair's table from it
-            if ((rc = CiLeadEnsure(c, s))) return rc;
-            const int64_t R = (int64_t)c->leadrows_host.size();
-            if ((rc = c->gram0.ensure((size_t)(R * R * 4)))) return rc;
-            bool done = false;
-            if ((rc = CiGram0Mfma(c, pair0, n, s, &done))) return rc;
-            if (!done) {
-                if ((rc = CiGram0Tasks(c, pair0, pair0 + n, s))) return rc;
-                c->l0_info[0] = 1, c->l0_info[1] = R, c->l0_info[4] = c->g0_ntasks;
-                e = fbn_ci_gram(c->bits.as<uint32_t>(), c->bits_W, c->leadrows.as<int32_t>(),
-                                c->g0tasks.as<int32_t>(), c->g0_ntasks, c->gram0.as<int32_t>(), c->num_cu, s);
-            }
-            if (e == hipSuccess)
-                e = fbn_ci_gram_pairs(c->gram0.as<int32_t>(), R, c->lead0.as<int32_t>(), c->ddims.as<int32_t>(),
-                                      c->brow.as<int32_t>(), c->browcnt.as<int32_t>(), pair0, n, c->nvars,
-                                      S.bcounts.as<int32_t>(), pmode == 1 ? c->pairtab.as<int32_t>() : nullptr,
-                                      c->num_cu, s);
-            if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci gram level 0: %s", hipGetErrorString(e));
-        }
-        if (tiled) {
-            e = fbn_ci_bits_pairs_tiled(c->bits.as<uint32_t>(), c->brow.as<int32_t>(), c->browcnt.as<int32_t>(),
-                                        c->bits_W, c->ptasks.as<int32_t>(), c->ptask_n, c->nvars, pair0, pair0 + n,
-                                        S.bcounts.as<int32_t>(), pmode == 1 ? c->pairtab.as<int32_t>() : nullptr,
-                                        c->num_cu, s);
-            if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci tiled pairs launch: %s", hipGetErrorString(e));
-        }
-        e = fbn_ci_bits_launch(c->bits.as<uint32_t>(), c->ddims.as<int32_t>(), c->brow.as<int32_t>(),
-                                          ditems, c->bits_W, n, d, alpha,
-                                          want_g2p ? c->g2.as<double>() : g2rec, zc_df ? zc_df : S.df.as<int32_t>(),
-                                          want_g2p ? c->p.as<double>() : nullptr,
-                                          zc_indep ? zc_indep : S.indep.as<uint8_t>(),
-                                          S.bcounts.as<int32_t>(), counts_dev, c->stats.as<unsigned long long>(),
-                                          c->browcnt.as<int32_t>(), c->pairtab.as<int32_t>(), pmode, c->nvars,
-                                          c->num_cu, (long long)pair0, (tiled || gram0) ? 1 : 0, band,
-                                          nband, s);
-        if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci bits kernel launch: %s", hipGetErrorString(e));
-        if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
-        return FBN_OK;
+    if (!q.all_pairs && (rc = S.items.ensure((size_t)q.n * (2 + q.d) * 4))) return rc;
+    if ((rc = S.indep.ensure((size_t)q.n))) return rc;
+    if ((rc = S.df.ensure((size_t)q.n * 4))) return rc;
+    if (q.want_g2p) {
+        if ((rc = c->g2.ensure((size_t)q.n * 8))) return rc;
+        if ((rc = c->p.ensure((size_t)q.n * 8))) return rc;
     }
-    if (all_pairs) return SetError(FBN_ERR_ARG, "implicit pair batches need the bit-sliced path");
+    return FBN_OK;
+}
+
+// the bit-sliced path (d <= 1, every state count <= 4); dim_rows: sum of the items' state counts
+static int CiLaunchBits(fbn_ci_ctx *c, const CiBatchReq &q, int64_t dim_rows, hipStream_t s) {
+    CiSlot &S = c->slot[q.k];
+    const int64_t n = q.n, pair0 = q.pair0;
+    const int d = q.d;
+    const bool all_pairs = q.all_pairs, want_g2p = q.want_g2p;
+    int rc;
+    if ((rc = CiBitsEnsure(c, s))) return rc;
+    if ((rc = CiOutputsEnsure(c, S, q))) return rc;
+    if ((rc = S.bcounts.ensure((size_t)n * 64 * 4))) return rc;
+    if (!q.zc_items && !all_pairs)
+        FBN_HIP(hipMemcpyAsync(S.items.p, q.items, (size_t)n * (2 + d) * 4, hipMemcpyHostToDevice, s));
+    int pmode = 0;
+    double *g2rec = nullptr;  // level 0's G^2 per pair, kept for the level-1 screen
+    if (c->pair_mode == 1 && d == 0) {
+        const size_t np = (size_t)c->nvars * (c->nvars - 1) / 2;
+        if ((rc = c->pairtab.ensure(std::max<size_t>(np, 1) * 16 * 4))) return rc;
+        pmode = 1;
+        c->pairs_recorded = true;
+        if (all_pairs && !want_g2p && pair0 == c->l1mi_covered) {
+            if ((rc = c->l1mi.ensure(std::max<size_t>(np, 1) * 8))) return rc;
+            g2rec = c->l1mi.as<double>() + pair0;
+            c->l1mi_covered = pair0 + n;
+        }
+    } else if (c->pair_mode == 2 && d == 1 && c->pairs_recorded) {
+        pmode = 2;
+    }
+    // mask rows the count kernel reads: the last value of x and y (and z with pair tables)
+    // is derived, not read (ci_bits.hip)
+    const int64_t skipped = d == 0 ? 2 : (pmode == 2 ? 3 : 0);
+    S.last_bytes = (dim_rows - skipped * n) * c->bits_W * 4;
+    const double *band = nullptr;  // decisions only: p evaluated inside the band
+    int nband = 0;
+    if (!want_g2p && (rc = CiBand(c, q.alpha, s, &band, &nband))) return rc;
+    if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
+    // all pairs of a range: register-blocked count kernel (ci_bits_pairs_tiled), then phase 2
+    const bool gram0 = all_pairs && d == 0 && CiGram0Eligible(c);
+    const bool tiled = all_pairs && d == 0 && !gram0;
+    if (tiled && (rc = CiPairTasks(c, pair0, pair0 + n, s))) return rc;
+    if (all_pairs && d == 0) {  // fbn_ci_level0_info (the Gram branches below fill in theirs)
+        std::fill(c->l0_info, c->l0_info + 8, 0);
+        c->l0_info[0] = tiled ? 3 : 0;
+    }
+    hipError_t e = hipSuccess;
+    if (gram0) {  // Gram of the leading rows, then every pair's table from it
+        if ((rc = CiLeadEnsure(c, s))) return rc;
+        const int64_t R = (int64_t)c->leadrows_host.size();
+        if ((rc = c->gram0.ensure((size_t)(R * R * 4)))) return rc;
+        bool done = false;
+        if ((rc = CiGram0Mfma(c, pair0, n, s, &done))) return rc;
+        if (!done) {
+            if ((rc = CiGram0Tasks(c, pair0, pair0 + n, s))) return rc;
+            c->l0_info[0] = 1, c->l0_info[1] = R, c->l0_info[4] = c->g0_ntasks;
+            e = fbn_ci_gram(c->bits.as<uint32_t>(), c->bits_W, c->leadrows.as<int32_t>(),
+                            c->g0tasks.as<int32_t>(), c->g0_ntasks, c->gram0.as<int32_t>(), c->num_cu, s);
+        }
+        if (e == hipSuccess)
+            e = fbn_ci_gram_pairs(c->gram0.as<int32_t>(), R, c->lead0.as<int32_t>(), c->ddims.as<int32_t>(),
+                                  c->brow.as<int32_t>(), c->browcnt.as<int32_t>(), pair0, n, c->nvars,
+                                  S.bcounts.as<int32_t>(), pmode == 1 ? c->pairtab.as<int32_t>() : nullptr,
+                                  c->num_cu, s);
+        if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci gram level 0: %s", hipGetErrorString(e));
+    }
+    if (tiled) {
+        e = fbn_ci_bits_pairs_tiled(c->bits.as<uint32_t>(), c->brow.as<int32_t>(), c->browcnt.as<int32_t>(),
+                                    c->bits_W, c->ptasks.as<int32_t>(), c->ptask_n, c->nvars, pair0, pair0 + n,
+                                    S.bcounts.as<int32_t>(), pmode == 1 ? c->pairtab.as<int32_t>() : nullptr,
+                                    c->num_cu, s);
+        if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci tiled pairs launch: %s", hipGetErrorString(e));
+    }
+    CiBitsArgs a{};
+    a.bits = c->bits.as<uint32_t>(), a.dims = c->ddims.as<int32_t>();
+    a.row0 = c->brow.as<int32_t>(), a.rowcnt = c->browcnt.as<int32_t>();
+    // all pairs of the complete graph: the kernels decode test t into its pair (no item array)
+    a.items = all_pairs ? nullptr : q.zc_items ? q.zc_items : S.items.as<int32_t>();
+    a.W = c->bits_W, a.n = n, a.t0 = pair0;
+    a.d = d, a.alpha = q.alpha;
+    a.g2 = want_g2p ? c->g2.as<double>() : g2rec;
+    a.df = q.zc_df ? q.zc_df : S.df.as<int32_t>();
+    a.p = want_g2p ? c->p.as<double>() : nullptr;
+    a.indep = q.zc_indep ? q.zc_indep : S.indep.as<uint8_t>();
+    a.counts = S.bcounts.as<int32_t>(), a.counts0 = q.counts_dev;
+    a.stats = c->stats.as<unsigned long long>();
+    a.pairtab = c->pairtab.as<int32_t>(), a.pmode = pmode;
+    a.nvars = c->nvars, a.num_cu = c->num_cu;
+    a.counted = (tiled || gram0) ? 1 : 0;
+    a.band = band, a.nband = nband;
+    e = fbn_ci_bits_launch(&a, s);
+    if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci bits kernel launch: %s", hipGetErrorString(e));
+    if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
+    return FBN_OK;
+}
+
+// the histogram path (ci_kernels.hip); maxdim: the items' largest state count
+static int CiLaunchHist(fbn_ci_ctx *c, const CiBatchReq &q, int maxdim, hipStream_t s) {
+    CiSlot &S = c->slot[q.k];
+    const int32_t *items = q.items;
+    const int64_t n = q.n;
+    const int d = q.d, w = 2 + d;
+    const bool want_g2p = q.want_g2p;
+    int rc;
     size_t lds = 0;
     int64_t mask_rows = 0;  // bit-sliced counting: dimz * (dx + dy + d) mask rows per test
     for (int64_t i = 0; i < n; ++i) {
@@ -543,14 +528,8 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
     // tables beyond the LDS budget: the same layout in a per-workgroup global scratch region
     // (the kernel's own static LDS comes on top of the dynamic region)
     const bool global_tables = lds + fbn_ci_static_lds_bytes() > 160 * 1024;
-    if ((rc = S.items.ensure((size_t)n * w * 4))) return rc;
-    if ((rc = S.indep.ensure((size_t)n))) return rc;
-    if ((rc = S.df.ensure((size_t)n * 4))) return rc;
-    if (want_g2p) {
-        if ((rc = c->g2.ensure((size_t)n * 8))) return rc;
-        if ((rc = c->p.ensure((size_t)n * 8))) return rc;
-    }
-    if (!zc_items) FBN_HIP(hipMemcpyAsync(S.items.p, items, (size_t)n * w * 4, hipMemcpyHostToDevice, s));
+    if ((rc = CiOutputsEnsure(c, S, q))) return rc;
+    if (!q.zc_items) FBN_HIP(hipMemcpyAsync(S.items.p, items, (size_t)n * w * 4, hipMemcpyHostToDevice, s));
     int grid = (int)std::min<int64_t>(n, (int64_t)c->num_cu * 8);
     int32_t *gscratch = nullptr;
     if (global_tables) {
@@ -578,7 +557,7 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
     if (!want_g2p) {
         double dfmax = (double)(maxdim - 1) * (maxdim - 1);
         for (int j = 0; j < d; ++j) dfmax *= maxdim;
-        if ((rc = CiBand(c, alpha, s, &hband, &hnband, (int)std::min<double>(dfmax, kBandDfMax)))) return rc;
+        if ((rc = CiBand(c, q.alpha, s, &hband, &hnband, (int)std::min<double>(dfmax, kBandDfMax)))) return rc;
     }
     // every variable of the batch with <= 4 states and >= 64k samples: the histogram kernel reads
     // the columns packed 2 bits per sample (a quarter of the byte columns' bytes; built once per
@@ -615,17 +594,52 @@ int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double
         }
     }
     if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
-    hipError_t e = fbn_ci_launch(c->cols.as<uint8_t>(), c->ddims.as<int32_t>(),
-                                 zc_items ? zc_items : S.items.as<int32_t>(), c->N, n, d, alpha,
-                                 want_g2p ? c->g2.as<double>() : nullptr, zc_df ? zc_df : S.df.as<int32_t>(),
-                                 want_g2p ? c->p.as<double>() : nullptr, zc_indep ? zc_indep : S.indep.as<uint8_t>(),
-                                 counts_dev, lds, grid, gscratch, c->stats.as<unsigned long long>(),
-                                 bitsn ? c->bits.as<uint32_t>() : nullptr, c->brow.as<int32_t>(), c->bits_W, hband,
-                                 hnband, pk ? c->pack2.as<uint32_t>() : nullptr, c->pack2_W, c->counts_stride, tab,
-                                 tstride, split, split_grid, der2 ? c->pairtab.as<int32_t>() : nullptr, c->nvars, s);
+    CiArgs a{};
+    a.cols = c->cols.as<uint8_t>(), a.dims = c->ddims.as<int32_t>();
+    a.items = q.zc_items ? q.zc_items : S.items.as<int32_t>();
+    a.N = c->N, a.n = n, a.alpha = q.alpha;
+    a.g2 = want_g2p ? c->g2.as<double>() : nullptr;
+    a.df = q.zc_df ? q.zc_df : S.df.as<int32_t>();
+    a.p = want_g2p ? c->p.as<double>() : nullptr;
+    a.indep = q.zc_indep ? q.zc_indep : S.indep.as<uint8_t>();
+    a.counts = q.counts_dev, a.cstride = c->counts_stride;
+    a.gscratch = gscratch;
+    a.stats = c->stats.as<unsigned long long>();
+    a.bits = bitsn ? c->bits.as<uint32_t>() : nullptr;
+    a.row0 = c->brow.as<int32_t>(), a.W = c->bits_W;
+    a.band = hband, a.nband = hnband;
+    a.pk = pk ? c->pack2.as<uint32_t>() : nullptr, a.PW = c->pack2_W;
+    a.tab = tab, a.tstride = tstride, a.split = split;
+    a.pairtab = der2 ? c->pairtab.as<int32_t>() : nullptr;
+    a.nvars = c->nvars;
+    hipError_t e = fbn_ci_launch(&a, d, lds, grid, split_grid, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci kernel launch: %s", hipGetErrorString(e));
     if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
     return FBN_OK;
+}
+
+int CiLaunchDevice(fbn_ci_ctx *c, const CiBatchReq &q, hipStream_t s) {
+    if (q.d < 0 || q.d > 8) return SetError(FBN_ERR_LIMIT, "conditioning set size %d (supported 0..8)", q.d);
+    const int w = 2 + q.d;
+    // one validation pass: variable ranges and the largest state count (bit-sliced eligibility)
+    // (skipped for batches generated by the driver from the skeleton, which pass the same figures)
+    int maxdim = 0;
+    int64_t dim_rows = 0;  // sum of the items' state counts (bit-sliced input bytes)
+    const int *dims = c->dims.data();
+    if (q.pre) {
+        maxdim = q.pre->maxdim, dim_rows = q.pre->dim_rows;
+    } else {
+        for (int64_t i = 0; i < q.n * w; ++i) {
+            const int v = q.items[i];
+            if ((unsigned)v >= (unsigned)c->nvars)
+                return SetError(FBN_ERR_ARG, "test %lld: variable %d out of range", (long long)(i / w), v);
+            maxdim = std::max(maxdim, dims[v]);
+            dim_rows += dims[v];
+        }
+    }
+    if (q.d <= 1 && CiBitsEligible(c, maxdim)) return CiLaunchBits(c, q, dim_rows, s);
+    if (q.all_pairs) return SetError(FBN_ERR_ARG, "implicit pair batches need the bit-sliced path");
+    return CiLaunchHist(c, q, maxdim, s);
 }
 
 }  // namespace fbn
@@ -640,7 +654,10 @@ int fbn_ci_run(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double alp
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (std::find(c->streams_used.begin(), c->streams_used.end(), s) == c->streams_used.end())
         c->streams_used.push_back(s);
-    int rc = fbn::CiLaunchDevice(c, items, n, d, alpha, g2 || p, nullptr, s);
+    fbn::CiBatchReq q;
+    q.items = items, q.n = n, q.d = d, q.alpha = alpha;
+    q.want_g2p = g2 || p;
+    int rc = fbn::CiLaunchDevice(c, q, s);
     if (rc) return rc;
     if (g2) FBN_HIP(hipMemcpyAsync(g2, c->g2.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     if (p) FBN_HIP(hipMemcpyAsync(p, c->p.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
@@ -665,7 +682,11 @@ int fbn_ci_counts(fbn_ci_ctx *c, int x, int y, const int32_t *z, int d, int32_t 
     if (cells) *cells = nc;
     FBN_HIP(hipSetDevice(c->device));
     if ((rc = c->counts.ensure((size_t)nc * 4))) return rc;
-    rc = fbn::CiLaunchDevice(c, item.data(), 1, d, 0.05, false, c->counts.as<int32_t>(), nullptr);
+    fbn::CiBatchReq q;
+    q.items = item.data(), q.n = 1, q.d = d;
+    q.counts_dev = c->counts.as<int32_t>();
+    const hipStream_t null_stream = nullptr;
+    rc = fbn::CiLaunchDevice(c, q, null_stream);
     if (rc) return rc;
     if (counts) FBN_HIP(hipMemcpy(counts, c->counts.p, (size_t)std::min(nc, cap) * 4, hipMemcpyDeviceToHost));
     FBN_HIP(hipDeviceSynchronize());
@@ -701,8 +722,7 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
     fbn::PCResultHost scratch;
     PairModeGuard guard{c, c->pair_mode, c->pairs_recorded};
     auto level0 = [&]() -> int {  // the PC run's level 0, pair tables recorded
-        fbn::CiBatchStats st{0, 0};
-        for (int v = 0; v < nv; ++v) st.dim_rows += (int64_t)(nv - 1) * c->dims[v], st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
+        const fbn::CiBatchStats st = fbn::CiAllPairsStats(c->dims.data(), nv);
         if (!fbn::CiAllPairsEligible(c, st))
             return SetError(FBN_ERR_ARG, "dataset not eligible for the bit-sliced level-0 path");
         const int64_t P = (int64_t)nv * (nv - 1) / 2;
@@ -720,7 +740,7 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
         for (int64_t t = 0; t < n; ++t) {
             const int x = items[2 * t], y = items[2 * t + 1];
             if (x >= y) return SetError(FBN_ERR_ARG, "level-0 tests are pairs x < y");
-            const int64_t pi = (int64_t)x * nv - (int64_t)x * (x + 1) / 2 + (y - x - 1);
+            const int64_t pi = fbn::PairIndex(x, y, nv);
             FBN_HIP(hipMemcpy(rec.data() + t * 64, c->slot[0].bcounts.as<int32_t>() + pi * 64, 64 * 4,
                               hipMemcpyDeviceToHost));
         }
@@ -741,9 +761,10 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
         return FBN_OK;
     }
     if (d == 2) {  // a PC run's level 2 has its level-0 pair tables (derived counting, ci_kernels.hip MODE 3)
-        fbn::CiBatchStats st{0, 0};
-        for (int v = 0; v < nv; ++v) st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
-        if (!c->pairs_recorded && st.maxdim <= 4 && c->N >= 4096 && (rc = level0())) return rc;
+        // (the rule of CiBitsEligible without its knobs: with FBN_CI_NO_BITS this call refuses, as it
+        // always has, where the knob-reading form would fall through to the plain histogram)
+        const int maxdim = *std::max_element(c->dims.begin(), c->dims.end());
+        if (!c->pairs_recorded && maxdim <= 4 && c->N >= fbn::kCiBitsMinSamples && (rc = level0())) return rc;
         if (c->pairs_recorded) fbn::CiSetPairMode(c, 2);
     }
     for (int64_t t = 0; t < n; ++t) {  // the kernel writes every cell of a table: each must fit its row
@@ -757,7 +778,10 @@ int fbn_ci_debug_counts(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, i
     if ((rc = c->counts.ensure((size_t)n * cap * 4))) return rc;
     FBN_HIP(hipMemsetAsync(c->counts.p, 0, (size_t)n * cap * 4, c->stream));  // cells beyond a table: 0
     c->counts_stride = cap;
-    rc = fbn::CiLaunchDevice(c, items, n, d, 0.05, false, c->counts.as<int32_t>(), c->stream);
+    fbn::CiBatchReq q;
+    q.items = items, q.n = n, q.d = d;
+    q.counts_dev = c->counts.as<int32_t>();
+    rc = fbn::CiLaunchDevice(c, q, c->stream);
     c->counts_stride = 0;
     if (rc) return rc;
     FBN_HIP(hipStreamSynchronize(c->stream));
@@ -785,12 +809,9 @@ int fbn_ci_debug_level0_range(fbn_ci_ctx *c, int64_t pair0, int64_t n, int32_t *
     if (n == 0) return FBN_OK;
     FBN_HIP(hipSetDevice(c->device));
     PairModeGuard guard{c, c->pair_mode, c->pairs_recorded};
-    fbn::CiBatchStats st{0, 0};
+    const fbn::CiBatchStats st = fbn::CiAllPairsStats(c->dims.data(), nv);
     int64_t R = 0;
-    for (int v = 0; v < nv; ++v) {
-        st.dim_rows += (int64_t)(nv - 1) * c->dims[v], st.maxdim = std::max(st.maxdim, (int)c->dims[v]);
-        R += c->dims[v] - 1;
-    }
+    for (int v = 0; v < nv; ++v) R += c->dims[v] - 1;
     if (!fbn::CiAllPairsEligible(c, st))
         return SetError(FBN_ERR_ARG, "dataset not eligible for the bit-sliced level-0 path");
     int rc;
@@ -807,9 +828,8 @@ int fbn_ci_debug_level0_range(fbn_ci_ctx *c, int64_t pair0, int64_t n, int32_t *
     FBN_HIP(hipStreamSynchronize(c->stream));
     std::vector<int32_t> rec((size_t)n * 64);
     FBN_HIP(hipMemcpy(rec.data(), c->slot[0].bcounts.p, rec.size() * 4, hipMemcpyDeviceToHost));
-    int x = 0;
-    while ((int64_t)(x + 1) * nv - (int64_t)(x + 1) * (x + 2) / 2 <= pair0) ++x;  // the row of pair0
-    int y = x + 1 + (int)(pair0 - ((int64_t)x * nv - (int64_t)x * (x + 1) / 2));
+    int x = fbn::PairRow(pair0, nv);
+    int y = x + 1 + (int)(pair0 - fbn::PairIndex(x, x + 1, nv));
     for (int64_t t = 0; t < n; ++t) {
         const int cells = c->dims[x] * c->dims[y];
         std::fill(std::copy(rec.begin() + t * 64, rec.begin() + t * 64 + cells, counts + t * 16), counts + t * 16 + 16, 0);

@@ -415,11 +415,19 @@ static int LaunchLds(fbn_jt_plan *p, DevBuf &ws, const int8_t *d_evidence, int64
         FBN_HIP(hipMemsetAsync(p->prof.p, 0, (size_t)grid * 16 * 8, s));
         p->last_grid = grid;
     }
-    hipError_t e = fbn_jt_lds_launch(p->lops.as<JtOp>(), (int)l.ops.size(), p->laux.as<int32_t>(),
-                                     p->linitv.as<double>(), p->ldig.as<uint64_t>(), d_evidence, V, ncases, SD, marg,
-                                     labels, ws.as<double>(), reinterpret_cast<int32_t *>(ws.as<char>() + ws_d),
-                                     wave_entries, store_off, den_off, sep_off, spill_off, nc, cap, spill, force_exact,
-                                     flags, grid, prof ? p->prof.as<unsigned long long>() : nullptr, vm ? 1 : 0, s);
+    JtLdsArgs a{};
+    a.par.ncases = ncases, a.par.wave_entries = wave_entries;
+    a.par.store_off = store_off, a.par.den_off = den_off, a.par.sep_off = sep_off, a.par.spill_off = spill_off;
+    a.par.nops = (int)l.ops.size(), a.par.V = V, a.par.SD = SD, a.par.nc = nc, a.par.cap = cap;
+    a.par.force_exact = force_exact, a.par.vmajor = vm ? 1 : 0;
+    a.par.flags = flags;
+    a.ops = p->lops.as<JtOp>(), a.aux = p->laux.as<int32_t>();
+    a.initv = p->linitv.as<double>(), a.dig = p->ldig.as<uint64_t>();
+    a.evid = d_evidence, a.marg = marg, a.labels = labels;
+    a.ws = ws.as<double>(), a.wsi = reinterpret_cast<int32_t *>(ws.as<char>() + ws_d);
+    a.spill = spill, a.grid = grid;
+    a.prof = prof ? p->prof.as<unsigned long long>() : nullptr;
+    hipError_t e = fbn_jt_lds_launch(&a, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "jt kernel launch: %s", hipGetErrorString(e));
     return FBN_OK;
 }
@@ -530,10 +538,15 @@ static int JtRunDevice(fbn_jt_plan *p, const int8_t *d_evidence, int64_t ncases,
         const size_t ws_i = (size_t)grid * nc * 64 * 4;
         if ((rc = p->ws.ensure(ws_d + ws_i))) return rc;
         if (p->ktiming) FBN_HIP(hipEventRecord(p->ev0, s));
-        hipError_t e = fbn_jt_launch(p->ops.as<JtOp>(), (int)g.ops.size(), p->aux.as<int32_t>(), p->initv.as<double>(),
-                                     p->dig.as<uint64_t>(), d_evidence, V, ncases, SD, marg, labels,
-                                     p->ws.as<double>(), reinterpret_cast<int32_t *>(p->ws.as<char>() + ws_d),
-                                     g.state_entries, nc, grid, vm_direct ? 1 : 0, s);
+        JtArgs a{};
+        a.ops = p->ops.as<JtOp>(), a.aux = p->aux.as<int32_t>();
+        a.initv = p->initv.as<double>(), a.dig = p->dig.as<uint64_t>();
+        a.evid = d_evidence, a.marg = marg, a.labels = labels;
+        a.ws = p->ws.as<double>(), a.wsi = reinterpret_cast<int32_t *>(p->ws.as<char>() + ws_d);
+        a.ncases = ncases, a.NE = g.state_entries;
+        a.nops = (int)g.ops.size(), a.V = V, a.SD = SD, a.nc = nc;
+        a.vmajor = vm_direct ? 1 : 0;
+        hipError_t e = fbn_jt_launch(&a, grid, s);
         if (e != hipSuccess) return SetError(FBN_ERR_HIP, "jt kernel launch: %s", hipGetErrorString(e));
     } else if (variant == 4) {
         // streamed tables: small register footprint, many resident waves; the per-wave store holds

@@ -275,21 +275,20 @@ int CiBatchLaunch(fbn_ci_ctx *c, int k, const int32_t *items, int64_t n, int d, 
     // decisions to the pinned buffers directly (one launch + one sync per round); large rounds
     // stage through device memory with DMA copies
     S.zc = ib <= kZeroCopyBytes && !fbn::KnobSet("FBN_CI_NO_ZEROCOPY");
-    if (S.zc) {
-        rc = CiLaunchDevice(c, hi, n, d, alpha, false, nullptr, c->stream, k, hi, h_ind, want_df ? h_df : nullptr, pre);
-        if (rc) return rc;
-    } else {
-        rc = CiLaunchDevice(c, hi, n, d, alpha, false, nullptr, c->stream, k, nullptr, nullptr, nullptr, pre);
-        if (rc) return rc;
+    CiBatchReq q;
+    q.items = hi, q.n = n, q.d = d, q.alpha = alpha;
+    q.k = k;
+    q.pre = pre;
+    if (S.zc) q.zc_items = hi, q.zc_indep = h_ind, q.zc_df = want_df ? h_df : nullptr;
+    if ((rc = CiLaunchDevice(c, q, c->stream))) return rc;
+    if (!S.zc) {
         FBN_HIP(hipMemcpyAsync(h_ind, S.indep.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
         if (want_df) FBN_HIP(hipMemcpyAsync(h_df, S.df.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     }
     FBN_HIP(hipEventRecord(S.done, c->stream));
     return FBN_OK;
 }
-bool CiAllPairsEligible(const fbn_ci_ctx *c, const CiBatchStats &st) {
-    return st.maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_BITS") && (c->N >= 4096 || fbn::KnobSet("FBN_CI_FORCE_BITS"));
-}
+bool CiAllPairsEligible(const fbn_ci_ctx *c, const CiBatchStats &st) { return CiBitsEligible(c, st.maxdim); }
 int CiBatchLaunchAllPairs(fbn_ci_ctx *c, double alpha, const CiBatchStats *pre, int64_t t0, int64_t n,
                           bool copy_flags) {
     CiSlot &S = c->slot[0];
@@ -299,9 +298,11 @@ int CiBatchLaunchAllPairs(fbn_ci_ctx *c, double alpha, const CiBatchStats *pre, 
     if (n == 0) return FBN_OK;
     int rc;
     if ((rc = PinnedEnsure(S.h_res, S.h_res_bytes, (size_t)n * 5 + 8))) return rc;
-    rc = CiLaunchDevice(c, nullptr, n, 0, alpha, false, nullptr, c->stream, 0, nullptr, nullptr, nullptr, pre, true,
-                        t0);
-    if (rc) return rc;
+    CiBatchReq q;
+    q.n = n, q.d = 0, q.alpha = alpha;
+    q.pre = pre;
+    q.all_pairs = true, q.pair0 = t0;
+    if ((rc = CiLaunchDevice(c, q, c->stream))) return rc;
     if (copy_flags) FBN_HIP(hipMemcpyAsync(S.h_res, S.indep.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     FBN_HIP(hipEventRecord(S.done, c->stream));
     return FBN_OK;
@@ -314,12 +315,9 @@ bool CiPairsReady(const fbn_ci_ctx *c) { return c->pair_mode == 2 && c->pairs_re
 // -- every one-shot CLI run -- takes the device path from its first PC run on.
 bool CiL0L1DeviceEligible(fbn_ci_ctx *c, int group_size) {
     if (group_size != 1 || fbn::KnobSet("FBN_PC_HOST_L1") || fbn::KnobSet("FBN_PC_HOST_L0L1") || c->nvars < 2) return false;
-    for (int v = 0; v < c->nvars; ++v)
-        if (c->dims[v] > 4) return false;
-    if (!c->bits_ready) {
-        const bool bits_path = !fbn::KnobSet("FBN_CI_NO_BITS") && (c->N >= 4096 || fbn::KnobSet("FBN_CI_FORCE_BITS"));
-        if (!bits_path || CiBitsEnsure(c, c->stream) != FBN_OK) return false;
-    }
+    const int maxdim = *std::max_element(c->dims.begin(), c->dims.end());
+    if (maxdim > 4) return false;
+    if (!c->bits_ready && (!CiBitsEligible(c, maxdim) || CiBitsEnsure(c, c->stream) != FBN_OK)) return false;
     return true;
 }
 
@@ -535,14 +533,26 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     chunk = std::min(chunk, max_chunk);
     // the setup writes round 0's lengths and zeroes the open-count ring; each round's resolve writes
     // the next round's lengths and zeroes the other ring slot (no length kernel or memset per round)
-    unsigned long long *sstat = c->l1sstat.as<unsigned long long>();
-    hipError_t e = fbn_ci_l1_setup(c->l1pairs.as<int32_t>(), E, c->l1adj.as<int32_t>(), c->l1adjoff.as<int32_t>(),
-                                   c->l1ed.p, c->l1pos.as<int32_t>(), c->l1st.as<uint8_t>(), c->l1sep.as<int32_t>(),
-                                   c->l1cnt.as<long long>(), (int)chunk, c->l1len.as<int32_t>(),
-                                   c->l1off.as<int32_t>(), c->l1open.as<unsigned>(), sstat, cap, scal, c->num_cu,
-                                   c->pairtab.as<int32_t>(), mi, mi_from_tables ? 1 : 0, c->ddims.as<int32_t>(), band, nband, nv,
-                                   2.0 * (double)c->N, c->l1pcnt.as<int32_t>(), c->l1plist.as<int32_t>(),
-                                   c->l1sstat2.as<unsigned long long>(), scal + 8, s);
+    CiL1Args a{};
+    a.pairs = c->l1pairs.as<int32_t>();
+    a.adj = c->l1adj.as<int32_t>(), a.adj_off = c->l1adjoff.as<int32_t>();
+    a.E = E, a.nv = nv, a.num_cu = c->num_cu;
+    a.ed = c->l1ed.p, a.pos = c->l1pos.as<int32_t>(), a.st = c->l1st.as<uint8_t>();
+    a.sep = c->l1sep.as<int32_t>(), a.counted = c->l1cnt.as<long long>();
+    a.len = c->l1len.as<int32_t>(), a.off = c->l1off.as<int32_t>();
+    a.ring = c->l1open.as<unsigned>(), a.sstat = c->l1sstat.as<unsigned long long>();
+    a.scal = scal, a.cap = cap, a.chunk0 = (int)chunk;
+    a.bits = c->bits.as<uint32_t>(), a.W = c->bits_W;
+    a.dims = c->ddims.as<int32_t>(), a.row0 = c->brow.as<int32_t>();
+    a.pairtab = c->pairtab.as<int32_t>();
+    a.items = c->l1items.as<int32_t>(), a.counts = c->l1counts.as<int32_t>(), a.df = c->l1df.as<int32_t>();
+    a.indep = c->l1indep.as<uint8_t>();
+    a.alpha = alpha, a.stats = c->stats.as<unsigned long long>();
+    a.band = band, a.nband = nband;
+    a.mi = mi, a.mi_from_tables = mi_from_tables ? 1 : 0, a.two_n = 2.0 * (double)c->N;
+    a.pcnt = c->l1pcnt.as<int32_t>(), a.plist = mi ? c->l1plist.as<int32_t>() : nullptr;
+    a.sstat2 = c->l1sstat2.as<unsigned long long>(), a.scal2 = scal + 8;
+    hipError_t e = fbn_ci_l1_setup(&a, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci level-1 setup: %s", hipGetErrorString(e));
     const bool l1timing = fbn::PcTiming();  // diagnostic
     const auto tl0 = std::chrono::steady_clock::now();
@@ -551,14 +561,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
         rounds = r + 1;
         unsigned *open_r = c->l1open.as<unsigned>() + (r & 1);
         const int64_t next_chunk = std::min<int64_t>(chunk * growth, max_chunk);
-        e = fbn_ci_l1_round(c->bits.as<uint32_t>(), c->ddims.as<int32_t>(), c->brow.as<int32_t>(), c->bits_W,
-                            c->l1adj.as<int32_t>(), c->pairtab.as<int32_t>(), nv, c->l1ed.p, c->l1pos.as<int32_t>(),
-                            c->l1st.as<uint8_t>(), c->l1sep.as<int32_t>(), c->l1cnt.as<long long>(),
-                            c->l1len.as<int32_t>(), c->l1off.as<int32_t>(), E, cap, scal, c->l1items.as<int32_t>(),
-                            c->l1counts.as<int32_t>(), c->l1df.as<int32_t>(), c->l1indep.as<uint8_t>(), alpha,
-                            c->stats.as<unsigned long long>(), band, nband, open_r, c->num_cu,
-                            c->l1open.as<unsigned>() + ((r + 1) & 1), (int)next_chunk, sstat, (unsigned)(r + 2),
-                            mi ? c->l1plist.as<int32_t>() : nullptr, s);
+        e = fbn_ci_l1_round(&a, open_r, c->l1open.as<unsigned>() + ((r + 1) & 1), (int)next_chunk, (unsigned)(r + 2), s);
         if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci level-1 round: %s", hipGetErrorString(e));
         FBN_HIP(hipMemcpyAsync(c->h_open + (r & 1), open_r, 4, hipMemcpyDeviceToHost, s));
         FBN_HIP(hipEventRecord(c->l1ev[r & 1], s));

@@ -207,16 +207,34 @@ namespace fbn {
 constexpr int kBandDf = 36;
 constexpr int kBandDfMax = 256;  // larger df (few tests, deep levels): p evaluated
 
+// the bit-sliced path's sample threshold (CiBitsEligible, pc_internal.h)
+constexpr int64_t kCiBitsMinSamples = 4096;
+
 int CiBand(fbn_ci_ctx *c, double alpha, hipStream_t s, const double **out, int *nband, int want_df = 0);
 int CiResetMargin(fbn_ci_ctx *c);
 int CiReadMargin(fbn_ci_ctx *c, double *min_margin, int64_t *near_alpha, bool own_stream_only = false);
 int CiLeadEnsure(fbn_ci_ctx *c, hipStream_t s);
 int CiBitsEnsure(fbn_ci_ctx *c, hipStream_t s);
 int CiPack2Ensure(fbn_ci_ctx *c, hipStream_t s);
-int CiLaunchDevice(fbn_ci_ctx *c, const int32_t *items, int64_t n, int d, double alpha, bool want_g2p,
-                   int32_t *counts_dev, hipStream_t s, int k = 0, const int32_t *zc_items = nullptr,
-                   uint8_t *zc_indep = nullptr, int32_t *zc_df = nullptr, const CiBatchStats *pre = nullptr,
-                   bool all_pairs = false, int64_t pair0 = 0);
+// One batch of n tests with d conditioning variables for CiLaunchDevice (filled by name).
+struct CiBatchReq {
+    const int32_t *items = nullptr;  // host copy [n][2 + d] (validated unless pre); null with all_pairs
+    int64_t n = 0;
+    int d = 0;
+    double alpha = 0.05;  // (the count-only callers, fbn_ci_counts / fbn_ci_debug_counts, leave it)
+    bool want_g2p = false;          // G^2 and p into c->g2 / c->p (else decisions only, through the band)
+    int32_t *counts_dev = nullptr;  // optional: test 0's table (every test's with c->counts_stride)
+    int k = 0;                      // the slot whose buffers and events the batch uses
+    // optional device-visible (pinned, mapped) host buffers the kernels read the items from and write
+    // the decisions to directly -- no staging copies for the small batches of a latency-bound round
+    const int32_t *zc_items = nullptr;
+    uint8_t *zc_indep = nullptr;
+    int32_t *zc_df = nullptr;
+    const CiBatchStats *pre = nullptr;  // the items' statistics, from a caller that generated them: no validation
+    bool all_pairs = false;  // no items: test t is pair pair0 + t of the complete graph (bit-sliced path only)
+    int64_t pair0 = 0;
+};
+int CiLaunchDevice(fbn_ci_ctx *c, const CiBatchReq &q, hipStream_t s);
 
 }  // namespace fbn
 

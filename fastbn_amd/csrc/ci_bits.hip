@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "ci_chisq.h"
+#include "fbn_device.h"
 #include "launchers.h"
 
 
@@ -377,6 +378,7 @@ __device__ __forceinline__ void pair_block(const uint32_t *__restrict__ bits, co
         for (int b = 0; b < BY; ++b) {
             const int x = xs[a], y = ys[b];
             const int u = x < y ? x : y, v = x < y ? y : x;
+            // (fbn_pair_index written out: through the helper this kernel's register allocation changes)
             const long long t = (long long)u * nvars - (long long)u * (u + 1) / 2 + (v - u - 1);
             if (!(a < nx && b < ny && x < y && t >= t0 && t < t1)) continue;  // wave-uniform
             const int32_t *cx = rowcnt + row0[x], *cy = rowcnt + row0[y];
@@ -459,7 +461,7 @@ __global__ __launch_bounds__(256) void ci_bits_count(const uint32_t *__restrict_
         const int32_t *nx = rowcnt + row0[x], *ny = rowcnt + row0[y];
         // level 0 of a PC run records every pair's table (pair index of x < y, 16 slots)
         int32_t *rec = (D == 0 && pairtab && x < y)
-                           ? pairtab + 16 * ((long long)x * nvars - (long long)x * (x + 1) / 2 + (y - x - 1))
+                           ? pairtab + 16 * fbn_pair_index(x, y, nvars)
                            : nullptr;
         switch (dx * 8 + dy) {
 #define FBN_PAIR(A, B)                                                             \
@@ -480,7 +482,7 @@ __global__ __launch_bounds__(256) void ci_bits_count(const uint32_t *__restrict_
 // level >= 1 of a PC run, one conditioning variable, pair tables recorded: derived counting
 __device__ __forceinline__ const int32_t *pair_table(const int32_t *pairtab, int nvars, int u, int v) {
     const int i = u < v ? u : v, j = u < v ? v : u;
-    return pairtab + 16 * ((long long)i * nvars - (long long)i * (i + 1) / 2 + (j - i - 1));
+    return pairtab + 16 * fbn_pair_index(i, j, nvars);
 }
 // XCD-contiguous work split: workgroups are dispatched round-robin over the 8 XCDs (block b on XCD
 // b % 8), each with its own L2.  Cutting the n units into 8 contiguous ranges, range j worked by
@@ -992,7 +994,7 @@ struct L1Edge {
 // orders above the rounding of either side: a few 1e-16 relative on values <= log 4.)
 __device__ __forceinline__ long long l1_pidx(int u, int v, int nv) {
     const int i = u < v ? u : v, j = u < v ? v : u;
-    return (long long)i * nv - (long long)i * (i + 1) / 2 + (j - i - 1);
+    return fbn_pair_index(i, j, nv);
 }
 // (in G^2 units: g2[pair] = 2N I of the pair's level-0 table; the margin 1e-9 nats = two_n * 1e-9)
 __device__ __forceinline__ bool l1_plausible(const double *__restrict__ g2, int nv, const int32_t *__restrict__ dims,
@@ -1388,9 +1390,6 @@ extern "C" size_t fbn_ci_l1_edge_bytes(void) { return sizeof(L1Edge); }
 // (lexicographic, as the host's vec_edges) and the CSR adjacency (each list ascending: the lower
 // neighbours, then the upper ones -- the order the host builds from the edge list).  One wave per
 // variable, 64 flags per step with a ballot.
-__device__ __forceinline__ long long kept_pidx(int i, int j, int n) {
-    return (long long)i * n - (long long)i * (i + 1) / 2 + (j - i - 1);
-}
 __global__ __launch_bounds__(256) void ci_kept_count(const uint8_t *__restrict__ indep, int n, int32_t *__restrict__ low,
                                                      int32_t *__restrict__ up) {
     const int lane = threadIdx.x & 63, v = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1398,11 +1397,11 @@ __global__ __launch_bounds__(256) void ci_kept_count(const uint8_t *__restrict__
     int lo = 0, hi = 0;
     for (int u0 = 0; u0 < v; u0 += 64) {
         const int u = u0 + lane;
-        lo += __popcll(__ballot(u < v && indep[kept_pidx(u, v, n)] == 0));
+        lo += __popcll(__ballot(u < v && indep[fbn_pair_index(u, v, n)] == 0));
     }
     for (int w0 = v + 1; w0 < n; w0 += 64) {
         const int w = w0 + lane;
-        hi += __popcll(__ballot(w < n && indep[kept_pidx(v, w, n)] == 0));
+        hi += __popcll(__ballot(w < n && indep[fbn_pair_index(v, w, n)] == 0));
     }
     if (lane == 0) low[v] = lo, up[v] = hi;
 }
@@ -1449,14 +1448,14 @@ __global__ __launch_bounds__(256) void ci_kept_fill(const uint8_t *__restrict__ 
     int r = off[v], q = upoff[v];
     for (int u0 = 0; u0 < v; u0 += 64) {
         const int u = u0 + lane;
-        const bool k = u < v && indep[kept_pidx(u, v, n)] == 0;
+        const bool k = u < v && indep[fbn_pair_index(u, v, n)] == 0;
         const unsigned long long m = __ballot(k);
         if (k) adj[r + __popcll(m & below)] = u;
         r += __popcll(m);
     }
     for (int w0 = v + 1; w0 < n; w0 += 64) {
         const int w = w0 + lane;
-        const bool k = w < n && indep[kept_pidx(v, w, n)] == 0;
+        const bool k = w < n && indep[fbn_pair_index(v, w, n)] == 0;
         const unsigned long long m = __ballot(k);
         if (k) {
             const int i = __popcll(m & below);
@@ -1513,33 +1512,25 @@ extern "C" hipError_t fbn_ci_kept_csr(const uint8_t *indep, int n, int32_t *low,
     return hipGetLastError();
 }
 
-// mi != nullptr: the information screen first over mi = every pair's level-0 G^2 (indexed by pair;
-// computed here from the pair tables when mi_from_tables), band for the level's alpha, two_n = 2N,
-// pcnt >= E ints, plist >= the level's candidate sets, sstat2 / scal2 a second tile-status array
-// (>= tiles) and 4 long longs)
-extern "C" hipError_t fbn_ci_l1_setup(const int32_t *pairs, int E, const int32_t *adj, const int32_t *adj_off,
-                                      void *ed, int32_t *pos, uint8_t *st, int32_t *sep, long long *counted,
-                                      int chunk0, int32_t *len, int32_t *off, unsigned *ring,
-                                      unsigned long long *sstat, long long cap, long long *scal, int num_cu,
-                                      const int32_t *pairtab, double *mi, int mi_from_tables, const int32_t *dims,
-                                      const double *band, int nband, int nv, double two_n, int32_t *pcnt,
-                                      int32_t *plist, unsigned long long *sstat2, long long *scal2, hipStream_t s) {
+// a->mi != nullptr: the information screen first (ci_args.h)
+extern "C" hipError_t fbn_ci_l1_setup(const CiL1Args *a, hipStream_t s) {
+    const int E = a->E, nv = a->nv;
     const int ntiles = (E + 255) / 256;
     if (E <= 0) return hipSuccess;
-    const unsigned gw = (unsigned)std::min((E + 3) / 4, num_cu * 8);  // one wave per edge
-    if (mi) {
+    const unsigned gw = (unsigned)std::min((E + 3) / 4, a->num_cu * 8);  // one wave per edge
+    if (a->mi) {
         const long long P = (long long)nv * (nv - 1) / 2, b = (P + 255) / 256;
-        if (mi_from_tables)
-            hipLaunchKernelGGL(ci_pair_g2, dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, pairtab, dims, nv, P, mi);
-        hipLaunchKernelGGL(ci_l1_screen_count, dim3(gw), dim3(256), 0, s, pairs, E, adj, adj_off, (const double *)mi,
-                           dims, band, nband, nv, two_n, pcnt);
+        if (a->mi_from_tables)
+            hipLaunchKernelGGL(ci_pair_g2, dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, a->pairtab, a->dims, nv, P, a->mi);
+        hipLaunchKernelGGL(ci_l1_screen_count, dim3(gw), dim3(256), 0, s, a->pairs, E, a->adj, a->adj_off,
+                           (const double *)a->mi, a->dims, a->band, a->nband, nv, a->two_n, a->pcnt);
     }
-    hipLaunchKernelGGL(ci_l1_setup, dim3((unsigned)std::min(ntiles, num_cu * 4)), dim3(256), 0, s, pairs, E, adj,
-                       adj_off, (L1Edge *)ed, pos, st, sep, counted, chunk0, len, off, ring, sstat, cap, scal,
-                       mi ? (const int32_t *)pcnt : nullptr, sstat2, scal2);
-    if (mi)
-        hipLaunchKernelGGL(ci_l1_screen_fill, dim3(gw), dim3(256), 0, s, (const L1Edge *)ed, E, adj, (const double *)mi,
-                           dims, band, nband, nv, two_n, plist);
+    hipLaunchKernelGGL(ci_l1_setup, dim3((unsigned)std::min(ntiles, a->num_cu * 4)), dim3(256), 0, s, a->pairs, E, a->adj,
+                       a->adj_off, (L1Edge *)a->ed, a->pos, a->st, a->sep, a->counted, a->chunk0, a->len, a->off, a->ring,
+                       a->sstat, a->cap, a->scal, a->mi ? (const int32_t *)a->pcnt : nullptr, a->sstat2, a->scal2);
+    if (a->mi)
+        hipLaunchKernelGGL(ci_l1_screen_fill, dim3(gw), dim3(256), 0, s, (const L1Edge *)a->ed, E, a->adj,
+                           (const double *)a->mi, a->dims, a->band, a->nband, nv, a->two_n, a->plist);
     return hipGetLastError();
 }
 
@@ -1547,36 +1538,34 @@ extern "C" hipError_t fbn_ci_l1_setup(const int32_t *pairs, int E, const int32_t
 // generation, counting, G^2 / decisions, resolution + the next round's lengths and offsets for
 // next_chunk; scal[0] = the round's test count (device), open_cnt += edges still open after it,
 // *open_next = 0; epoch = round + 2
-extern "C" hipError_t fbn_ci_l1_round(const uint32_t *bits, const int32_t *dims, const int32_t *row0, long long W,
-                                      const int32_t *adj, const int32_t *pairtab, int nvars, void *edv, int32_t *pos,
-                                      uint8_t *st, int32_t *sep, long long *counted, int32_t *len, int32_t *off,
-                                      int E, long long cap, long long *scal, int32_t *items, int32_t *counts,
-                                      int32_t *df, uint8_t *indep, double alpha, unsigned long long *stats,
-                                      const double *band, int nband, unsigned *open_cnt, int num_cu,
-                                      unsigned *open_next, int next_chunk, unsigned long long *sstat, unsigned epoch,
-                                      const int32_t *plist, hipStream_t s) {
-    const L1Edge *ed = (const L1Edge *)edv;
-    const long long gcap = (long long)num_cu * 8;
+extern "C" hipError_t fbn_ci_l1_round(const CiL1Args *a, unsigned *open_cnt, unsigned *open_next, int next_chunk,
+                                      unsigned epoch, hipStream_t s) {
+    const L1Edge *ed = (const L1Edge *)a->ed;
+    const int E = a->E;
+    const long long cap = a->cap;
+    const int32_t *plist = a->plist;
+    const long long gcap = (long long)a->num_cu * 8;
     const long long gt = (cap + 255) / 256;
     const dim3 gT((unsigned)(gt < gcap ? gt : gcap));
     const long long gw = (cap + 3) / 4;
     const dim3 gW((unsigned)(gw < gcap ? gw : gcap));
     const int ntiles = (E + 255) / 256;
-    const long long *total = scal;
-    unsigned long long *rows_read = reinterpret_cast<unsigned long long *>(scal + 2);
-    hipLaunchKernelGGL(ci_l1_gen, gT, dim3(256), 0, s, ed, pos, off, E, total, adj, items, dims, rows_read, plist);
-    hipLaunchKernelGGL(ci_bits_count_derived, gW, dim3(256), 0, s, bits, dims, row0, (const int32_t *)items, W, cap,
-                       counts, pairtab, nvars, 1, total);
+    const long long *total = a->scal;
+    unsigned long long *rows_read = reinterpret_cast<unsigned long long *>(a->scal + 2);
+    hipLaunchKernelGGL(ci_l1_gen, gT, dim3(256), 0, s, ed, a->pos, a->off, E, total, a->adj, a->items, a->dims, rows_read,
+                       plist);
+    hipLaunchKernelGGL(ci_bits_count_derived, gW, dim3(256), 0, s, a->bits, a->dims, a->row0, (const int32_t *)a->items,
+                       a->W, cap, a->counts, a->pairtab, a->nv, 1, total);
     // four lanes per test: the screened rounds are small (a few thousand to ~27k tests on config 5),
     // where the lane-per-test kernel's single latency chain per test dominated (config 5: 0.22 ->
     // 0.13 ms of G^2 per run)
     const long long gq = (cap + kG2TestsPerBlock - 1) / kG2TestsPerBlock;
-    hipLaunchKernelGGL(ci_bits_g2q<1>, dim3((unsigned)(gq < gcap ? gq : gcap)), dim3(256), 0, s, (const int32_t *)counts, dims, (const int32_t *)items, cap, alpha,
-                       (double *)nullptr, df, (double *)nullptr, indep, (int32_t *)nullptr, stats, nvars, 0ll, band,
-                       nband, total);
-    hipLaunchKernelGGL(ci_l1_resolve, dim3((unsigned)std::min(ntiles, num_cu * 4)), dim3(256), 0, s, ed, pos, len,
-                       off, st, sep, counted, (const uint8_t *)indep, (const int32_t *)items, E, open_cnt, open_next,
-                       next_chunk, sstat, epoch, cap, scal, plist);
+    hipLaunchKernelGGL(ci_bits_g2q<1>, dim3((unsigned)(gq < gcap ? gq : gcap)), dim3(256), 0, s, (const int32_t *)a->counts,
+                       a->dims, (const int32_t *)a->items, cap, a->alpha, (double *)nullptr, a->df, (double *)nullptr,
+                       a->indep, (int32_t *)nullptr, a->stats, a->nv, 0ll, a->band, a->nband, total);
+    hipLaunchKernelGGL(ci_l1_resolve, dim3((unsigned)std::min(ntiles, a->num_cu * 4)), dim3(256), 0, s, ed, a->pos, a->len,
+                       a->off, a->st, a->sep, a->counted, (const uint8_t *)a->indep, (const int32_t *)a->items, E, open_cnt,
+                       open_next, next_chunk, a->sstat, epoch, cap, a->scal, plist);
     return hipGetLastError();
 }
 
@@ -1601,33 +1590,31 @@ extern "C" hipError_t fbn_ci_gram_pairs(const int32_t *G, long long ld, const in
     return hipGetLastError();
 }
 
-extern "C" hipError_t fbn_ci_bits_launch(const uint32_t *bits, const int32_t *dims, const int32_t *row0,
-                                         const int32_t *items, long long W, long long n, int d, double alpha,
-                                         double *g2, int32_t *df, double *p, uint8_t *indep, int32_t *counts,
-                                         int32_t *counts0, unsigned long long *stats, const int32_t *rowcnt,
-                                         int32_t *pairtab, int pmode, int nvars, int num_cu, long long t0,
-                                         int counted, const double *band, int nband, hipStream_t s) {
-    const long long g1 = (n + 3) / 4, cap = (long long)num_cu * 8;
+extern "C" hipError_t fbn_ci_bits_launch(const CiBitsArgs *a, hipStream_t s) {
+    const long long n = a->n;
+    const long long g1 = (n + 3) / 4, cap = (long long)a->num_cu * 8;
     // launches too small to fill the chip with a lane per test (ALARM's 8.7k level-1 tests: 137
     // waves on 1024 SIMDs) take four lanes per test, which cuts each test's latency chain ~4x
     const bool quad = n <= kG2QuadMax;
     const long long g2g = quad ? (n + kG2TestsPerBlock - 1) / kG2TestsPerBlock : (n + 255) / 256;
     const dim3 b1((unsigned)(g1 < cap ? g1 : cap)), b2((unsigned)(g2g < cap ? g2g : cap));
-    if (d == 0) {
-        if (!counted)  // counted = 1: the counts are already in place (ci_bits_pairs_tiled)
-            hipLaunchKernelGGL(ci_bits_count<0>, b1, dim3(256), 0, s, bits, dims, row0, items, W, n, counts, rowcnt,
-                               pmode == 1 ? pairtab : nullptr, nvars, t0);
-        hipLaunchKernelGGL((quad ? ci_bits_g2q<0> : ci_bits_g2<0>), b2, dim3(256), 0, s, counts, dims, items, n,
-                           alpha, g2, df, p, indep, counts0, stats, nvars, t0, band, nband, (const long long *)nullptr);
-    } else if (d == 1) {
-        if (pmode == 2)  // (xcd = 1: the XCD-contiguous split of the items)
-            hipLaunchKernelGGL(ci_bits_count_derived, b1, dim3(256), 0, s, bits, dims, row0, items, W, n, counts,
-                               (const int32_t *)pairtab, nvars, 1, (const long long *)nullptr);
+    if (a->d == 0) {
+        if (!a->counted)  // counted = 1: the counts are already in place (ci_bits_pairs_tiled)
+            hipLaunchKernelGGL(ci_bits_count<0>, b1, dim3(256), 0, s, a->bits, a->dims, a->row0, a->items, a->W, n,
+                               a->counts, a->rowcnt, a->pmode == 1 ? a->pairtab : nullptr, a->nvars, a->t0);
+        hipLaunchKernelGGL((quad ? ci_bits_g2q<0> : ci_bits_g2<0>), b2, dim3(256), 0, s, a->counts, a->dims, a->items, n,
+                           a->alpha, a->g2, a->df, a->p, a->indep, a->counts0, a->stats, a->nvars, a->t0, a->band,
+                           a->nband, (const long long *)nullptr);
+    } else if (a->d == 1) {
+        if (a->pmode == 2)  // (xcd = 1: the XCD-contiguous split of the items)
+            hipLaunchKernelGGL(ci_bits_count_derived, b1, dim3(256), 0, s, a->bits, a->dims, a->row0, a->items, a->W, n,
+                               a->counts, (const int32_t *)a->pairtab, a->nvars, 1, (const long long *)nullptr);
         else
-            hipLaunchKernelGGL(ci_bits_count<1>, b1, dim3(256), 0, s, bits, dims, row0, items, W, n, counts, rowcnt,
-                               nullptr, nvars, 0ll);
-        hipLaunchKernelGGL((quad ? ci_bits_g2q<1> : ci_bits_g2<1>), b2, dim3(256), 0, s, counts, dims, items, n,
-                           alpha, g2, df, p, indep, counts0, stats, nvars, 0ll, band, nband, (const long long *)nullptr);
+            hipLaunchKernelGGL(ci_bits_count<1>, b1, dim3(256), 0, s, a->bits, a->dims, a->row0, a->items, a->W, n,
+                               a->counts, a->rowcnt, nullptr, a->nvars, 0ll);
+        hipLaunchKernelGGL((quad ? ci_bits_g2q<1> : ci_bits_g2<1>), b2, dim3(256), 0, s, a->counts, a->dims, a->items, n,
+                           a->alpha, a->g2, a->df, a->p, a->indep, a->counts0, a->stats, a->nvars, 0ll, a->band, a->nband,
+                           (const long long *)nullptr);
     } else {
         return hipErrorInvalidValue;
     }

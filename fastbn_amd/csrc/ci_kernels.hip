@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "ci_chisq.h"
+#include "fbn_device.h"
 #include "launchers.h"
 
 namespace {
@@ -41,50 +42,6 @@ __device__ __host__ inline int sub_lanes(int cells) {
     return cells <= 16 ? 0 : cells <= 256 ? 4 : cells <= 512 ? 2 : cells <= 4096 ? 1 : 0;
 }
 
-struct CiArgs {
-    const uint8_t *cols;  // [nvars][N]
-    const int32_t *dims;
-    const int32_t *items;  // [n][2+D]
-    long long N;
-    long long n;
-    double alpha;
-    double *g2;
-    int32_t *df;
-    double *p;
-    uint8_t *indep;
-    int32_t *counts;  // optional: histogram of item 0
-    int32_t *gscratch;  // non-null: tables too large for LDS live in global memory, one region per
-    long long gstride;  // workgroup of gstride ints (same layout as the LDS one)
-    // decision-margin log: [0] = min over tests of |p - alpha| as IEEE bits
-    // (non-negative doubles order like their bit patterns), [1] = #tests with |p - alpha| < 1e-9
-    unsigned long long *stats;
-    // non-null: count from the bit-sliced store instead (every variable of every test has <= 4
-    // states; all value rows of variable v start at row0[v], W words per row)
-    const uint32_t *bits;
-    const int32_t *row0;
-    long long W;
-    // decisions only (p == nullptr): [lo, hi] per df 1..nband then delta (ci_chisq.h fbn_chisq_band)
-    const double *band;
-    int nband;
-    // PK instantiation: the columns packed 2 bits per sample (every state count <= 4), 16 samples
-    // per word, PW words per variable (fbn_ci_pack2_build)
-    const uint32_t *pk;
-    long long PW;
-    // counts != nullptr: cstride == 0 -> the table of test 0 only; cstride > 0 -> every test's table
-    // at counts + test * cstride (fbn_ci_debug_counts)
-    long long cstride;
-    // split mode (small batches, MODE 1 / 2): test t's table at tab + t * tstride (zeroed), its
-    // packed words divided among `split` workgroups
-    int32_t *tab;
-    long long tstride;
-    int split;
-    // MODE 3 (d = 2, bit-sliced, derived): the pair tables of this PC run's level 0 (every pair u < v
-    // of the nvars variables, [value of u][value of v], ci_bits.hip pair_table)
-    const int32_t *pairtab;
-    int nvars;
-    int dbg;  // diagnostic ablations, 0 from every launcher: bit 0 = MODE 3 skips its counting
-};
-
 // ---- MODE 3: tests with two conditioning variables (z1, z2), every state count <= 4, from the
 // bit-sliced store, counting only LEADING cells (values 0 .. d-2 of each variable; the masks of a
 // variable partition the samples, so the last value of any variable follows by subtraction):
@@ -101,7 +58,7 @@ struct CiArgs {
 __device__ __forceinline__ int pair_at(const int32_t *__restrict__ pairtab, int nvars, const int32_t *__restrict__ dims,
                                        int u, int a, int v, int b) {
     const int i = u < v ? u : v, j = u < v ? v : u;
-    const int32_t *T = pairtab + 16 * ((long long)i * nvars - (long long)i * (i + 1) / 2 + (j - i - 1));
+    const int32_t *T = pairtab + 16 * fbn_pair_index(i, j, nvars);
     return u < v ? T[a * dims[v] + b] : T[b * dims[u] + a];
 }
 
@@ -782,25 +739,19 @@ extern "C" size_t fbn_ci_lds_bytes(int dimz, int dx, int dy) {
 // instantiation, rounded up): a launch needs both within the 160 KiB of a workgroup
 extern "C" size_t fbn_ci_static_lds_bytes() { return 512; }
 
-extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, const int32_t *items, long long N,
-                                    long long n, int d, double alpha, double *g2, int32_t *df, double *p,
-                                    uint8_t *indep, int32_t *counts, size_t lds_bytes, int grid,
-                                    int32_t *gscratch, unsigned long long *stats, const uint32_t *bits,
-                                    const int32_t *row0, long long W, const double *band, int nband,
-                                    const uint32_t *pk, long long PW, long long cstride, int32_t *tab,
-                                    long long tstride, int split, int split_grid, const int32_t *pairtab, int nvars,
+extern "C" hipError_t fbn_ci_launch(const CiArgs *args, int d, size_t lds_bytes, int grid, int split_grid,
                                     hipStream_t stream) {
-    CiArgs a{cols, dims, items, N, n, alpha, g2, df, p, indep, counts, gscratch, (long long)(lds_bytes / 4 + 1) & ~1ll,
-             stats, bits, row0, W, band, nband, pk, PW, cstride, tab, tstride, split, pairtab, nvars,
-             /*debug word*/ 0};
-    if (gscratch) lds_bytes = 0;
-    if (pairtab && bits && d == 2) {  // MODE 3: derived bit-sliced counting (every state count <= 4)
+    CiArgs a = *args;
+    a.gstride = (long long)(lds_bytes / 4 + 1) & ~1ll;
+    a.dbg = 0;
+    if (a.gscratch) lds_bytes = 0;
+    if (a.pairtab && a.bits && d == 2) {  // MODE 3: derived bit-sliced counting (every state count <= 4)
         // registers for 3 waves per SIMD (config-5 level 2: 0.47 / 0.42 / 0.49 ms at 2 / 3 / 4 waves)
         hipLaunchKernelGGL((ci_g2_kernel<2, true, false, 256, 4>), dim3(grid), dim3(256), lds_bytes, stream, a);
         return hipGetLastError();
     }
-    if (split > 1 && pk && !bits && !gscratch) {  // small batch: count in parts, then decide
-        hipError_t e = hipMemsetAsync(tab, 0, (size_t)n * tstride * 4, stream);
+    if (a.split > 1 && a.pk && !a.bits && !a.gscratch) {  // small batch: count in parts, then decide
+        hipError_t e = hipMemsetAsync(a.tab, 0, (size_t)a.n * a.tstride * 4, stream);
         if (e != hipSuccess) return e;
         switch (d) {
 #define FBN_CI_SPLIT_CASE(DD)                                                                                 \
@@ -826,17 +777,17 @@ extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, co
     // batches of at most kWideTests tests (deep PC levels: a few hundred tests or fewer, one
     // workgroup per test on part of the chip): 16 waves per test instead of 4, so each test's
     // sample loop and epilogue have 4x the waves to hide latency
-    const bool wide = n <= kWideTests;
+    const bool wide = a.n <= kWideTests;
     switch (d) {
 #define FBN_CI_CASE(DD)                                                                              \
     case DD:                                                                                         \
-        if (bits && DD >= 2)                                                                         \
+        if (a.bits && DD >= 2)                                                                       \
             hipLaunchKernelGGL((ci_g2_kernel<DD, true>), dim3(grid), dim3(256), lds_bytes, stream, a);  \
-        else if (wide && pk)                                                                         \
+        else if (wide && a.pk)                                                                       \
             hipLaunchKernelGGL((ci_g2_kernel<DD, false, true, 1024>), dim3(grid), dim3(1024), lds_bytes, stream, a); \
         else if (wide)                                                                               \
             hipLaunchKernelGGL((ci_g2_kernel<DD, false, false, 1024>), dim3(grid), dim3(1024), lds_bytes, stream, a); \
-        else if (pk)                                                                                 \
+        else if (a.pk)                                                                               \
             hipLaunchKernelGGL((ci_g2_kernel<DD, false, true>), dim3(grid), dim3(256), lds_bytes, stream, a); \
         else                                                                                         \
             hipLaunchKernelGGL((ci_g2_kernel<DD, false>), dim3(grid), dim3(256), lds_bytes, stream, a); \

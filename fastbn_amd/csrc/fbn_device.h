@@ -20,6 +20,12 @@
         if (e_ != hipSuccess) return fbn::SetError(FBN_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
+// the index of pair (i < j) among the n (n - 1) / 2 pairs of n variables in lexicographic order, for
+// the kernels and their callers (the host-only twin with its inverse: fbn::PairIndex, pc_internal.h)
+__host__ __device__ inline long long fbn_pair_index(int i, int j, int n) {
+    return (long long)i * n - (long long)i * (i + 1) / 2 + (j - i - 1);
+}
+
 namespace fbn {
 
 // growable device buffer

@@ -19,22 +19,6 @@
 
 namespace {
 
-struct JtArgs {
-    const JtOp *ops;
-    const int32_t *aux;
-    const double *initv;
-    const uint64_t *dig;
-    const int8_t *evid;  // [ncases][V]
-    double *marg;        // [ncases][SD]
-    int32_t *labels;     // [ncases]
-    double *ws;          // [grid][NE][64]
-    int32_t *wsi;        // [grid][nc][64]
-    long long ncases;
-    long long NE;
-    int nops, V, SD, nc;
-    int vmajor;  // marginals variable-major [SD][ncases] (fbn_jt_set_output_layout)
-};
-
 // one case's marginal outputs: a case-major row (vs = 1) or a column stride of the variable-major
 // layout (vs = ncases); value d of the output at index k is o[d] of `out + k`
 struct MOut {
@@ -333,16 +317,8 @@ __global__ __launch_bounds__(64) void jt_interp_kernel(JtArgs A) {
 // LDS-resident variant: the clique in flight is held in LDS ([entry][64 lanes], rows >= cap spill
 // to a per-wave global buffer), its pending denominator in a register.  HBM sees each clique table
 // once when parked after Collect and once when reloaded in Distribute, plus the separator messages.
-struct JtLParams {
-    long long ncases;
-    long long wave_entries;  // store + nc + sep + spill
-    long long store_off, den_off, sep_off, spill_off;
-    int nops, V, SD, nc, cap;
-    int force_exact;  // ablation/testing: always take the IEEE division path
-    int vmajor;        // marginals variable-major [SD][ncases]
-    const int *flags;  // fixup mode (non-null): only the blocks the specialized kernel flagged
-};
-
+// (JtLParams, jt_program.h, is the kernel's by-value scalar block.)
+//
 // Pointers are separate __restrict__ kernel arguments (not a struct): the compiler can then prove
 // that the program arrays are never written and turns their wave-uniform reads into SMEM loads.
 // the clique in flight: LDS rows [0, cap), spilled rows in per-wave global memory
@@ -623,69 +599,30 @@ __global__ __launch_bounds__(64) void jt_lds_kernel(const JtOp *__restrict__ ops
 
 }  // namespace
 
-extern "C" hipError_t fbn_jt_lds_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
-                                        const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
-                                        double *marg, int32_t *labels, double *ws, int32_t *wsi, long long wave_entries,
-                                        long long store_off, long long den_off, long long sep_off,
-                                        long long spill_off, int nc, int cap, bool spill, int force_exact,
-                                        const int *flags, int grid, unsigned long long *prof, int vmajor,
-                                        hipStream_t stream) {
-    JtLParams a;
-    a.force_exact = force_exact;
-    a.vmajor = vmajor;
-    a.flags = flags;
-    a.ncases = ncases;
-    a.wave_entries = wave_entries;
-    a.store_off = store_off;
-    a.den_off = den_off;
-    a.sep_off = sep_off;
-    a.spill_off = spill_off;
-    a.nops = nops;
-    a.V = V;
-    a.SD = SD;
-    a.nc = nc;
-    a.cap = cap;
-    const size_t lds = (size_t)cap * 64 * sizeof(double);
-    if (prof) {
-        if (spill)
-            hipLaunchKernelGGL((jt_lds_kernel<true, true>), dim3(grid), dim3(64), lds, stream, ops, aux, initv, dig,
-                               evid, marg, labels, ws, wsi, a, prof);
+extern "C" hipError_t fbn_jt_lds_launch(const JtLdsArgs *l, hipStream_t stream) {
+    const JtLParams &a = l->par;
+    const int grid = l->grid;
+    const size_t lds = (size_t)a.cap * 64 * sizeof(double);
+    if (l->prof) {
+        if (l->spill)
+            hipLaunchKernelGGL((jt_lds_kernel<true, true>), dim3(grid), dim3(64), lds, stream, l->ops, l->aux, l->initv,
+                               l->dig, l->evid, l->marg, l->labels, l->ws, l->wsi, a, l->prof);
         else
-            hipLaunchKernelGGL((jt_lds_kernel<false, true>), dim3(grid), dim3(64), lds, stream, ops, aux, initv, dig,
-                               evid, marg, labels, ws, wsi, a, prof);
-    } else if (spill) {
-        hipLaunchKernelGGL((jt_lds_kernel<true, false>), dim3(grid), dim3(64), lds, stream, ops, aux, initv, dig,
-                           evid, marg, labels, ws, wsi, a, nullptr);
+            hipLaunchKernelGGL((jt_lds_kernel<false, true>), dim3(grid), dim3(64), lds, stream, l->ops, l->aux, l->initv,
+                               l->dig, l->evid, l->marg, l->labels, l->ws, l->wsi, a, l->prof);
+    } else if (l->spill) {
+        hipLaunchKernelGGL((jt_lds_kernel<true, false>), dim3(grid), dim3(64), lds, stream, l->ops, l->aux, l->initv,
+                           l->dig, l->evid, l->marg, l->labels, l->ws, l->wsi, a, nullptr);
     } else {
-        hipLaunchKernelGGL((jt_lds_kernel<false, false>), dim3(grid), dim3(64), lds, stream, ops, aux, initv, dig,
-                           evid, marg, labels, ws, wsi, a, nullptr);
+        hipLaunchKernelGGL((jt_lds_kernel<false, false>), dim3(grid), dim3(64), lds, stream, l->ops, l->aux, l->initv,
+                           l->dig, l->evid, l->marg, l->labels, l->ws, l->wsi, a, nullptr);
     }
     return hipGetLastError();
 }
 
 // launch wrapper (called from capi_jt.hip)
-extern "C" hipError_t fbn_jt_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
-                                    const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
-                                    double *marg, int32_t *labels, double *ws, int32_t *wsi, long long NE, int nc,
-                                    int grid, int vmajor, hipStream_t stream) {
-    JtArgs a;
-    a.vmajor = vmajor;
-    a.ops = ops;
-    a.aux = aux;
-    a.initv = initv;
-    a.dig = dig;
-    a.evid = evid;
-    a.marg = marg;
-    a.labels = labels;
-    a.ws = ws;
-    a.wsi = wsi;
-    a.ncases = ncases;
-    a.NE = NE;
-    a.nops = nops;
-    a.V = V;
-    a.SD = SD;
-    a.nc = nc;
-    hipLaunchKernelGGL(jt_interp_kernel, dim3(grid), dim3(64), 0, stream, a);
+extern "C" hipError_t fbn_jt_launch(const JtArgs *a, int grid, hipStream_t stream) {
+    hipLaunchKernelGGL(jt_interp_kernel, dim3(grid), dim3(64), 0, stream, *a);
     return hipGetLastError();
 }
 

@@ -60,6 +60,53 @@ struct JtOp {
 
 #define JT_MAX_DIG_WORDS 4  // 8 variables per 64-bit word -> at most 32 variables per table
 
+// ---- what the two interpreters' launchers take (launchers.h), filled by name in capi_jt.hip.
+// JtArgs is jt_interp_kernel's by-value parameter: its layout is the kernarg layout.
+struct JtArgs {
+    const JtOp *ops;
+    const int32_t *aux;
+    const double *initv;
+    const uint64_t *dig;
+    const int8_t *evid;  // [ncases][V]
+    double *marg;        // [ncases][SD]
+    int32_t *labels;     // [ncases]
+    double *ws;          // [grid][NE][64]
+    int32_t *wsi;        // [grid][nc][64]
+    long long ncases;
+    long long NE;
+    int nops, V, SD, nc;
+    int vmajor;  // marginals variable-major [SD][ncases] (fbn_jt_set_output_layout)
+};
+
+// jt_lds_kernel's by-value scalars (kernarg layout)
+struct JtLParams {
+    long long ncases;
+    long long wave_entries;  // store + nc + sep + spill
+    long long store_off, den_off, sep_off, spill_off;
+    int nops, V, SD, nc, cap;
+    int force_exact;  // ablation/testing: always take the IEEE division path
+    int vmajor;        // marginals variable-major [SD][ncases]
+    const int *flags;  // fixup mode (non-null): only the blocks the specialized kernel flagged
+};
+
+// host-only: fbn_jt_lds_launch's arguments.  The pointers reach the kernel as separate __restrict__
+// arguments (jt_kernels.hip says why); the dynamic LDS is par.cap rows of 64 doubles.
+struct JtLdsArgs {
+    JtLParams par;
+    const JtOp *ops;
+    const int32_t *aux;
+    const double *initv;
+    const uint64_t *dig;
+    const int8_t *evid;
+    double *marg;
+    int32_t *labels;
+    double *ws;
+    int32_t *wsi;
+    bool spill;  // rows >= par.cap of the clique in flight live in the per-wave global buffer
+    int grid;
+    unsigned long long *prof;  // non-null: the diagnostic instantiation, cycles per op type [grid][16]
+};
+
 // ---- streamed ("virtual table") variant, jt_virt.hip: clique tables are never stored.  Every
 // pass over a clique recomputes each entry from its initial potential, the case's evidence mask,
 // the messages already received and the normalization denominators of the earlier steps:

@@ -1,32 +1,28 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits.hip,
 // ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip) and by every caller (capi_*.hip), so a
-// definition that disagrees with its declaration does not compile.  Internal to libfastbn.  (pc_small.h and param_counts.h carry
-// their own kernels' launchers.)
+// definition that disagrees with its declaration does not compile.  A launcher with many arguments
+// takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiL1Args),
+// jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
+// Internal to libfastbn.  (pc_small.h and param_counts.h carry their own kernels' launchers.)
 #ifndef FBN_LAUNCHERS_H
 #define FBN_LAUNCHERS_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ci_args.h"
 #include "jt_program.h"
 #include "lbp_model.h"
 
-extern "C" hipError_t fbn_jt_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
-                                    const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
-                                    double *marg, int32_t *labels, double *ws, int32_t *wsi, long long NE, int nc,
-                                    int grid, int vmajor, hipStream_t stream);
+extern "C" hipError_t fbn_jt_launch(const JtArgs *a, int grid, hipStream_t stream);
 extern "C" hipError_t fbn_jt_marg_transpose(const double *in, double *out, long long n, int SD, hipStream_t s);
 extern "C" hipError_t fbn_jt_score_terms(const double *marg, const double *golden, long long n, int SD, int vmajor,
                                          const int32_t *dom, int V, double *terms, hipStream_t s);
-extern "C" hipError_t fbn_ci_launch(const uint8_t *cols, const int32_t *dims, const int32_t *items, long long N,
-                                    long long n, int d, double alpha, double *g2, int32_t *df, double *p,
-                                    uint8_t *indep, int32_t *counts, size_t lds_bytes, int grid,
-                                    int32_t *gscratch, unsigned long long *stats, const uint32_t *bits,
-                                    const int32_t *row0, long long W, const double *band, int nband,
-                                    const uint32_t *pk, long long PW, long long cstride, int32_t *tab,
-                                    long long tstride, int split, int split_grid, const int32_t *pairtab,
-                                    int nvars, hipStream_t stream);
+// a->gstride is derived from lds_bytes here (the caller leaves it 0); split_grid: the counting launch
+// of the split mode (a->split > 1)
+extern "C" hipError_t fbn_ci_launch(const CiArgs *a, int d, size_t lds_bytes, int grid, int split_grid,
+                                    hipStream_t stream);
 extern "C" hipError_t fbn_ci_pack2_build(const uint8_t *cols, int nvars, long long N, long long PW, uint32_t *pk,
                                          hipStream_t stream);
 extern "C" size_t fbn_ci_lds_bytes(int dimz, int dx, int dy);
@@ -37,12 +33,7 @@ extern "C" hipError_t fbn_ci_cols_check(const uint8_t *cols, const int32_t *dims
                                         hipStream_t s);
 extern "C" hipError_t fbn_ci_bits_build(const uint8_t *cols, const int32_t *dims, const int32_t *row0, long long N,
                                         long long W, int nvars, uint32_t *bits, hipStream_t s);
-extern "C" hipError_t fbn_ci_bits_launch(const uint32_t *bits, const int32_t *dims, const int32_t *row0,
-                                         const int32_t *items, long long W, long long n, int d, double alpha,
-                                         double *g2, int32_t *df, double *p, uint8_t *indep, int32_t *counts,
-                                         int32_t *counts0, unsigned long long *stats, const int32_t *rowcnt,
-                                         int32_t *pairtab, int pmode, int nvars, int num_cu, long long t0,
-                                         int counted, const double *band, int nband, hipStream_t s);
+extern "C" hipError_t fbn_ci_bits_launch(const CiBitsArgs *a, hipStream_t s);
 extern "C" hipError_t fbn_ci_bits_rowcount(const uint32_t *bits, long long rows, long long W, int32_t *rowcnt,
                                            hipStream_t s);
 extern "C" int fbn_ci_pair_block(int d);
@@ -59,21 +50,9 @@ extern "C" hipError_t fbn_ci_l1_results(const uint8_t *st, const int32_t *sep, c
                                         long long *part, hipStream_t s);
 extern "C" hipError_t fbn_ci_kept_csr(const uint8_t *indep, int n, int32_t *low, int32_t *up, int32_t *off,
                                       int32_t *upoff, int32_t *adj, int32_t *pairs, long long *scal, hipStream_t s);
-extern "C" hipError_t fbn_ci_l1_setup(const int32_t *pairs, int E, const int32_t *adj, const int32_t *adj_off,
-                                      void *ed, int32_t *pos, uint8_t *st, int32_t *sep, long long *counted,
-                                      int chunk0, int32_t *len, int32_t *off, unsigned *ring,
-                                      unsigned long long *sstat, long long cap, long long *scal, int num_cu,
-                                      const int32_t *pairtab, double *mi, int mi_from_tables, const int32_t *dims,
-                                      const double *band, int nband, int nv, double two_n, int32_t *pcnt,
-                                      int32_t *plist, unsigned long long *sstat2, long long *scal2, hipStream_t s);
-extern "C" hipError_t fbn_ci_l1_round(const uint32_t *bits, const int32_t *dims, const int32_t *row0, long long W,
-                                      const int32_t *adj, const int32_t *pairtab, int nvars, void *edv, int32_t *pos,
-                                      uint8_t *st, int32_t *sep, long long *counted, int32_t *len, int32_t *off,
-                                      int E, long long cap, long long *scal, int32_t *items, int32_t *counts,
-                                      int32_t *df, uint8_t *indep, double alpha, unsigned long long *stats,
-                                      const double *band, int nband, unsigned *open_cnt, int num_cu,
-                                      unsigned *open_next, int next_chunk, unsigned long long *sstat, unsigned epoch,
-                                      const int32_t *plist, hipStream_t s);
+extern "C" hipError_t fbn_ci_l1_setup(const CiL1Args *a, hipStream_t s);
+extern "C" hipError_t fbn_ci_l1_round(const CiL1Args *a, unsigned *open_cnt, unsigned *open_next, int next_chunk,
+                                      unsigned epoch, hipStream_t s);
 extern "C" hipError_t fbn_ci_gram(const uint32_t *bits, long long W, const int32_t *rl, const int32_t *tasks,
                                   long long ntasks, int32_t *out, int num_cu, hipStream_t s);
 extern "C" hipError_t fbn_ci_gram_pairs(const int32_t *G, long long ld, const int32_t *lead0, const int32_t *dims,
@@ -94,13 +73,7 @@ extern "C" hipError_t fbn_jt_virt_launch(const JtVClique *cls, const int32_t *au
                                          double *ws, int32_t *wsi, int *flags, long long ncases, long long store_rows,
                                          long long scratch_row, long long scratch_rows, int nc, int V, int SD,
                                          int grid, int dbg, hipStream_t stream);
-extern "C" hipError_t fbn_jt_lds_launch(const JtOp *ops, int nops, const int32_t *aux, const double *initv,
-                                        const uint64_t *dig, const int8_t *evid, int V, long long ncases, int SD,
-                                        double *marg, int32_t *labels, double *ws, int32_t *wsi, long long wave_entries,
-                                        long long store_off, long long den_off, long long sep_off,
-                                        long long spill_off, int nc, int cap, bool spill, int force_exact,
-                                        const int *flags, int grid, unsigned long long *prof, int vmajor,
-                                        hipStream_t stream);
+extern "C" hipError_t fbn_jt_lds_launch(const JtLdsArgs *a, hipStream_t stream);
 // lds != 0: the messages in lds_bytes of LDS per workgroup; else in a->ws, 3 * a->M doubles per workgroup
 extern "C" hipError_t fbn_lbp_launch(const fbn::LbpDeviceArgs *a, int lds, size_t lds_bytes, int grid,
                                      hipStream_t stream);

@@ -277,9 +277,7 @@ int fbn_pc_dist_run(fbn_pc_dist *s, fbn_ci_ctx *c, int32_t *record) {
     const size_t b = (size_t)s->cuts[s->rank], e = (size_t)s->cuts[s->rank + 1];
     if (s->d == 0 && s->implicit0) {
         // the range of the implicit complete graph: all-pairs batches straight into the flags
-        const int32_t *dims = fbn::CiCtxDims(c);
-        fbn::CiBatchStats st{0, 0};
-        for (int v = 0; v < nv; ++v) st.dim_rows += (int64_t)(nv - 1) * dims[v], st.maxdim = std::max(st.maxdim, (int)dims[v]);
+        const fbn::CiBatchStats st = fbn::CiAllPairsStats(fbn::CiCtxDims(c), nv);
         if (fbn::CiAllPairsEligible(c, st)) {
             std::vector<uint8_t> rm(e - b);
             const int64_t chunk = std::max<int64_t>(1, fbn::KnobOr("FBN_PC_L0CHUNK", (int64_t)1 << 22));
@@ -323,7 +321,7 @@ int fbn_pc_dist_pairs_chunk(const fbn_pc_dist *s, int64_t *pairs_per_rank) {
     if (!s || !pairs_per_rank) return SetError(FBN_ERR_ARG, "null pointer");
     if (s->world == 0) return SetError(FBN_ERR_ARG, "no level in progress (fbn_pc_dist_level)");
     // 0 = nothing to exchange: this rank's level 0 recorded no pair tables (the bit-sliced path was
-    // not eligible -- > 4 states, < 4096 samples, FBN_CI_NO_BITS -- or FBN_CI_NO_PAIRS); that depends
+    // not eligible, CiBitsEligible, or FBN_CI_NO_PAIRS is set); that depends
     // only on the dataset and the environment, so every rank of a run agrees
     if (!s->pairs || s->d != 0 || !s->ran || !s->ctx || !fbn::CiPairsRecorded(s->ctx)) {
         *pairs_per_rank = 0;

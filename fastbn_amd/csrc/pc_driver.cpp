@@ -134,7 +134,7 @@ int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::ve
         CiCtxShape(ctx, &nv, &ns);
         CiBatchStats st0{0, 0};
         if (e_begin == 0 && (int64_t)E == (int64_t)nv * (nv - 1) / 2 && edges.size() == E) {
-            for (int v = 0; v < nv; ++v) st0.dim_rows += (int64_t)(nv - 1) * dims[v], st0.maxdim = std::max(st0.maxdim, (int)dims[v]);
+            st0 = CiAllPairsStats(dims, nv);
         } else {
             for (size_t e = e_begin; e < e_end; ++e) {
                 const int a = dims[edges[e].first], b = dims[edges[e].second];
@@ -440,9 +440,7 @@ int RunPCStable(fbn_ci_ctx *ctx, double alpha, int depth, int group_size, PCResu
     CiSetPairMode(ctx, pairs ? 1 : 0);
     // level 0 over the implicit complete graph (the kernels decode pair indices): no edge list or
     // adjacency of the complete graph is built; the kept pairs become the skeleton directly
-    const int32_t *dims = CiCtxDims(ctx);
-    CiBatchStats st_all{0, 0};
-    for (int v = 0; v < n; ++v) st_all.dim_rows += (int64_t)(n - 1) * dims[v], st_all.maxdim = std::max(st_all.maxdim, (int)dims[v]);
+    const CiBatchStats st_all = CiAllPairsStats(CiCtxDims(ctx), n);
     int d0 = 0;
     bool small_done = false;  // the device-resident search ran (all levels, or the first ones)
     int small_levels = 0;

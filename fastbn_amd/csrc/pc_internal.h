@@ -15,6 +15,19 @@
 
 namespace fbn {
 
+// the complete graph's pairs (i < j) of n variables in lexicographic order: the index of a pair, and
+// the row i of pair index t (its inverse: the largest i with PairIndex(i, i + 1, n) <= t)
+inline int64_t PairIndex(int64_t i, int64_t j, int64_t n) { return i * n - i * (i + 1) / 2 + (j - i - 1); }
+inline int PairRow(int64_t t, int n) {
+    int64_t lo = 0, hi = n - 2;
+    while (lo < hi) {
+        const int64_t m = (lo + hi + 1) / 2;
+        if (PairIndex(m, m + 1, n) <= t) lo = m;
+        else hi = m - 1;
+    }
+    return (int)lo;
+}
+
 // sepsets keyed by (min, max), flat: keys, (offset, length) into one int pool.  Appended per level,
 // sorted once on first lookup / iteration (a node-based map cost ~40 ms, a vector of vectors ~3 ms,
 // of host time for the ~500k marginal removals of a 1000-variable run)
@@ -150,7 +163,7 @@ class SepsetMap {
     bool l0_hit(std::pair<int, int> key) const {
         const int i = key.first, j = key.second;
         return !l0_.empty() && 0 <= i && i < j && j < n0_ &&
-               l0_[(size_t)i * n0_ - (size_t)i * (i + 1) / 2 + (size_t)(j - i - 1)];
+               l0_[(size_t)PairIndex(i, j, n0_)];
     }
     void sort() const {
         if (sorted_) return;
@@ -205,6 +218,12 @@ struct CiBatchStats {
     int maxdim;
     int64_t dim_rows;
 };
+// of every pair of the complete graph over nv variables: each variable is in nv - 1 pairs
+inline CiBatchStats CiAllPairsStats(const int32_t *dims, int nv) {
+    CiBatchStats st{0, 0};
+    for (int v = 0; v < nv; ++v) st.dim_rows += (int64_t)(nv - 1) * dims[v], st.maxdim = std::max(st.maxdim, (int)dims[v]);
+    return st;
+}
 int CiBatchLaunch(fbn_ci_ctx *c, int k, const int32_t *items, int64_t n, int d, double alpha, bool want_df,
                   const CiBatchStats *pre = nullptr);
 const int32_t *CiCtxDims(const fbn_ci_ctx *c);  // state count per variable
@@ -212,6 +231,9 @@ const int32_t *CiCtxDims(const fbn_ci_ctx *c);  // state count per variable
 // slot 0 with no item array (the kernels decode the pair); only when eligible for the bit-sliced
 // path (st = the batch's statistics)
 bool CiAllPairsEligible(const fbn_ci_ctx *c, const CiBatchStats &st);
+// the rule of the bit-sliced path (capi_ci.hip), beside the batch's d <= 1: every state count <= 4,
+// enough samples or FBN_CI_FORCE_BITS, not FBN_CI_NO_BITS (the knobs are read per call)
+bool CiBitsEligible(const fbn_ci_ctx *c, int maxdim);
 // pairs [t0, t0 + n) of that order (one rank's range of a distributed level 0)
 int CiBatchLaunchAllPairs(fbn_ci_ctx *c, double alpha, const CiBatchStats *pre, int64_t t0, int64_t n,
                           bool copy_flags = true);
