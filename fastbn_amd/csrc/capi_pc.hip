@@ -33,25 +33,23 @@ int fbn_pc_stable(fbn_ci_ctx *c, double alpha, int depth, int group_size, fbn_pc
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
     FBN_HIP(hipSetDevice(c->device));
     const bool timing = fbn::PcTiming();  // diagnostic
-    auto t0 = std::chrono::steady_clock::now();
+    using fbn::Clock;
+    using fbn::Ms;
+    auto t0 = Clock::now();
     int rc;
     // the device-resident search (small graphs) sets the ctx's margin log itself (and resets it when
     // it falls back to the host levels)
     if (!fbn::CiPCSmallEligible(c, group_size) && (rc = fbn::CiResetMargin(c))) return rc;
-    auto t1 = std::chrono::steady_clock::now();
+    auto t1 = Clock::now();
     if ((rc = fbn::RunPCStable(c, alpha, depth, group_size, r->r))) return rc;
-    auto t2 = std::chrono::steady_clock::now();
+    auto t2 = Clock::now();
     // the run's work is all on the ctx stream
     if (!r->r.margin_done && (rc = fbn::CiReadMargin(c, &r->r.min_margin, &r->r.near_alpha, true))) return rc;
-    auto t3 = std::chrono::steady_clock::now();
+    auto t3 = Clock::now();
     if ((rc = fbn::OrientPC(c->nvars, r->r))) return rc;  // StructLearnByPCStable steps 2-3
-    if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-            return std::chrono::duration<double, std::milli>(b - a).count();
-        };
+    if (timing)
         fprintf(stderr, "pc_stable: margin reset %.2f ms, skeleton %.2f ms, margin read %.2f ms, orientation %.2f ms\n",
-                ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, std::chrono::steady_clock::now()));
-    }
+                Ms(t0, t1), Ms(t1, t2), Ms(t2, t3), Ms(t3, Clock::now()));
     *out = r.release();
     return FBN_OK;
 }
@@ -138,20 +136,21 @@ int fbn_pc_level(fbn_ci_ctx *c, double alpha, int d, int group_size, const int32
     if (!c || d < 0 || d > 8 || group_size < 1 || group_size > 8 || nedges < 0 || (nedges && !edges) ||
         e_begin < 0 || e_end < e_begin || e_end > nedges || (e_end > e_begin && !removed))
         return SetError(FBN_ERR_ARG, "bad argument");
-    std::vector<std::pair<int, int>> ev((size_t)nedges);
-    std::vector<std::vector<int>> adj(c->nvars);
+    fbn::Skeleton sk;
+    sk.Reset(c->nvars);
+    auto &ev = sk.edges;
+    ev.resize((size_t)nedges);
     for (int64_t i = 0; i < nedges; ++i) {
         const int a = edges[2 * i], b = edges[2 * i + 1];
         if (a < 0 || b <= a || b >= c->nvars) return SetError(FBN_ERR_ARG, "edge %lld must be (x < y) in range", (long long)i);
         if (i && !(ev[i - 1] < std::make_pair(a, b))) return SetError(FBN_ERR_ARG, "edges must be in (x, y) lexicographic order");
         ev[i] = {a, b};
-        adj[a].push_back(b);  // lexicographic edges: every list comes out sorted (no sort pass)
-        adj[b].push_back(a);
     }
+    sk.RebuildAdj(false);
     FBN_HIP(hipSetDevice(c->device));
     fbn::PCResultHost scratch;
     fbn::LevelOut out;
-    int rc = fbn::RunLevel(c, alpha, d, group_size, adj, ev, (size_t)e_begin, (size_t)e_end, out, scratch);
+    int rc = fbn::RunLevel(c, alpha, d, group_size, sk, (size_t)e_begin, (size_t)e_end, out, scratch);
     if (rc) return rc;
     for (int64_t e = 0; e < e_end - e_begin; ++e) {
         removed[e] = out.removed[e] ? 1 : 0;
@@ -368,21 +367,14 @@ int CiL0L1Device(fbn_ci_ctx *c, int64_t P, int *E, int64_t *cands, PCResultHost 
     return FBN_OK;
 }
 
-int CiL0L1Host(fbn_ci_ctx *c, int64_t P, int E, std::vector<char> &removed, std::vector<std::pair<int, int>> &edges,
-               std::vector<std::vector<int>> &adj) {
+int CiL0L1Host(fbn_ci_ctx *c, int64_t P, int E, std::vector<char> &removed, Skeleton &sk) {
     FBN_HIP(hipEventSynchronize(c->side_ev));
     removed.resize((size_t)P);
     memcpy(removed.data(), c->slot[0].h_res, (size_t)P);
     static_assert(sizeof(std::pair<int, int>) == 8, "pair layout");
-    edges.resize((size_t)E);
-    if (E) memcpy(static_cast<void *>(edges.data()), c->h_pairs, (size_t)E * 8);
-    const int n = c->nvars;
-    {
-        std::vector<int> deg(n, 0);
-        for (auto &e : edges) ++deg[e.first], ++deg[e.second];
-        for (int v = 0; v < n; ++v) adj[v].reserve(deg[v]);
-    }
-    for (auto &e : edges) adj[e.first].push_back(e.second), adj[e.second].push_back(e.first);
+    sk.edges.resize((size_t)E);
+    if (E) memcpy(static_cast<void *>(sk.edges.data()), c->h_pairs, (size_t)E * 8);
+    sk.RebuildAdj(true);
     return FBN_OK;
 }
 int CiPairTablesCopy(fbn_ci_ctx *c, int64_t p0, int64_t np, void *buf, bool buf_on_device, bool to_ctx) {
@@ -426,8 +418,7 @@ void CiSetPairsRecorded(fbn_ci_ctx *c) {
 // r & 1, the host reads round r - 1's entry while round r runs).  The per-edge chunk is clamped so
 // a round's exclusive scan of the lengths (int32 offsets, hipcub) cannot overflow: E * chunk < 2^31.
 constexpr int kL1Ring = 2;
-int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<int>> &adj,
-                   const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, LevelOut &out,
+int CiLevel1Device(fbn_ci_ctx *c, double alpha, const Skeleton &sk, size_t e_begin, size_t e_end, LevelOut &out,
                    PCResultHost &res, bool *done) {
     *done = false;
     if (c->pair_mode != 2 || !c->pairs_recorded || !c->bits_ready || fbn::KnobSet("FBN_PC_HOST_L1")) return FBN_OK;
@@ -436,7 +427,7 @@ int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<in
         if (c->dims[v] > 4) return FBN_OK;
     const int E = (int)(e_end - e_begin);
     int64_t cands = 0;  // every candidate set of the range: the most one round could hold
-    for (size_t e = e_begin; e < e_end; ++e) cands += adj[edges[e].first].size() + adj[edges[e].second].size() - 2;
+    for (size_t e = e_begin; e < e_end; ++e) cands += sk.EdgeCost(e, 1);
     // a level the host driver takes in one round (full speculation, ALARM-size) stays there: one
     // launch instead of a round's seven
     if (cands <= fbn::KnobOr("FBN_PC_FULLSPEC", 16384)) return FBN_OK;
@@ -446,7 +437,7 @@ int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<in
         return FBN_OK;
     }
     const bool ptiming = fbn::PcTiming();  // diagnostic
-    auto tq0 = std::chrono::steady_clock::now();
+    auto tq0 = Clock::now();
     FBN_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     int rc;
@@ -455,19 +446,18 @@ int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<in
     adj_off.assign(nv + 1, 0);
     for (int u = 0; u < nv; ++u) {
         adj_off[u] = (int32_t)adjf.size();
-        adjf.insert(adjf.end(), adj[u].begin(), adj[u].end());
+        adjf.insert(adjf.end(), sk.adj[u].begin(), sk.adj[u].end());
     }
     adj_off[nv] = (int32_t)adjf.size();
     if ((rc = c->l1pairs.ensure((size_t)E * 8)) || (rc = c->l1adj.ensure(std::max<size_t>(adjf.size(), 1) * 4)) ||
         (rc = c->l1adjoff.ensure((size_t)(nv + 1) * 4)))
         return rc;
     static_assert(sizeof(std::pair<int, int>) == 8, "pair layout");
-    FBN_HIP(hipMemcpyAsync(c->l1pairs.p, edges.data() + e_begin, (size_t)E * 8, hipMemcpyHostToDevice, s));
+    FBN_HIP(hipMemcpyAsync(c->l1pairs.p, sk.edges.data() + e_begin, (size_t)E * 8, hipMemcpyHostToDevice, s));
     if (!adjf.empty()) FBN_HIP(hipMemcpyAsync(c->l1adj.p, adjf.data(), adjf.size() * 4, hipMemcpyHostToDevice, s));
     FBN_HIP(hipMemcpyAsync(c->l1adjoff.p, adj_off.data(), (size_t)(nv + 1) * 4, hipMemcpyHostToDevice, s));
     if (ptiming)
-        fprintf(stderr, "  level 1 device setup (host): %.3f ms\n",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count());
+        fprintf(stderr, "  level 1 device setup (host): %.3f ms\n", Ms(tq0, Clock::now()));
     *done = true;
     return CiLevel1Run(c, alpha, E, cands, out, res, nullptr);
 }
@@ -555,7 +545,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     hipError_t e = fbn_ci_l1_setup(&a, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "ci level-1 setup: %s", hipGetErrorString(e));
     const bool l1timing = fbn::PcTiming();  // diagnostic
-    const auto tl0 = std::chrono::steady_clock::now();
+    const auto tl0 = Clock::now();
     int rounds = 0;
     for (int r = 0;; ++r) {
         rounds = r + 1;
@@ -574,7 +564,7 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
         chunk = next_chunk;
     }
     if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
-    const auto tl1 = std::chrono::steady_clock::now();
+    const auto tl1 = Clock::now();
     // results straight into one pinned buffer by a kernel (zero-copy writes; no DMA copies):
     // [scalars 32 | sepsets 4E | removal flags E]
     if ((rc = PinnedEnsure(c->h_xfer, c->h_xfer_bytes, (size_t)E * 5 + 40))) return rc;
@@ -593,9 +583,8 @@ int CiLevel1Run(fbn_ci_ctx *c, double alpha, int E, int64_t cands, LevelOut &out
     out.counted = sc[0];
     out.launched = sc[1];
     if (l1timing)
-        fprintf(stderr, "  level 1 device rounds: %d, loop %.3f ms, read-back + results %.3f ms\n", rounds,
-                std::chrono::duration<double, std::milli>(tl1 - tl0).count(),
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl1).count());
+        fprintf(stderr, "  level 1 device rounds: %d, loop %.3f ms, read-back + results %.3f ms\n", rounds, Ms(tl0, tl1),
+                Ms(tl1, Clock::now()));
     if (c->timing) {
         float ms = 0.f;
         FBN_HIP(hipEventElapsedTime(&ms, S.ev0, S.ev1));
@@ -691,13 +680,13 @@ bool CiPCSmallEligible(const fbn_ci_ctx *c, int group_size) {
     return PCSmallShape(c->nvars, c->N, c->dims.data(), group_size);
 }
 
-int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::vector<std::pair<int, int>> &edges,
-              std::vector<std::vector<int>> &adj, int *levels, bool *handoff, bool *fellback) {
+int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, Skeleton &sk, int *levels, bool *handoff,
+              bool *fellback) {
     *levels = 0;
     *handoff = false;
     *fellback = false;
     const bool htime = fbn::PcTiming();  // diagnostic: host phases of the call
-    const auto h0 = std::chrono::steady_clock::now();
+    const auto h0 = Clock::now();
     FBN_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     int rc;
@@ -781,7 +770,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
         trace_host.assign(tb / 8, 0);
     }
     CiSlot &S = c->slot[0];
-    const auto h1 = std::chrono::steady_clock::now();
+    const auto h1 = Clock::now();
     if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
     // FBN_PC_SMALL_FAIL (test knob): "launch" = treat the launch as refused, "timeout" = a barrier
     // limit of one tick, so the first level's barrier times out in the kernel itself
@@ -803,7 +792,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
         }
     }
     if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
-    const auto h2 = std::chrono::steady_clock::now();
+    const auto h2 = Clock::now();
     // wait for the kernel's completion word (written after the record) instead of a stream sync;
     // a stream sync only for the events / trace, or when the word does not come (fault, hang)
     {
@@ -818,7 +807,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
         }
         if (!got || c->timing || trace) FBN_HIP(hipStreamSynchronize(s));
     }
-    const auto h3 = std::chrono::steady_clock::now();
+    const auto h3 = Clock::now();
     if (trace) {
         FBN_HIP(hipMemcpy(trace_host.data(), trace_dev.p, trace_host.size() * 8, hipMemcpyDeviceToHost));
         h_trace = trace_host.data();
@@ -896,13 +885,11 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
         res.device_bytes += out->launched[d] * (int64_t)(d + 2) * ((c->N + 3) / 4);
         for (int v = 0; v < n; ++v) prev[v] = out->adj[d][v];
     }
-    edges.clear();
+    sk.Reset(n);
     for (int x = 0; x < n; ++x)
         for (int y = x + 1; y < n; ++y)
-            if ((prev[x] >> y) & 1ull) edges.push_back({x, y});
-    adj.assign(n, {});
-    for (auto &e : edges) adj[e.first].push_back(e.second), adj[e.second].push_back(e.first);
-    for (auto &l : adj) std::sort(l.begin(), l.end());
+            if ((prev[x] >> y) & 1ull) sk.edges.push_back({x, y});
+    sk.RebuildAdj(false);  // (x then y ascending = lexicographic: the lists come out sorted)
     *levels = L;
     *handoff = out->handoff != 0;
     if (!*handoff) {
@@ -912,14 +899,9 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::ve
         res.near_alpha = (int64_t)out->near;
         res.margin_done = true;
     }
-    if (htime) {
-        const auto h4 = std::chrono::steady_clock::now();
-        auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-            return std::chrono::duration<double, std::micro>(b - a).count();
-        };
+    if (htime)
         fprintf(stderr, "pc small host: set-up %.1f us, launch %.1f us, wait %.1f us, record -> result %.1f us\n",
-                us(h0, h1), us(h1, h2), us(h2, h3), us(h3, h4));
-    }
+                Us(h0, h1), Us(h1, h2), Us(h2, h3), Us(h3, Clock::now()));
     return FBN_OK;
 }
 }  // namespace fbn

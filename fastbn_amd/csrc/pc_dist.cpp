@@ -17,7 +17,6 @@
 //                       test counts, removals (src/PCStable.cpp:131-147, 310-326), FreeDegree stop.
 // Nothing per edge crosses the C-ABI except inside the records; no Python loops per edge.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -36,11 +35,10 @@ struct fbn_pc_dist {
     int depth = 1000, group_size = 1;
     int d = 0;
     bool done = false;
-    // level 0 works on the implicit complete graph (pair index = edge index): edges / adj are built
+    // level 0 works on the implicit complete graph (pair index = edge index): the skeleton is built
     // from the kept pairs after it (or materialized on demand: Complete())
     bool implicit0 = true;
-    std::vector<std::pair<int, int>> edges;
-    std::vector<std::vector<int>> adj;
+    fbn::Skeleton sk;
     fbn::PCResultHost res;
     // the current level's partition (valid after fbn_pc_dist_level)
     int world = 0, rank = 0;
@@ -53,11 +51,7 @@ struct fbn_pc_dist {
                                 // the last fbn_pc_dist_apply, which snapshots its margin log
     // the last applied level's sepsets (d >= 1), appended to the store while the next level's first
     // batches run (RunLevel's deferred hook) instead of on the exchange's critical path
-    bool pending = false;
-    int pend_d = 0;
-    std::vector<std::pair<int, int>> pend_keys;  // the level's edges before its removals
-    std::vector<char> pend_rm;
-    std::vector<int> pend_sep;
+    fbn::PendingSepsets pend;
     double wall_s = 0.0;
     bool margin_taken = false;
     double min_margin = 0.0;
@@ -67,16 +61,6 @@ struct fbn_pc_dist {
 namespace {
 
 constexpr int kHdr = 8;  // record header: d, n, counted (2), launched (2), kernel us (2)
-
-int64_t Binom(int64_t m, int k) {
-    if (k < 0 || m < k) return 0;
-    int64_t r = 1;
-    for (int i = 1; i <= k; ++i) {
-        r = r * (m - k + i) / i;
-        if (r > (int64_t)1 << 40) return (int64_t)1 << 40;
-    }
-    return r;
-}
 
 void Put64(int32_t *p, int64_t v) { memcpy(p, &v, 8); }
 
@@ -110,32 +94,16 @@ int64_t Get64(const int32_t *p) {
     return v;
 }
 
-// the complete graph's edge list and adjacency (GenerateUndirectedCompleteGraph order,
-// src/Network.cpp:346-358), only when a level-0 path needs them explicitly
+// the complete graph's edge list and adjacency, only when a level-0 path needs them explicitly
 void Complete(fbn_pc_dist *s) {
     if (!s->implicit0) return;
-    const int n = s->nvars;
-    s->edges.clear();
-    s->edges.reserve((size_t)n * (n - 1) / 2);
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j) s->edges.push_back({i, j});
-    s->adj.assign(n, {});
-    for (int i = 0; i < n; ++i) {
-        s->adj[i].reserve(n - 1);
-        for (int j = 0; j < n; ++j)
-            if (i != j) s->adj[i].push_back(j);
-    }
+    s->sk.SetComplete(s->nvars);
     s->implicit0 = false;
 }
-void FlushSepsets(fbn_pc_dist *s) {
-    if (!s->pending) return;
-    s->res.sepset.append_level(s->pend_keys.data(), s->pend_rm.data(), s->pend_sep.data(), s->pend_keys.size(),
-                               s->pend_d);
-    s->pending = false;
-}
+void FlushSepsets(fbn_pc_dist *s) { s->pend.Flush(s->res.sepset); }
 
 int64_t NumEdges(const fbn_pc_dist *s) {
-    return s->d == 0 && s->implicit0 ? (int64_t)s->nvars * (s->nvars - 1) / 2 : (int64_t)s->edges.size();
+    return s->d == 0 && s->implicit0 ? (int64_t)s->nvars * (s->nvars - 1) / 2 : (int64_t)s->sk.edges.size();
 }
 
 int Partition(fbn_pc_dist *s, int world) {
@@ -149,11 +117,8 @@ int Partition(fbn_pc_dist *s, int world) {
         for (int r = 1; r < world; ++r) s->cuts[r] = std::min<int64_t>(E, r * chunk);
     } else {
         std::vector<double> cum((size_t)E + 1, 0.0);
-        for (int64_t e = 0; e < E; ++e) {
-            const auto &ed = s->edges[(size_t)e];
-            cum[e + 1] = cum[e] + (double)Binom((int64_t)s->adj[ed.first].size() - 1, s->d) +
-                         (double)Binom((int64_t)s->adj[ed.second].size() - 1, s->d) + 1.0;
-        }
+        // (integers: the sums are exact while the total stays below 2^53)
+        for (int64_t e = 0; e < E; ++e) cum[e + 1] = cum[e] + (double)s->sk.EdgeCost((size_t)e, s->d) + 1.0;
         for (int r = 1; r < world; ++r) {
             const double target = cum[E] * r / world;
             s->cuts[r] = std::lower_bound(cum.begin(), cum.end(), target) - cum.begin();
@@ -215,7 +180,7 @@ int fbn_pc_dist_create(int nvars, double alpha, int depth, int group_size, fbn_p
     s->depth = depth;
     s->group_size = group_size;
     s->pairs = !fbn::KnobSet("FBN_CI_NO_PAIRS");
-    s->adj.assign(nvars, {});
+    s->sk.Reset(nvars);
     *out = s.release();
     return FBN_OK;
 }
@@ -254,7 +219,7 @@ int fbn_pc_dist_edges(const fbn_pc_dist *s, int32_t *pairs, int64_t cap) {
             for (int j = i + 1; j < s->nvars && k < n; ++j, ++k) pairs[2 * k] = i, pairs[2 * k + 1] = j;
         return FBN_OK;
     }
-    for (int64_t i = 0; i < n; ++i) pairs[2 * i] = s->edges[i].first, pairs[2 * i + 1] = s->edges[i].second;
+    for (int64_t i = 0; i < n; ++i) pairs[2 * i] = s->sk.edges[i].first, pairs[2 * i + 1] = s->sk.edges[i].second;
     return FBN_OK;
 }
 
@@ -265,7 +230,7 @@ int fbn_pc_dist_run(fbn_pc_dist *s, fbn_ci_ctx *c, int32_t *record) {
     int64_t ns = 0;
     fbn::CiCtxShape(c, &nv, &ns);
     if (nv != s->nvars) return SetError(FBN_ERR_ARG, "context has %d variables, the session %d", nv, s->nvars);
-    auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = fbn::Clock::now();
     int rc;
     if (s->d == 0) {
         if ((rc = fbn::CiMarginReset(c))) return rc;
@@ -280,30 +245,23 @@ int fbn_pc_dist_run(fbn_pc_dist *s, fbn_ci_ctx *c, int32_t *record) {
         const fbn::CiBatchStats st = fbn::CiAllPairsStats(fbn::CiCtxDims(c), nv);
         if (fbn::CiAllPairsEligible(c, st)) {
             std::vector<uint8_t> rm(e - b);
-            const int64_t chunk = std::max<int64_t>(1, fbn::KnobOr("FBN_PC_L0CHUNK", (int64_t)1 << 22));
-            for (int64_t t0 = (int64_t)b; t0 < (int64_t)e; t0 += chunk) {
-                const int64_t m = std::min<int64_t>(chunk, (int64_t)e - t0);
-                if ((rc = fbn::CiBatchLaunchAllPairs(c, s->alpha, &st, t0, m))) return rc;
-                if ((rc = fbn::CiBatchWait(c, 0, rm.data() + (t0 - (int64_t)b), nullptr, scratch))) return rc;
-            }
+            if ((rc = fbn::RunImplicitLevel0(c, s->alpha, st, (int64_t)b, (int64_t)e, rm.data(), nullptr, scratch))) return rc;
             s->res.kernel_s += scratch.kernel_s;
             s->res.device_bytes += scratch.device_bytes;
             rc = Pack(s, rm.data(), nullptr, (int64_t)(e - b), (int64_t)(e - b), scratch.kernel_s, record);
-            s->wall_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            s->wall_s += std::chrono::duration<double>(fbn::Clock::now() - t0).count();
             return rc;
         }
         Complete(s);
     }
-    std::function<void()> deferred;
-    if (s->pending) deferred = [s]() { FlushSepsets(s); };
-    rc = fbn::RunLevel(c, s->alpha, s->d, s->group_size, s->adj, s->edges, b, e, out, scratch, &deferred);
+    rc = fbn::RunLevel(c, s->alpha, s->d, s->group_size, s->sk, b, e, out, scratch, [s]() { FlushSepsets(s); });
     FlushSepsets(s);
     if (rc) return rc;
     s->res.kernel_s += scratch.kernel_s;
     s->res.device_bytes += scratch.device_bytes;
     std::vector<uint8_t> rm(out.removed.begin(), out.removed.end());
     rc = Pack(s, rm.data(), out.sep.data(), out.counted, out.launched, scratch.kernel_s, record);
-    s->wall_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    s->wall_s += std::chrono::duration<double>(fbn::Clock::now() - t0).count();
     return rc;
 }
 
@@ -354,7 +312,7 @@ int fbn_pc_dist_pairs_import(fbn_pc_dist *s, fbn_ci_ctx *c, const void *buf, int
 int fbn_pc_dist_apply(fbn_pc_dist *s, const int32_t *records, int *more) {
     if (!s || !records) return SetError(FBN_ERR_ARG, "null pointer");
     if (s->done || s->world == 0) return SetError(FBN_ERR_ARG, "no level in progress (fbn_pc_dist_level)");
-    auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = fbn::Clock::now();
     const int d = s->d, world = s->world;
     const size_t E = (size_t)NumEdges(s);
     std::vector<char> rm(E, 0);
@@ -412,46 +370,40 @@ int fbn_pc_dist_apply(fbn_pc_dist *s, const int32_t *records, int *more) {
         }
     }
     const bool timing = fbn::PcTiming();
-    auto ta = std::chrono::steady_clock::now();
+    const auto ta = fbn::Clock::now();
     FlushSepsets(s);
     if (d == 0) s->res.sepset.set_level0(s->nvars, std::move(rm));  // edges = the complete graph (flags taken over)
-    else s->pend_keys.assign(s->edges.begin(), s->edges.end());  // sepsets: FlushSepsets, below or next run
+    else s->pend.keys.assign(s->sk.edges.begin(), s->sk.edges.end());  // sepsets: FlushSepsets, below or next run
     s->res.tests_per_level.push_back(counted);
     s->res.launched_per_level.push_back(launched);
     if (d == 0) {  // the kept pairs of the complete graph, in pair order, become the skeleton
         const int n = s->nvars;
-        s->edges.resize(kept.size());
+        auto &edges = s->sk.edges;
+        edges.resize(kept.size());
         int i = 0;
         int64_t row0 = 0, row1 = n - 1;  // pair indices of row i: [row0, row1)
         for (size_t t = 0; t < kept.size(); ++t) {
             while (kept[t] >= row1) ++i, row0 = row1, row1 += n - 1 - i;
-            s->edges[t] = {i, i + 1 + (int)(kept[t] - row0)};
+            edges[t] = {i, i + 1 + (int)(kept[t] - row0)};
         }
-        // adjacency sized from the degrees first: one allocation per list instead of a doubling
-        // chain of them (~0.2 ms for the ~30k kept pairs of a 1000-variable run)
-        std::vector<int> deg(n, 0);
-        for (auto &ed : s->edges) ++deg[ed.first], ++deg[ed.second];
-        s->adj.resize(n);
-        for (int v = 0; v < n; ++v) s->adj[v].clear(), s->adj[v].reserve(deg[v]);
-        for (auto &ed : s->edges) s->adj[ed.first].push_back(ed.second), s->adj[ed.second].push_back(ed.first);
+        s->sk.RebuildAdj(true);
         s->implicit0 = false;
         if (timing)
-            fprintf(stderr, "pc dist apply level 0: records %.3f ms, skeleton %.3f ms\n",
-                    std::chrono::duration<double, std::milli>(ta - t0).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count());
+            fprintf(stderr, "pc dist apply level 0: records %.3f ms, skeleton %.3f ms\n", fbn::Ms(t0, ta),
+                    fbn::Ms(ta, fbn::Clock::now()));
     } else {
-        fbn::ApplyRemovals(rm, s->edges, s->adj);
-        s->pend_rm = std::move(rm);
-        s->pend_sep = std::move(sep);
-        s->pend_d = d;
-        s->pending = true;
+        s->sk.ApplyRemovals(rm);
+        s->pend.rm = std::move(rm);
+        s->pend.sep = std::move(sep);
+        s->pend.d = d;
+        s->pend.armed = true;
     }
     if (d == 0 && s->ctx) {
         // level 1 derives from pair tables only if every pair's table is in the ctx
         if (world == 1 && s->pairs) fbn::CiSetPairMode(s->ctx, 2);
         else if (!s->pairs_imported) fbn::CiSetPairMode(s->ctx, 0);
     }
-    const bool cont = d + 1 < s->depth && (d == 0 || fbn::ContinueAfter(s->adj, d));
+    const bool cont = d + 1 < s->depth && (d == 0 || s->sk.ContinueAfter(d));
     if (cont) ++s->d;
     else s->done = true, FlushSepsets(s);
     if (!cont && s->ctx) {
@@ -467,7 +419,7 @@ int fbn_pc_dist_apply(fbn_pc_dist *s, const int32_t *records, int *more) {
     s->world = 0;
     s->ran = false;
     if (more) *more = cont ? 1 : 0;
-    s->wall_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    s->wall_s += std::chrono::duration<double>(fbn::Clock::now() - t0).count();
     return FBN_OK;
 }
 
@@ -478,7 +430,7 @@ int fbn_pc_dist_result(fbn_pc_dist *s, fbn_pc_result **out) {
     auto r = std::unique_ptr<fbn_pc_result>(new (std::nothrow) fbn_pc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
     r->r = s->res;
-    r->r.edges = s->edges;
+    r->r.edges = s->sk.edges;
     r->r.total_s = s->wall_s;
     if (s->margin_taken) r->r.min_margin = s->min_margin, r->r.near_alpha = s->near_alpha;  // this rank's tests
     int rc = fbn::OrientPC(s->nvars, r->r);

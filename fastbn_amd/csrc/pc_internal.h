@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -14,6 +15,11 @@
 #include "../../include/fastbn.h"
 
 namespace fbn {
+
+// host phase times of the FBN_PC_TIMING prints
+using Clock = std::chrono::steady_clock;
+inline double Ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+inline double Us(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
 
 // the complete graph's pairs (i < j) of n variables in lexicographic order: the index of a pair, and
 // the row i of pair index t (its inverse: the largest i with PairIndex(i, i + 1, n) <= t)
@@ -27,6 +33,76 @@ inline int PairRow(int64_t t, int n) {
     }
     return (int)lo;
 }
+
+inline int64_t Binom(int64_t m, int k) {  // C(m, k), saturating at 2^40
+    if (k < 0 || m < k) return 0;
+    int64_t r = 1;
+    for (int i = 1; i <= k; ++i) {
+        r = r * (m - k + i) / i;
+        if (r > (int64_t)1 << 40) return (int64_t)1 << 40;
+    }
+    return r;
+}
+
+// the skeleton: the edge list and its adjacency lists, stated once for the driver, the multi-GPU
+// session, the device seam (capi_pc.hip) and the level search
+struct Skeleton {
+    std::vector<std::pair<int, int>> edges;  // (x < y), lexicographic = vec_edges order
+    std::vector<std::vector<int>> adj;       // sorted
+    // no edges over n variables; the edge list and every adjacency list keep their capacity (a run of
+    // config 5 otherwise allocates ~1,000 adjacency vectors before level 1: ~0.05 ms)
+    void Reset(int n) {
+        edges.clear();
+        if ((int)adj.size() > n) adj.resize(n);
+        for (auto &a : adj) a.clear();
+        adj.resize(n);
+    }
+    // the complete graph (GenerateUndirectedCompleteGraph order, src/Network.cpp:346-358)
+    void SetComplete(int n) {
+        Reset(n);
+        edges.reserve((size_t)n * (n - 1) / 2);
+        for (int i = 0; i < n; ++i)
+            for (int j = i + 1; j < n; ++j) edges.push_back({i, j});
+        for (int i = 0; i < n; ++i) {
+            adj[i].reserve(n - 1);
+            for (int j = 0; j < n; ++j)
+                if (i != j) adj[i].push_back(j);
+        }
+    }
+    // adj from edges in O(E).  The edges are in (x < y) lexicographic order, so every list comes out
+    // sorted with no sort pass: v's lower neighbours u arrive from the edges (u, v), ascending in u and
+    // all before the edges (v, w), which bring its upper neighbours ascending in w.
+    // reserve_by_degree: one allocation per list instead of a doubling chain of them (~0.2 ms for the
+    // ~30k kept pairs of a 1000-variable run's level 0)
+    void RebuildAdj(bool reserve_by_degree) {
+        for (auto &a : adj) a.clear();
+        if (reserve_by_degree) {
+            std::vector<int> deg(adj.size(), 0);
+            for (auto &e : edges) ++deg[e.first], ++deg[e.second];
+            for (size_t v = 0; v < adj.size(); ++v) adj[v].reserve(deg[v]);
+        }
+        for (auto &e : edges) adj[e.first].push_back(e.second), adj[e.second].push_back(e.first);
+    }
+    // removals after a level, in vec_edges order (src/PCStable.cpp:310-326): the edge list is compacted
+    // in place (no second edge array) and the lists rebuilt from the kept edges, instead of erasing
+    // element by element (the reference's O(E^2) hot spot)
+    void ApplyRemovals(const std::vector<char> &rm) {
+        size_t w = 0;
+        for (size_t e = 0; e < edges.size(); ++e)
+            if (!rm[e]) edges[w++] = edges[e];
+        edges.resize(w);
+        RebuildAdj(false);
+    }
+    bool ContinueAfter(int d) const {  // FreeDegree > d (src/PCStable.cpp:557-563)
+        size_t maxdeg = 0;
+        for (auto &a : adj) maxdeg = std::max(maxdeg, a.size());
+        return (int64_t)maxdeg - 1 > d;
+    }
+    // the candidate sets of edge e at level d: C(|adj x| - 1, d) + C(|adj y| - 1, d)
+    int64_t EdgeCost(size_t e, int d) const {
+        return Binom((int64_t)adj[edges[e].first].size() - 1, d) + Binom((int64_t)adj[edges[e].second].size() - 1, d);
+    }
+};
 
 // sepsets keyed by (min, max), flat: keys, (offset, length) into one int pool.  Appended per level,
 // sorted once on first lookup / iteration (a node-based map cost ~40 ms, a vector of vectors ~3 ms,
@@ -205,6 +281,21 @@ struct PCResultHost {
     int path = 0;
 };
 
+// a level's removals, recorded in the sepset store while the next level's first batches run (only
+// the orientation reads them) instead of on the critical path
+struct PendingSepsets {
+    std::vector<std::pair<int, int>> keys;  // the level's edges before its removals
+    std::vector<char> rm;
+    std::vector<int> sep;
+    int d = 0;
+    bool armed = false;
+    void Flush(SepsetMap &m) {
+        if (!armed) return;
+        m.append_level(keys.data(), rm.data(), sep.data(), keys.size(), d);
+        armed = false;
+    }
+};
+
 void CiCtxShape(const fbn_ci_ctx *c, int *nvars, int64_t *nsamples);
 // run n tests of size d on the device; indep[n] (and df[n] if non-null) come back to the host;
 // accumulates kernel time into res.kernel_s
@@ -252,15 +343,15 @@ int CiBatchWait(fbn_ci_ctx *c, int k, uint8_t *indep, int32_t *df, PCResultHost 
 int RunPCStable(fbn_ci_ctx *ctx, double alpha, int depth, int group_size, PCResultHost &res);
 // The skeleton search of a small graph (<= 64 variables, every state count <= 4, group size 1) in
 // ONE device launch (pc_small.hip).  Levels [0, *levels) land in res (tests and launched per level,
-// sepsets) and edges / adj hold the skeleton after them; *handoff: a level the kernel does not take
+// sepsets) and sk holds the skeleton after them; *handoff: a level the kernel does not take
 // (d > 4 or > 2^22 candidate sets) follows, and the host driver continues at level *levels.  When
 // the search ended on the device res.min_margin / near_alpha hold its decision-margin log.
 bool CiPCSmallEligible(const fbn_ci_ctx *c, int group_size);
 bool PCSmallShape(int nvars, int64_t N, const int32_t *dims, int group_size);  // (the same rule, from the shape)
-// *fellback: the launch was refused or a grid barrier timed out; res / edges / adj untouched and the
+// *fellback: the launch was refused or a grid barrier timed out; res / sk untouched and the
 // ctx's margin log reset, the caller runs the host-driven levels from level 0
-int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, std::vector<std::pair<int, int>> &edges,
-              std::vector<std::vector<int>> &adj, int *levels, bool *handoff, bool *fellback);
+int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, Skeleton &sk, int *levels, bool *handoff,
+              bool *fellback);
 // one level for an edge range (the unit a multi-GPU driver partitions), see pc_driver.cpp
 struct LevelOut {
     std::vector<char> removed;
@@ -272,8 +363,7 @@ struct LevelOut {
 // order, compacted on the device (capi_pc.hip)
 int CiAllPairsKept(fbn_ci_ctx *c, int64_t t0, int64_t P, std::vector<std::pair<int, int>> &kept);
 // a PC run's level 1 (group size 1) on the device (capi_pc.hip); *done = false: not eligible
-int CiLevel1Device(fbn_ci_ctx *c, double alpha, const std::vector<std::vector<int>> &adj,
-                   const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, LevelOut &out,
+int CiLevel1Device(fbn_ci_ctx *c, double alpha, const Skeleton &sk, size_t e_begin, size_t e_end, LevelOut &out,
                    PCResultHost &res, bool *done);
 // the level-1 rounds over an edge list / adjacency already on the device (capi_pc.hip); host_work runs
 // once while the first round is on the device
@@ -289,17 +379,18 @@ bool CiPairsReady(const fbn_ci_ctx *c);
 // *E and *cands (the level's candidate sets); the decision flags and the edge list are copied to
 // pinned host memory on a side stream (CiL0L1Host waits for them); accounts the level-0 batch in res
 int CiL0L1Device(fbn_ci_ctx *c, int64_t P, int *E, int64_t *cands, PCResultHost &res);
-// the host's copies: removed[P] (level-0 decisions), edges (lexicographic) and adj
-int CiL0L1Host(fbn_ci_ctx *c, int64_t P, int E, std::vector<char> &removed, std::vector<std::pair<int, int>> &edges,
-               std::vector<std::vector<int>> &adj);
-// deferred (optional): host work run once while the level's first batches are on the device
-int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const std::vector<std::vector<int>> &adj,
-             const std::vector<std::pair<int, int>> &edges, size_t e_begin, size_t e_end, LevelOut &out,
-             PCResultHost &res, std::function<void()> *deferred = nullptr);
-// removals after a level in vec_edges order + adjacency rebuild; FreeDegree > d (pc_driver.cpp)
-void ApplyRemovals(const std::vector<char> &rm, std::vector<std::pair<int, int>> &edges,
-                   std::vector<std::vector<int>> &adj);
-bool ContinueAfter(const std::vector<std::vector<int>> &adj, int d);
+// the host's copies: removed[P] (level-0 decisions) and the skeleton (edges lexicographic)
+int CiL0L1Host(fbn_ci_ctx *c, int64_t P, int E, std::vector<char> &removed, Skeleton &sk);
+// Level 0 over pairs [t0, t1) of the implicit complete graph (pair index = edge index; only when
+// CiAllPairsEligible) in batches of at most FBN_PC_L0CHUNK pairs (per-test count records: 256 B each;
+// a 10k-variable graph has 5e7 pairs): the decisions land in flags[0 .. t1 - t0); kept (optional): the
+// kept pairs of each batch appended, compacted on the device.  ms (optional): += launch + wait, kept pairs
+int RunImplicitLevel0(fbn_ci_ctx *ctx, double alpha, const CiBatchStats &st, int64_t t0, int64_t t1, uint8_t *flags,
+                      std::vector<std::pair<int, int>> *kept, PCResultHost &res, double *ms = nullptr);
+// edges [e_begin, e_end) of sk at level d (pc_driver.cpp); deferred (optional): host work run once
+// while the level's first batches are on the device
+int RunLevel(fbn_ci_ctx *ctx, double alpha, int d, int group_size, const Skeleton &sk, size_t e_begin, size_t e_end,
+             LevelOut &out, PCResultHost &res, const std::function<void()> &deferred = nullptr);
 // decision-margin log of a ctx (capi_pc.hip): reset / read
 int CiMarginReset(fbn_ci_ctx *c);
 int CiMarginRead(fbn_ci_ctx *c, double *min_margin, int64_t *near_alpha);
