@@ -108,6 +108,44 @@ class JTGen {
     // op boundary (+ diagnostic cycle stamp of op category k when FBN_JT_PROFILE is set)
     bool profile = false;
     static constexpr int64_t kInitBatch = 16;  // fast order: entries per software-pipelined batch of the fused product
+    // Pipeline of the initial potentials' scalar loads, on where the register pool is on
+    // (FBN_JT_SCHED, default 1; 0 = the loads as without the pool).  Values are untouched: only
+    // where the loads stand changes.  Without it batch b + 1 is requested right before batch b's
+    // first use, and as scalar loads return out of order that use's wait (lgkmcnt(0)) covers the
+    // request just made: every second batch paid a whole scalar-cache round trip.  With it
+    //  * batch b + 1 is requested after the first products of batch b, so behind their wait;
+    //  * the first batch of fused product n + 1 (kSchedFirst entries: the SGPRs it holds across the
+    //    sums of op n) is requested right after fused product n, the first product's in front of
+    //    its op;
+    //  * the loads are volatile vector loads (IvLoads), which keep their place.
+    static constexpr int64_t kSchedFirst = 8;
+    bool sched = false;
+    int64_t BatchEnd(int64_t b0, int64_t T) const { return std::min(T, b0 + (b0 == 0 && sched ? kSchedFirst : kInitBatch)); }
+    bool iv_issued = false;  // the next fused product's first batch is already requested
+    // With the pipeline, the product trees of kSchedGroup entries of a fused product and the bin
+    // sums of kSchedGroup bins of a Collect message are written level by level (every node over two
+    // leaves first, then the nodes over those), one named temporary per inner node: the same trees
+    // as prod / TreeSum, so the same operands and association.  No barrier between the levels: the
+    // order is a hint to the compiler, which keeps enough of it.
+    static constexpr int64_t kSchedGroup = 2;
+    int64_t ntemp = 0;  // the temporaries' names
+    struct LTree {  // one statement: head <balanced tree of the leaves> ; tail
+        std::string head;
+        std::vector<std::string> leaves;
+        std::string tail;
+    };
+    std::vector<std::string> Levels(const std::vector<LTree> &trees, char op);  // the statements, by level
+    bool in_leaf_rc = false;
+    std::string IvLoads(const std::string &P, int c, int64_t b0);
+    // the first batch of the next fused product: a marker in the text after each fused product,
+    // which Run replaces at the end
+    std::vector<std::string> iv_first;
+    void IvFirst(const std::string &P, int c) {
+        if (iv_first.empty()) o << IvLoads(P, c, 0);
+        else iv_first.back() = IvLoads(P, c, 0);
+        iv_issued = true;
+    }
+    static std::string IvMarker(size_t n) { return "/*@iv" + std::to_string(n) + "@*/"; }
     // fast order: a clique's SepDis ops and marginals share one op region (independent of each
     // other: their latencies overlap); inside it an op's closing boundary is left out
     bool in_merged = false;
@@ -133,7 +171,9 @@ class JTGen {
         for (int64_t j = 0; j < Ts; ++j) o << "        double " << name << s << "_" << j << ";\n";
         o << "        { // recompute the Collect message of leaf clique " << c << "\n";
         const std::string P = "r" + name;
+        in_leaf_rc = true;  // (a scope of its own: no first batch of the next fused product in it)
         InitProd(P, c, {}, -1, "");
+        in_leaf_rc = false;
         for (int64_t j = 0; j < Ts; ++j) {
             std::vector<std::string> terms;
             for (int64_t q = 0; q < Q; ++q) terms.push_back(N(P, c, q * Ts + j));
@@ -287,6 +327,63 @@ void JTGen::Init(const std::string &P, int c) {
     normed = false;
 }
 
+std::vector<std::string> JTGen::Levels(const std::vector<LTree> &trees, char op) {
+    std::vector<std::string> lv;
+    const std::string ops = std::string(" ") + op + " ";
+    for (const LTree &t : trees) {
+        // (name, height) of the node over the leaves [lo, hi), split like TreeSum
+        std::function<std::pair<std::string, size_t>(size_t, size_t)> node = [&](size_t lo, size_t hi) -> std::pair<std::string, size_t> {
+            if (hi - lo == 1) return {t.leaves[lo], 0};
+            const size_t m = lo + (hi - lo) / 2;
+            const auto a = node(lo, m), b = node(m, hi);
+            const size_t h = 1 + std::max(a.second, b.second);
+            if (lv.size() < h) lv.resize(h);
+            if (lo == 0 && hi == t.leaves.size()) {
+                lv[h - 1] += t.head + a.first + ops + b.first + ";" + t.tail;
+                return {"", h};
+            }
+            const std::string nm = "x" + std::to_string(ntemp++);
+            lv[h - 1] += "        const double " + nm + " = " + a.first + ops + b.first + ";\n";
+            return {nm, h};
+        };
+        const auto r = node(0, t.leaves.size());
+        if (t.leaves.size() == 1) {
+            if (lv.empty()) lv.resize(1);
+            lv[0] += t.head + r.first + ";" + t.tail;
+        }
+    }
+    return lv;
+}
+
+std::string JTGen::IvLoads(const std::string &P, int c, int64_t b0) {
+    const int64_t T = plan.cliques[c].size();
+    std::ostringstream o;
+    if (b0 >= T) return std::string();
+    const int64_t b1 = BatchEnd(b0, T);
+    if (sched && !iv_lds) {
+        // Ordered loads: a plain load from the constant address space is tied to nothing, and
+        // instruction selection places it next to its first use whatever the statement order (the
+        // scheduling barriers bind the machine scheduler only).  A volatile load keeps its place
+        // between the barriers; whole vectors, so a batch is still two 64-byte scalar loads.
+        for (int64_t e = b0, n = 16; e < b1; e += n) {
+            while (n > b1 - e) n /= 2;
+            const std::string wv = "wv" + P + std::to_string(c) + "_" + std::to_string(e);
+            o << "        const " << (n > 1 ? "fbn_w" + std::to_string(n) : std::string("double")) << " " << wv << " = *(const volatile "
+              << (n > 1 ? "fbn_cw" + std::to_string(n) : std::string("cdouble")) << " *)&IV(" << init_off[c] + e << ");";
+            for (int64_t k = 0; k < n; ++k)
+                o << " const double w" << P << c << "_" << e + k << " = " << wv << (n > 1 ? "[" + std::to_string(k) + "]" : std::string()) << ";";
+            o << "\n";
+        }
+        o << "        __builtin_amdgcn_sched_barrier(0);\n";
+        return o.str();
+    }
+    o << "       ";
+    for (int64_t e = b0; e < b1; ++e)
+        o << " const double w" << P << c << "_" << e << " = IV(" << init_off[c] + e << ");";
+    o << "\n        __builtin_amdgcn_sched_barrier(0);\n";
+    return o.str();
+}
+
 void JTGen::InitProd(const std::string &P, int c, const std::vector<std::pair<int, std::string>> &kids, int up,
                      const std::string &upM) {
     const Table &t = plan.cliques[c];
@@ -309,28 +406,48 @@ void JTGen::InitProd(const std::string &P, int c, const std::vector<std::pair<in
         for (int64_t e = 0; e < t.size(); ++e) kidx[i].push_back(SepIndex(t, sp, e));
     }
     const int64_t Tup = up >= 0 ? plan.seps[up].size() : 0;
-    const int64_t kB = kInitBatch, T = t.size();
-    auto loads = [&](int64_t b0) {
-        if (b0 >= T) return;
-        o << "       ";
-        for (int64_t e = b0; e < std::min(T, b0 + kB); ++e)
-            o << " const double w" << P << c << "_" << e << " = IV(" << init_off[c] + e << ");";
-        o << "\n        __builtin_amdgcn_sched_barrier(0);\n";
+    const int64_t T = t.size();
+    if (!iv_issued) o << IvLoads(P, c, 0);
+    iv_issued = false;
+    // the factors of entry e, in the order of the product tree
+    auto factors = [&](int64_t e) {
+        std::vector<std::string> f{"w" + P + std::to_string(c) + "_" + std::to_string(e)};
+        int64_t r = e;
+        for (int j = 0; j < nv; ++j) {
+            const int64_t dgt = r / t.cum[j];
+            r %= t.cum[j];
+            if (ev_here[j]) f.push_back("i" + P + std::to_string(c) + "_" + std::to_string(j) + "_" + std::to_string(dgt));
+        }
+        for (size_t i = 0; i < kids.size(); ++i)
+            f.push_back(kids[i].second + std::to_string(kids[i].first) + "_" + std::to_string(kidx[i][e]));
+        if (up >= 0) f.push_back(upM + std::to_string(up) + "_" + std::to_string(e % Tup));
+        return f;
     };
-    loads(0);
-    for (int64_t b0 = 0; b0 < T; b0 += kB) {
-        loads(b0 + kB);
-        for (int64_t e = b0; e < std::min(T, b0 + kB); ++e) {
-            std::vector<std::string> f{"w" + P + std::to_string(c) + "_" + std::to_string(e)};
-            int64_t r = e;
-            for (int j = 0; j < nv; ++j) {
-                const int64_t dgt = r / t.cum[j];
-                r %= t.cum[j];
-                if (ev_here[j]) f.push_back("i" + P + std::to_string(c) + "_" + std::to_string(j) + "_" + std::to_string(dgt));
+    const std::string wpre = "w" + P + std::to_string(c) + "_";
+    for (int64_t b0 = 0, b1; b0 < T && sched; b0 = b1) {
+        b1 = BatchEnd(b0, T);
+        // the next batch is requested behind the first level that reads a potential of this one,
+        // so behind its wait
+        bool pending = b1 < T;
+        for (int64_t e0 = b0; e0 < b1; e0 += kSchedGroup) {
+            std::vector<LTree> trees;
+            for (int64_t e = e0; e < std::min(b1, e0 + kSchedGroup); ++e)
+                trees.push_back({"        " + std::string(e < kRegEntries ? "double " : "") + N(P, c, e) + " = ", factors(e), "\n"});
+            for (const std::string &l : Levels(trees, '*')) {
+                o << l;
+                if (pending && l.find(wpre) != std::string::npos) {
+                    o << "        __builtin_amdgcn_sched_barrier(0);\n" << IvLoads(P, c, b1);
+                    pending = false;
+                }
             }
-            for (size_t i = 0; i < kids.size(); ++i)
-                f.push_back(kids[i].second + std::to_string(kids[i].first) + "_" + std::to_string(kidx[i][e]));
-            if (up >= 0) f.push_back(upM + std::to_string(up) + "_" + std::to_string(e % Tup));
+        }
+        o << "        __builtin_amdgcn_sched_barrier(0);\n";
+    }
+    for (int64_t b0 = 0, b1; b0 < T && !sched; b0 = b1) {
+        b1 = BatchEnd(b0, T);
+        o << IvLoads(P, c, b1);
+        for (int64_t e = b0; e < b1; ++e) {
+            const std::vector<std::string> f = factors(e);
             // a balanced product tree (depth log2 of the factor count)
             std::function<std::string(size_t, size_t)> prod = [&](size_t lo, size_t hi) -> std::string {
                 if (hi - lo == 1) return f[lo];
@@ -342,6 +459,7 @@ void JTGen::InitProd(const std::string &P, int c, const std::vector<std::pair<in
         o << "        __builtin_amdgcn_sched_barrier(0);\n";
     }
     o << B(2);
+    if (sched && !in_leaf_rc) o << IvMarker(iv_first.size()) << "\n", iv_first.push_back(std::string());
     normed = false;
 }
 
@@ -372,7 +490,17 @@ void JTGen::SepCol(const std::string &P, int c, int s, bool store) {
         // message = the raw bin sums (tree sums), never normalized: every later use is invariant to
         // a per-case scale of it (the Distribute ratio a / old, the normalized marginals), and its
         // values are likelihoods of the evidence below (<= 1); Marg range-checks the products
-        for (int64_t j = 0; j < Ts; ++j) {
+        for (int64_t j0 = 0; j0 < Ts && sched; j0 += kSchedGroup) {
+            std::vector<LTree> trees;
+            for (int64_t j = j0; j < std::min(Ts, j0 + kSchedGroup); ++j) {
+                const std::string mc = "mc" + std::to_string(s) + "_" + std::to_string(j);
+                std::vector<std::string> terms;
+                for (int64_t q = 0; q < Q; ++q) terms.push_back(N(P, c, q * Ts + j));
+                trees.push_back({"        const double " + mc + " = ", terms, (store ? " " + col_loc[s][j] + " = " + mc + ";" : std::string()) + "\n"});
+            }
+            for (const std::string &l : Levels(trees, '+')) o << l;
+        }
+        for (int64_t j = 0; j < Ts && !sched; ++j) {
             std::vector<std::string> terms;
             for (int64_t q = 0; q < Q; ++q) terms.push_back(N(P, c, q * Ts + j));
             o << "        const double mc" << s << "_" << j << " = " << TreeSum(terms) << ";";
@@ -922,6 +1050,7 @@ int JTGen::Run(std::string &src, int64_t *wave_entries, std::vector<double> &ini
     // variable-major kernel only (the case-major one is faster with it too, but spills more SGPRs)
     int64_t reg_cap = fast && vmajor ? kDefaultRegPool : 0;
     if (const char *e = KnobValue("FBN_JT_REG_POOL")) reg_cap = fast ? std::max(0, atoi(e)) : 0;
+    sched = reg_cap > 0 && KnobOr("FBN_JT_SCHED", 1) != 0;
     if (reg_cap > 0) {
         int64_t best = -1, plan_peak = 0;
         int bvc = 0, bvd = 0;
@@ -1091,6 +1220,10 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
         }
         o << " __builtin_amdgcn_sched_barrier(0); } while (0)\n";
     }
+    if (sched)  // batches of initial potentials as vectors (IvLoads)
+        for (int n = 2; n <= 16; n *= 2)
+            o << "        typedef double fbn_w" << n << " __attribute__((ext_vector_type(" << n << "), aligned(8)));"
+              << " typedef __attribute__((address_space(4))) fbn_w" << n << " fbn_cw" << n << ";\n";
     for (int k = 0; k < nokw; ++k) o << "        unsigned okw" << k << " = 0u;\n";
     for (int k = 0; k < nobs; ++k) o << "        unsigned obs" << k << " = 0u;\n";
     // message entries parked in registers: one per block iteration, assigned by the op that forms
@@ -1144,6 +1277,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
                 for (int s : next)
                     if (!loaded_a[s]) Load("la", s), loaded_a[s] = true;
         }
+        if (fast && sched) IvFirst("t", c);
         o << B(1);
         const auto &down = plan.clique_down[c];
         if (fast) {
@@ -1202,6 +1336,7 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
                 if (ld_next && !loaded_d[nup]) Load("ld", nup), loaded_d[nup] = true;
             }
         }
+        if (c != cont_root && fast && early && sched) IvFirst("u", c);
         o << B(1);
         std::string P = "t";
         if (c != cont_root && fast && early) {  // all messages in registers: one fused op
@@ -1252,6 +1387,10 @@ fbn_jt_gen(const i8 *__restrict__ evid, double *__restrict__ marg, int *__restri
 }
 )";
     src = o.str();
+    for (size_t n = 0; n < iv_first.size(); ++n) {
+        const size_t at = src.find(IvMarker(n) + "\n");
+        src.replace(at, IvMarker(n).size() + 1, iv_first[n]);
+    }
     return FBN_OK;
 }
 

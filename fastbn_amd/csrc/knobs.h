@@ -44,6 +44,7 @@ inline constexpr Knob kKnobs[] = {
     {"FBN_JT_LEAF_RC", "0", kSeam, kPerCall},
     {"FBN_JT_MARG_V2", "1", kSeam, kPerCall},
     {"FBN_JT_REG_POOL", "the registers left under the budget", kSeam, kPerCall},
+    {"FBN_JT_SCHED", "1: the potentials' load pipeline and level-wise products (read only with the register pool on)", kSeam, kPerCall},
     {"FBN_JT_TILING", "0", kSeam, kPerCall},
     {"FBN_JT_TW", "1", kSeam, kPerCall},
     // PC-stable: drivers (pc_driver.cpp, pc_dist.cpp, capi_pc.hip)

@@ -107,6 +107,13 @@ ALARM_TEST_OPTIONS = ({"FBN_JT_LEAF_RC": "1"}, {"FBN_JT_LDS_POOL": "0"}, {"FBN_J
                       {"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"})
 
 
+# by output layout: the register pool's kernel with the load pipeline (FBN_JT_SCHED unset) and
+# without it (tests/test_gpu_jt_sched.py, tests/test_jt_sched_codegen.py); the pool is the default
+# of the variable-major layout (1) and on request in the case-major one (0)
+SCHED_TEST_OPTIONS = {0: ({"FBN_JT_REG_POOL": "256"}, {"FBN_JT_REG_POOL": "256", "FBN_JT_SCHED": "0"}),
+                      1: ({}, {"FBN_JT_SCHED": "0"})}
+
+
 def prebuild_options(xml, options, layout=0):
     """The fast-order kernel of `xml` under each set of generator environment options (read when
     the kernel is generated), built in a child process per set."""
@@ -130,7 +137,12 @@ def prebuild_default(clean=True):
     with tempfile.TemporaryDirectory() as d:
         built = prebuild([ALARM_XML], layouts=(0, 1)) + prebuild([synth_small_xml(d)] + fixture_xmls(d))
         built += prebuild_forests(d)
+        # (tests/test_gpu_jt_sched.py: the register pool's kernel of the synthetic network with and
+        # without the load pipeline)
+        built += prebuild_options(synth_small_xml(d), SCHED_TEST_OPTIONS[1], layout=1)
     built += prebuild_options(ALARM_XML, ALARM_TEST_OPTIONS)
+    for layout in (0, 1):
+        built += prebuild_options(ALARM_XML, SCHED_TEST_OPTIONS[layout], layout=layout)
     # (tests/test_gpu_jt_regpool.py compares the register pool on / off in both output layouts)
     built += prebuild_options(ALARM_XML, ({"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"}), layout=1)
     # (the exact-order kernels of the conflict networks and of the 32-state network take 5 .. 20 s each)
