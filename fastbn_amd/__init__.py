@@ -23,6 +23,8 @@ reference's names and argument meaning:
 * ``AISBN(network, num_samples, max_updates, interval, eps, seed).infer(evidence)`` and
   ``SelfImportanceSampling(...)`` -- the reference's ``-a 10`` / ``-a 8`` stubs (src/main.cpp:175-186,
   :149-160): samplers that learn their importance function from their own weighted samples
+* ``MostProbableExplanation(network).infer(evidence)`` -- the complete assignment argmax_x P(x, e) and its
+  log-probability, exact, by max-product on the junction forest (no reference counterpart)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -42,6 +44,7 @@ from .api import (  # noqa: F401
     EPISBN,
     AISBN,
     SelfImportanceSampling,
+    MostProbableExplanation,
     score_marginals,
     family_sizes,
     pdag_to_dag,
@@ -56,6 +59,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

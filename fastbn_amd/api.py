@@ -146,6 +146,14 @@ _SIGS = {
     "fbn_ais_info": [_vp, _i64, _vp, _vp, _vp, _vp],
     "fbn_ais_last_kernel_ms": [_vp, _vp],
     "fbn_ais_eta": [C.c_int, C.c_int, _vp],
+    "fbn_mpe_create": [_vp, C.c_int, _pp],
+    "fbn_mpe_destroy": [_vp],
+    "fbn_mpe_info": [_vp, _vp, _vp, _vp, _vp],
+    "fbn_mpe_run": [_vp, _vp, _i64, _vp, _vp],
+    "fbn_mpe_run_device": [_vp, _vp, _i64, _vp, _vp, _vp],
+    "fbn_mpe_debug_messages": [_vp, _vp, _i64, _vp, _vp],
+    "fbn_mpe_set_tuning": [_vp, C.c_int, _i64],
+    "fbn_mpe_last_kernel_ms": [_vp, _vp],
 }
 
 
@@ -205,7 +213,7 @@ lib = _Lib()
 # then host-only handles.
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
-                "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2,
+                "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2, "MostProbableExplanation": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -1255,3 +1263,68 @@ class SelfImportanceSampling(AISBN):
     cutoff's floor for support, so eps=0 is refused.  Otherwise as AISBN."""
 
     _method = 1
+
+
+class MostProbableExplanation(_Handle):
+    """Most probable explanation (fbn_mpe): the complete assignment x* = argmax_x P(x, e) that agrees with
+    the evidence, and log P(x*, e) -- exact, by max-product message passing with a back-trace on the
+    junction forest, so it takes any DAG.  The value is kept as a mantissa and a binary exponent and
+    does not underflow on networks of thousands of variables.  The reference has no counterpart.
+    device < 0: the host twin (bit-identical results)."""
+
+    _destroy = "fbn_mpe_destroy"
+
+    def __init__(self, network, device=0):
+        self.network = network
+        h = C.c_void_p()
+        lib.fbn_mpe_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def info(self):
+        """dict(cliques, entries, store_rows, components): store_rows = rows of one case's store."""
+        c, e, r, k = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+        lib.fbn_mpe_info(self._h, C.byref(c), C.byref(e), C.byref(r), C.byref(k))
+        return {"cliques": c.value, "entries": e.value, "store_rows": r.value, "components": k.value}
+
+    def value_parts(self, evidence):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (assignment int8 [ncases][num_nodes],
+        value fp64 [ncases][2] = (m, ex) with P(x*, e) = m * 2^ex, m in [0.5, 1))."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        assign = np.zeros((n, self.network.num_nodes), np.int8)
+        value = np.zeros((n, 2), np.float64)
+        lib.fbn_mpe_run(self._h, _p(ev), n, _p(assign), _p(value))
+        return assign, value
+
+    def infer(self, evidence):
+        """-> (assignment int8 [ncases][num_nodes], log_p fp64 [ncases] = log P(x*, e))."""
+        assign, value = self.value_parts(evidence)
+        return assign, np.log(value[:, 0]) + value[:, 1] * np.log(2.0)
+
+    def run_device(self, d_evidence_ptr, ncases, d_assignment_ptr, d_value_ptr, stream_ptr=None):
+        """Device-resident run (asynchronous on the stream after the evidence check)."""
+        lib.fbn_mpe_run_device(self._h, C.c_void_p(d_evidence_ptr), int(ncases), C.c_void_p(d_assignment_ptr),
+                               C.c_void_p(d_value_ptr), stream_ptr)
+
+    def debug_messages(self, evidence):
+        """(messages fp64 [ncases][sum of separator entries], exponents int32 [ncases][separators]) as
+        Collect leaves them."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        i = self.info()
+        nsep = i["cliques"] - i["components"]
+        msg = np.zeros((n, i["store_rows"] - nsep - i["cliques"]), np.float64)
+        exps = np.zeros((n, nsep), np.int32)
+        lib.fbn_mpe_debug_messages(self._h, _p(ev), n, _p(msg), _p(exps))
+        return msg, exps
+
+    def set_tuning(self, max_workgroups=0, store_bytes_max=0):
+        """fbn_mpe_set_tuning: max_workgroups caps the persistent grid, store_bytes_max the message store
+        of all waves together.  0 = default.  Results do not change."""
+        lib.fbn_mpe_set_tuning(self._h, int(max_workgroups), int(store_bytes_max))
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_mpe_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value

@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -98,5 +98,9 @@ struct AisDeviceArgs;
 }
 extern "C" hipError_t fbn_ais_launch(const fbn::AisDeviceArgs *a, int lds_state, size_t lds_bytes, int grid,
                                      hipStream_t stream);
+// The max-product kernel (jt_mpe_program.h's arguments): a persistent grid of a->grid one-wave
+// workgroups, 64 cases each per round, a->store_rows rows of a->store per workgroup.
+struct JtMpeArgs;
+extern "C" hipError_t fbn_mpe_launch(const JtMpeArgs *a, hipStream_t stream);
 
 #endif

@@ -744,6 +744,69 @@ int fbn_ais_last_kernel_ms(const fbn_ais *s, float *ms);
 /* eta[0 .. m) of a method, as the runs use it (for restatements that must not depend on pow). */
 int fbn_ais_eta(int method, int m, double *eta);
 
+/* ------------------------------------------------------------------ most probable explanation
+ * MPE: the complete assignment x* = argmax_x P(x, e) that agrees with the evidence e, and P(x*, e).
+ * Exact, by max-product message passing on the junction forest of fbn_jt_forest_plan_create (any DAG).
+ * The reference has no counterpart (its algorithms stop at marginals; its -a ends at 11).  The per-variable
+ * arg-maxes of the posterior marginals are a different thing and can form an assignment of probability 0.
+ *
+ * Plan: the forest plan -- cliques with initial potentials init_c (plain products of CPT entries; the
+ * product over all cliques is the joint), separators, clique_up / clique_down, levels, one root per
+ * component.  Evidence is applied by masking: a clique entry that disagrees with an observed variable is
+ * skipped.  Every CPT entry is (count + 1) / (total + |dom|) > 0, so P(x, e) > 0 for every evidence row that
+ * passes validation; no zero-probability branch exists beyond a guard.
+ * Collect: cliques deepest level first, plan order within a level.  For clique c scan its entries
+ *   e = 0 .. T-1 ascending, skipping masked ones:
+ *     v(e) = (((init_c[e] * M^_1[map_1(e)]) * M^_2[map_2(e)]) ...) over the children in clique_down order;
+ *   a non-root keeps msg[up(e)] = max(msg[up(e)], v(e)) from 0.0 (up: the entry's configuration of the
+ *   upstream separator); then mx = max_s msg[s], frexp(mx) = f * 2^k with f in [0.5, 1), the stored message
+ *   is M^_c[s] = ldexp(msg[s], -k) and the clique's integer exponent E_c = k + sum over children E_child.
+ *   Only powers of two rescale: every mantissa equals the unscaled product's, and nothing underflows on a
+ *   deep tree (the maximum is never divided by).
+ * Root and value: a root r takes the first strict maximum of v(e) over its unmasked entries (ascending e,
+ *   '>', from the first unmasked entry): e*_r and best_r = f_r * 2^(k_r), total exponent k_r + sum E_child.
+ *   The case's value is the product over the roots in ascending component order from (m, ex) = (1.0, 0):
+ *   m = m * f_r, re-frexp after each multiply, exponents added.  value[case] = {m, ex}, m in [0.5, 1), ex
+ *   integral, P(x*, e) = m * 2^ex -- representable where P itself is far below 2^-1074.  No log is
+ *   evaluated; a caller forms log P = log(m) + ex * log 2.
+ * Back-trace: cliques levels ascending, plan order within a level.  A root assigns its variables from
+ *   e*_r.  A clique c with parent p takes s* = map_{p->c}(e*_p), recomputes v(e) exactly as in Collect for
+ *   its unmasked entries with up(e) == s* (after the plan's table reorganisation: e = s* mod Ts), takes
+ *   the first strict maximum in ascending e and assigns its variables from it.  Observed variables keep
+ *   their evidence code; every variable is in a clique, so the row is complete.
+ * Only *, comparisons, frexp and ldexp: two runs, any split of a batch, any grid size and the host twin
+ * give identical bytes, the assignment under exact ties included.
+ * Limits: a clique of more than 32 variables, tables beyond int32 indexing, or one wave's store
+ * (store_rows * 512 bytes) past the handle's budget: FBN_ERR_LIMIT at create.  A cyclic network: FBN_ERR_ARG. */
+typedef struct fbn_mpe fbn_mpe;
+/* Build the forest plan, compile the max-product program and upload it to `device`.  device < 0: a
+ * host-only handle that runs the same algorithm on CPU threads (bit-identical); its *_device entry returns
+ * FBN_ERR_NODEV. */
+int fbn_mpe_create(const fbn_network *net, int device, fbn_mpe **out);
+int fbn_mpe_destroy(fbn_mpe *s);
+/* cliques, the sum of their entries, the rows of one case's store (separator entries + separators +
+ * cliques; never a clique table) and the forest's components. */
+int fbn_mpe_info(const fbn_mpe *s, int64_t *cliques, int64_t *entries, int64_t *store_rows, int *components);
+/* evidence [ncases][V] int8, -1 = unobserved, every code -1 or < the node's state count (checked before
+ * anything indexes with it: FBN_ERR_ARG naming the first bad case / node).  assignment [ncases][V] int8,
+ * value [ncases][2] fp64 = {m, ex}.  Host arrays, synchronous. */
+int fbn_mpe_run(fbn_mpe *s, const int8_t *evidence, int64_t ncases, int8_t *assignment, double *value);
+/* The same with device-resident buffers; asynchronous on hip_stream after the evidence check (one stream
+ * sync, as fbn_jt_run_device's). */
+int fbn_mpe_run_device(fbn_mpe *s, const int8_t *d_evidence, int64_t ncases, int8_t *d_assignment, double *d_value,
+                       void *hip_stream);
+/* Testing interface: the stored messages M^ [ncases][sum of separator entries] (separators in plan order)
+ * and the exponents E of each separator's child clique [ncases][separators], as Collect leaves them;
+ * at most 2^26 doubles.  Host arrays. */
+int fbn_mpe_debug_messages(fbn_mpe *s, const int8_t *evidence, int64_t ncases, double *messages, int32_t *exponents);
+/* Kernel tuning (an explicit API, not an environment variable).  max_workgroups: cap of the persistent
+ * grid, 0 = default.  store_bytes_max: the budget of the message store, all waves together (0 = default,
+ * 32 GiB, and never more than half of the free device memory); the grid shrinks to fit it, and a budget one wave's store does not fit is FBN_ERR_LIMIT (the
+ * handle keeps its setting).  Results never depend on either. */
+int fbn_mpe_set_tuning(fbn_mpe *s, int max_workgroups, int64_t store_bytes_max);
+/* Device kernel time (ms, hipEvent) of the handle's last launch. */
+int fbn_mpe_last_kernel_ms(const fbn_mpe *s, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
