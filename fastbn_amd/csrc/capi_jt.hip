@@ -254,18 +254,25 @@ int fbn_jt_set_variant(fbn_jt_plan *p, int variant) {
 // the plan-specialized kernel of the current arithmetic order, loaded (cache) or compiled (hiprtc)
 // once per plan and order; both orders stay loaded
 static fbn_jt_plan::GenKernel &GenCur(fbn_jt_plan *p, bool vm) { return p->gen[(JtFast(p) ? 1 : 0) + (vm ? 2 : 0)]; }
+// source, constant input and launch facts of the specialized kernel of the plan's current order
+static int GenSpec(const fbn_jt_plan *p, bool vm, fbn::JTKernelSpec &spec) {
+    if (!p->gen_eligible) return SetError(FBN_ERR_ARG, "plan not eligible for codegen");
+    return fbn::GenerateJTKernel(p->host, JtFast(p), vm, spec);
+}
+static int GenSpec(const fbn_jt_plan *p, fbn::JTKernelSpec &spec) { return GenSpec(p, p->out_layout == 1, spec); }
+
 static int GenEnsure(fbn_jt_plan *p, bool vm) {
-    const bool fast = JtFast(p);
     auto &k = GenCur(p, vm);
     if (k.state == 1) return FBN_OK;
     if (k.state == -1) return FBN_ERR_HIP;
     k.state = -1;
-    std::string src;
-    std::vector<double> iv;
-    int rc = fbn::GenerateJTKernel(p->host, src, &k.we, iv, &k.lds, fast, vm);
+    fbn::JTKernelSpec spec;
+    int rc = GenSpec(p, vm, spec);
     if (rc) return rc;
+    k.we = spec.wave_entries, k.lds = spec.lds_bytes;
+    const std::vector<double> &iv = spec.initv;
     std::vector<char> code;
-    if ((rc = fbn::JitCodeObject(src, code))) return rc;
+    if ((rc = fbn::JitCodeObject(spec.src, code))) return rc;
     FBN_HIP(hipModuleLoadData(&k.mod, code.data()));
     FBN_HIP(hipModuleGetFunction(&k.fn, k.mod, "fbn_jt_gen"));
     if ((rc = k.iv.ensure(std::max<size_t>(iv.size() * 8, 8)))) return rc;
@@ -292,12 +299,9 @@ int fbn_jt_debug_op_cycles(fbn_jt_plan *p, int enable, unsigned long long *cycle
 
 int fbn_jt_kernel_source(const fbn_jt_plan *p, char *buf, int64_t cap, int64_t *len) {
     if (!p) return SetError(FBN_ERR_ARG, "null pointer");
-    if (!p->gen_eligible) return SetError(FBN_ERR_ARG, "plan not eligible for codegen");
-    std::string src;
-    std::vector<double> iv;
-    int64_t we = 0;
-    int rc = fbn::GenerateJTKernel(p->host, src, &we, iv, nullptr, JtFast(p), p->out_layout == 1);
-    if (rc) return rc;
+    fbn::JTKernelSpec spec;
+    if (int rc = GenSpec(p, spec)) return rc;
+    const std::string &src = spec.src;
     if (len) *len = (int64_t)src.size() + 1;
     if (buf && cap > 0) {
         const size_t n = std::min<size_t>((size_t)cap - 1, src.size());
@@ -309,25 +313,17 @@ int fbn_jt_kernel_source(const fbn_jt_plan *p, char *buf, int64_t cap, int64_t *
 
 int fbn_jt_kernel_cache_path(const fbn_jt_plan *p, char *buf, int64_t cap) {
     if (!p || !buf || cap <= 0) return SetError(FBN_ERR_ARG, "bad argument");
-    if (!p->gen_eligible) return SetError(FBN_ERR_ARG, "plan not eligible for codegen");
-    std::string src;
-    std::vector<double> iv;
-    int64_t we = 0;
-    int rc = fbn::GenerateJTKernel(p->host, src, &we, iv, nullptr, JtFast(p), p->out_layout == 1);
-    if (rc) return rc;
-    snprintf(buf, (size_t)cap, "%s", fbn::JitCachePath(src).c_str());
+    fbn::JTKernelSpec spec;
+    if (int rc = GenSpec(p, spec)) return rc;
+    snprintf(buf, (size_t)cap, "%s", fbn::JitCachePath(spec.src).c_str());
     return FBN_OK;
 }
 
 int fbn_jt_kernel_placement(const fbn_jt_plan *p, int64_t *rows) {
     if (!p || !rows) return SetError(FBN_ERR_ARG, "null pointer");
-    if (!p->gen_eligible) return SetError(FBN_ERR_ARG, "plan not eligible for codegen");
-    std::string src;
-    std::vector<double> iv;
-    int64_t we = 0;
-    fbn::JTPlacement pl;
-    int rc = fbn::GenerateJTKernel(p->host, src, &we, iv, nullptr, JtFast(p), p->out_layout == 1, &pl);
-    if (rc) return rc;
+    fbn::JTKernelSpec spec;
+    if (int rc = GenSpec(p, spec)) return rc;
+    const fbn::JTPlacement &pl = spec.place;
     const int64_t r[8] = {pl.global[0], pl.global[1], pl.lds[0], pl.lds[1],
                           pl.reg[0], pl.reg[1], pl.workspace_rows, pl.lds_pool_rows};
     std::copy(r, r + 8, rows);
@@ -359,14 +355,10 @@ int fbn_jt_debug_flagged_blocks(fbn_jt_plan *p, int64_t *count) {
 
 int fbn_jt_kernel_build(const fbn_jt_plan *p) {
     if (!p) return SetError(FBN_ERR_ARG, "null pointer");
-    if (!p->gen_eligible) return SetError(FBN_ERR_ARG, "plan not eligible for codegen");
-    std::string src;
-    std::vector<double> iv;
-    int64_t we = 0;
-    int rc = fbn::GenerateJTKernel(p->host, src, &we, iv, nullptr, JtFast(p), p->out_layout == 1);
-    if (rc) return rc;
+    fbn::JTKernelSpec spec;
+    if (int rc = GenSpec(p, spec)) return rc;
     std::vector<char> code;
-    return fbn::JitCodeObject(src, code);
+    return fbn::JitCodeObject(spec.src, code);
 }
 
 int fbn_jt_kernel_options(char *buf, int64_t cap) {

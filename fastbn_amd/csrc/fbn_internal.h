@@ -158,21 +158,25 @@ struct JTProgramT {
 // > 32 digit bits in a clique, tables beyond int32 indexing).  lds_budget: bytes of factors per wave.
 int CompileJTProgramT(const JTPlanHost &plan, JTProgramT &prog, int lds_budget);
 
-// plan-specialized kernel source (jt_codegen.cpp): eligibility and generation.  The generated
+// plan-specialized kernel source (jt_gen_*.cpp): eligibility and generation.  The generated
 // kernel's per-wave workspace holds wave_entries rows of 64 fp64 lanes; initv is its constant input.
 bool JTCodegenEligible(const JTPlanHost &plan, int64_t *entry_ops);
-// fast: the fast arithmetic order (normalizations that cancel are left out; results within 1e-12 of
-// the exact order, which repeats the reference's every multiply + Normalize); var_major: marginals
-// stored variable-major [sum_dom][ncases] instead of case-major [ncases][sum_dom]
 // message rows (64 lanes x fp64 each) of the generated kernel per place, [0] Collect, [1] Distribute
 struct JTPlacement {
     int64_t global[2] = {0, 0}, lds[2] = {0, 0}, reg[2] = {0, 0};
     int64_t workspace_rows = 0;  // global rows per wave (a separator's two messages share theirs)
     int64_t lds_pool_rows = 0;   // LDS pool rows per wave (the most in use at one time)
 };
-int GenerateJTKernel(const JTPlanHost &plan, std::string &src, int64_t *wave_entries, std::vector<double> &initv,
-                     int64_t *lds_bytes = nullptr, bool fast = false, bool var_major = false,
-                     JTPlacement *placement = nullptr);
+struct JTKernelSpec {
+    std::string src;
+    std::vector<double> initv;
+    int64_t wave_entries = 0, lds_bytes = 0;  // per wave: workspace rows, dynamic LDS
+    JTPlacement place;
+};
+// fast: the fast arithmetic order (normalizations that cancel are left out; results within 1e-12 of
+// the exact order, which repeats the reference's every multiply + Normalize); var_major: marginals
+// stored variable-major [sum_dom][ncases] instead of case-major [ncases][sum_dom]
+int GenerateJTKernel(const JTPlanHost &plan, bool fast, bool var_major, JTKernelSpec &out);
 
 // compile + cache of the generated kernels (jt_jit.hip): the hiprtc options (part of the cache key),
 // the cache file of a source, its code object (cache hit or compile)

@@ -195,7 +195,7 @@ int fbn_jt_set_waves_per_cu(fbn_jt_plan *p, int waves);
 /* Kernel variant: -1 = auto (default: 3 when eligible and its code object loads, else 5 in the fast
  * order, else 4, else 0/1), 0 = clique-in-LDS interpreter, 1 = whole case state in a global
  * workspace interpreter, 2 = variant 0 with the IEEE division sequence forced (ablation / testing),
- * 3 = plan-specialized kernel (jt_codegen.cpp; hiprtc or the on-disk code-object cache) followed
+ * 3 = plan-specialized kernel (jt_gen_*.cpp; hiprtc or the on-disk code-object cache) followed
  *     by an exact-path fixup of the blocks it flags.  Selecting 3 fails if the plan is not eligible.
  * 4 = streamed ("virtual table") kernel for large trees (jt_virt.hip): tables recomputed per pass
  *     from initial potentials + received messages, only messages stored; exact-path fixup as 3.

@@ -1,5 +1,5 @@
 """The default (fast) arithmetic order of the plan-specialized ALARM-class kernel (variant 3,
-jt_codegen.cpp): a clique's table is its initial potential times its messages, normalized once
+jt_gen_emit.cpp): a clique's table is its initial potential times its messages, normalized once
 where a message or marginal is formed -- the reference's intermediate normalizations
 (src/JunctionTree.cpp:829-941, 1150-1238) cancel.  Labels equal the reference's own dumps and the
 oracle; marginals within 1e-12 relative (north_star allows 1e-6)."""

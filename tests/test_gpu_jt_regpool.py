@@ -1,4 +1,4 @@
-"""Register pool of the plan-specialized kernel (jt_codegen.cpp PlaceMessages, FBN_JT_REG_POOL):
+"""Register pool of the plan-specialized kernel (jt_gen_place.cpp JtGenPlace, FBN_JT_REG_POOL):
 message entries parked in registers the small cliques leave unused, and the child visit order the
 placement picks.  Where a message lives and when a subtree is visited change no arithmetic: the
 build with the pool agrees bitwise with the FBN_JT_REG_POOL=0 build (every message in LDS / global

@@ -1,4 +1,4 @@
-"""Load pipeline of the plan-specialized kernel (jt_codegen.cpp IvLoads, Levels, FBN_JT_SCHED): where
+"""Load pipeline of the plan-specialized kernel (jt_gen_emit.cpp IvLoads, Levels, FBN_JT_SCHED): where
 the scalar loads of the initial potentials stand -- the first batch of a fused product behind the
 previous fused product, batch b + 1 behind batch b's first use, as volatile vector loads -- and the
 product trees and Collect bin sums written level by level in pairs with named temporaries.  No

@@ -1,4 +1,4 @@
-"""Load pipeline and level-wise products of the plan-specialized ALARM kernel (jt_codegen.cpp IvLoads,
+"""Load pipeline and level-wise products of the plan-specialized ALARM kernel (jt_gen_emit.cpp IvLoads,
 Levels, FBN_JT_SCHED), checked without a GPU on the machine code of the default variable-major fast
 kernel (tools/jt_isa_stats.py: device=-1 build, llvm-objdump).  Figures of the commit before (= the
 FBN_JT_SCHED=0 build here, the same source byte for byte) and of this one, hiprtc / LLVM 22.0.0git
