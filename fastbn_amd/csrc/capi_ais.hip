@@ -15,7 +15,6 @@ using fbn::DevBuf;
 using fbn::SetError;
 
 struct fbn_ais : fbn::SamplerHandle {
-    int num_cu = 0;
     int64_t lds_bytes_max = FBN_AIS_LDS_DEFAULT;
     int max_workgroups = 0;
     DevBuf ws, di;                              // the state's global home; staging of the debug ICPT
@@ -27,7 +26,7 @@ struct fbn_ais : fbn::SamplerHandle {
     int64_t grid(int64_t ncases) const {
         int per_cu = FBN_AIS_GROUPS_PER_CU;
         const int64_t b = lds_state() ? lds_bytes() : base_bytes();
-        per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(per_cu, 160 * 1024 / b));
+        per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(per_cu, fbn::kCuLdsBytes / b));
         int64_t g = std::min<int64_t>(std::max<int64_t>(ncases, 1), (int64_t)std::max(num_cu, 1) * per_cu);
         if (max_workgroups > 0) g = std::min<int64_t>(g, max_workgroups);
         return g;
@@ -92,10 +91,10 @@ int AisHostBuffers(fbn_ais *s, const RunArgs &r, const int8_t *evidence, int32_t
 extern "C" {
 
 int fbn_ais_create(const fbn_network *net, int device, fbn_ais **out) {
-    return fbn::CreateSamplerHandle(net, out, [&](fbn_ais *s) { return s->Create(net->net, device, true, &s->num_cu); });
+    return fbn::CreateHandle(net, out, [&](fbn_ais *s) { return s->Create(net->net, device, true); });
 }
 
-int fbn_ais_destroy(fbn_ais *s) { return fbn::DestroySamplerHandle(s); }
+int fbn_ais_destroy(fbn_ais *s) { return fbn::DestroyHandle(s); }
 
 int fbn_ais_info(const fbn_ais *s, int64_t ncases, int64_t *lds_bytes, int64_t *state_bytes, int *path, int *grid) {
     if (!s) return SetError(FBN_ERR_ARG, "null pointer");
@@ -158,7 +157,7 @@ int fbn_ais_set_tuning(fbn_ais *s, int64_t lds_bytes_max, int max_workgroups) {
 }
 
 int fbn_ais_last_kernel_ms(const fbn_ais *s, float *ms) {
-    if (!s || !ms || !s->timed) return SetError(FBN_ERR_ARG, "no timed launch");
+    if (!s) return SetError(FBN_ERR_ARG, "no timed launch");
     return s->LastKernelMs(ms);
 }
 

@@ -527,7 +527,7 @@ static int CiLaunchHist(fbn_ci_ctx *c, const CiBatchReq &q, int maxdim, hipStrea
     }
     // tables beyond the LDS budget: the same layout in a per-workgroup global scratch region
     // (the kernel's own static LDS comes on top of the dynamic region)
-    const bool global_tables = lds + fbn_ci_static_lds_bytes() > 160 * 1024;
+    const bool global_tables = lds + fbn_ci_static_lds_bytes() > (size_t)fbn::kCuLdsBytes;
     if ((rc = CiOutputsEnsure(c, S, q))) return rc;
     if (!q.zc_items) FBN_HIP(hipMemcpyAsync(S.items.p, items, (size_t)n * w * 4, hipMemcpyHostToDevice, s));
     int grid = (int)std::min<int64_t>(n, (int64_t)c->num_cu * 8);

@@ -78,14 +78,14 @@ int EpisHostBuffers(fbn_epis *s, const RunArgs &r, const int8_t *evidence, int32
 extern "C" {
 
 int fbn_epis_create(const fbn_network *net, int device, fbn_epis **out) {
-    return fbn::CreateSamplerHandle(net, out, [&](fbn_epis *s) {
+    return fbn::CreateHandle(net, out, [&](fbn_epis *s) {
         int rc = fbn::BuildSamplerModel(net->net, s->M);
         if (rc == FBN_OK) rc = fbn_lbp_create(net, device, &s->lbp);
-        return rc ? rc : s->Attach(device, false, nullptr);
+        return rc ? rc : s->AttachTables(device, false);
     });
 }
 
-int fbn_epis_destroy(fbn_epis *s) { return fbn::DestroySamplerHandle(s); }
+int fbn_epis_destroy(fbn_epis *s) { return fbn::DestroyHandle(s); }
 
 int fbn_epis_info(const fbn_epis *s, int64_t *lds_bytes, int *path) {
     if (!s) return SetError(FBN_ERR_ARG, "null pointer");

@@ -3,7 +3,6 @@
 // (src/main.cpp:136-147) and its Parameter::propagation_length (include/Parameter.h:33).
 #include <hip/hip_runtime.h>
 
-#include <set>
 #include <vector>
 
 #include "fbn_device.h"
@@ -20,20 +19,12 @@ static constexpr int64_t kLbpLdsDefault = 64 * 1024;
 // workgroups per CU of the persistent grid (one wave each)
 static constexpr int kLbpGroupsPerCu = 16;
 
-struct fbn_lbp {
+struct fbn_lbp : fbn::DeviceHandle {
     fbn::LbpModel M;
-    int device = -1, num_cu = 0;
     int64_t lds_bytes_max = kLbpLdsDefault;
     int max_groups = 0;
-    DevBuf edges, terms, bin_edge, order, var_off, var_moff, marg_var, marg_off, self_moff, prob, dom, evcheck, ws;
+    DevBuf edges, terms, bin_edge, order, var_off, var_moff, marg_var, marg_off, self_moff, prob, ws;
     DevBuf evid, labels, marg, stats, msgs;  // staging of the host-buffer entries
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    std::set<hipStream_t> streams_used;
-    ~fbn_lbp() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
     int64_t lds_bytes() const { return 24 * M.M; }
     bool lds_path() const { return lds_bytes_max >= 0 && lds_bytes() <= lds_bytes_max; }
 };
@@ -44,15 +35,13 @@ namespace {
 int LbpDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double tol, double damping, int32_t *d_labels,
               double *d_marg, double *d_stats, double *d_msgs, hipStream_t st, double *d_lambda = nullptr,
               bool checked = false) {
-    s->streams_used.insert(st);
+    s->Note(st);
     // as fbn_jt_run_device's check: on the device, one stream sync
     if (!checked)
-        if (int rc = fbn::EvidenceCheckDevice(d_ev, ncases, s->M.V, s->dom.as<int32_t>(), s->M.dom.data(),
-                                              s->evcheck.as<unsigned long long>(), st))
-            return rc;
+        if (int rc = s->evidence.Run(d_ev, ncases, st)) return rc;
     const bool lds = s->lds_path();
     int per_cu = kLbpGroupsPerCu;
-    if (lds) per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(per_cu, 160 * 1024 / std::max<int64_t>(1, s->lds_bytes())));
+    if (lds) per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(per_cu, fbn::kCuLdsBytes / std::max<int64_t>(1, s->lds_bytes())));
     int64_t grid = std::min<int64_t>(ncases, (int64_t)s->num_cu * per_cu);
     if (s->max_groups > 0) grid = std::min<int64_t>(grid, s->max_groups);
     if (!lds)
@@ -61,7 +50,8 @@ int LbpDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double 
     a.edges = s->edges.as<fbn::LbpEdge>(), a.terms = s->terms.as<fbn::LbpTerm>();
     a.bin_edge = s->bin_edge.as<int32_t>(), a.order = s->order.as<int32_t>();
     a.var_off = s->var_off.as<int32_t>(), a.var_moff = s->var_moff.as<int32_t>();
-    a.marg_var = s->marg_var.as<int32_t>(), a.marg_off = s->marg_off.as<int32_t>(), a.dom = s->dom.as<int32_t>();
+    a.marg_var = s->marg_var.as<int32_t>(), a.marg_off = s->marg_off.as<int32_t>();
+    a.dom = s->evidence.dom.as<int32_t>();
     a.prob = s->prob.as<double>();
     a.ev = d_ev;
     a.V = s->M.V, a.SD = s->M.sum_dom, a.M = (int)s->M.M, a.d0 = s->M.dom[0];
@@ -69,11 +59,7 @@ int LbpDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, double 
     a.labels = d_labels, a.marg = d_marg, a.stats = d_stats, a.messages = d_msgs;
     a.ws = s->ws.as<double>();
     a.lambda = d_lambda, a.self_moff = s->self_moff.as<int32_t>();
-    FBN_HIP(hipEventRecord(s->ev0, st));
-    FBN_HIP(fbn_lbp_launch(&a, lds ? 1 : 0, (size_t)s->lds_bytes(), (int)grid, st));
-    FBN_HIP(hipEventRecord(s->ev1, st));
-    s->timed = true;
-    return FBN_OK;
+    return s->Timed(st, [&] { return fbn_lbp_launch(&a, lds ? 1 : 0, (size_t)s->lds_bytes(), (int)grid, st); });
 }
 
 int LbpHostBuffers(fbn_lbp *s, const int8_t *evidence, int64_t ncases, int iters, double tol, double damping,
@@ -120,44 +106,20 @@ int LbpLambdaDevice(fbn_lbp *s, const int8_t *d_ev, int64_t ncases, int iters, d
 extern "C" {
 
 int fbn_lbp_create(const fbn_network *net, int device, fbn_lbp **out) {
-    if (!net || !out) return SetError(FBN_ERR_ARG, "null pointer");
-    *out = nullptr;
-    fbn_lbp *s = new fbn_lbp;
-    int rc = fbn::BuildLbpModel(net->net, s->M);
-    if (rc == FBN_OK && device >= 0) {
-        s->device = device;
-        rc = [&]() -> int {
-            int r;
-            if ((r = fbn::CheckDevice(device, &s->num_cu)) || (r = Upload(s->edges, s->M.edges)) ||
-                (r = Upload(s->terms, s->M.terms)) || (r = Upload(s->bin_edge, s->M.bin_edge)) ||
-                (r = Upload(s->order, s->M.order)) ||
-                (r = Upload(s->var_off, s->M.var_off)) || (r = Upload(s->var_moff, s->M.var_moff)) ||
-                (r = Upload(s->marg_var, s->M.marg_var)) || (r = Upload(s->marg_off, s->M.marg_off)) ||
-                (r = Upload(s->self_moff, s->M.self_moff)) ||
-                (r = Upload(s->prob, s->M.prob)) || (r = Upload(s->dom, s->M.dom)) || (r = s->evcheck.ensure(8)))
-                return r;
-            FBN_HIP(hipEventCreate(&s->ev0));
-            FBN_HIP(hipEventCreate(&s->ev1));
-            return FBN_OK;
-        }();
-    }
-    if (rc) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return FBN_OK;
+    return fbn::CreateHandle(net, out, [&](fbn_lbp *s) -> int {
+        int r = fbn::BuildLbpModel(net->net, s->M);
+        if (r || device < 0) return r;
+        if ((r = s->Attach(device)) || (r = Upload(s->edges, s->M.edges)) || (r = Upload(s->terms, s->M.terms)) ||
+            (r = Upload(s->bin_edge, s->M.bin_edge)) || (r = Upload(s->order, s->M.order)) ||
+            (r = Upload(s->var_off, s->M.var_off)) || (r = Upload(s->var_moff, s->M.var_moff)) ||
+            (r = Upload(s->marg_var, s->M.marg_var)) || (r = Upload(s->marg_off, s->M.marg_off)) ||
+            (r = Upload(s->self_moff, s->M.self_moff)) || (r = Upload(s->prob, s->M.prob)))
+            return r;
+        return s->evidence.Attach(s->M.dom);
+    });
 }
 
-int fbn_lbp_destroy(fbn_lbp *s) {
-    if (!s) return FBN_OK;
-    if (s->device >= 0) {  // runs are queued on caller streams: drain those before the buffers go
-        (void)hipSetDevice(s->device);
-        for (hipStream_t st : s->streams_used) (void)hipStreamSynchronize(st);
-    }
-    delete s;
-    return FBN_OK;
-}
+int fbn_lbp_destroy(fbn_lbp *s) { return fbn::DestroyHandle(s); }
 
 int fbn_lbp_info(const fbn_lbp *s, int64_t *edges, int64_t *msg_doubles, int64_t *lds_bytes, int *path) {
     if (!s) return SetError(FBN_ERR_ARG, "null pointer");
@@ -206,10 +168,8 @@ int fbn_lbp_set_tuning(fbn_lbp *s, int64_t lds_bytes_max, int max_groups) {
 }
 
 int fbn_lbp_last_kernel_ms(const fbn_lbp *s, float *ms) {
-    if (!s || !ms || !s->timed) return SetError(FBN_ERR_ARG, "no timed launch");
-    FBN_HIP(hipEventSynchronize(s->ev1));
-    FBN_HIP(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    return FBN_OK;
+    if (!s) return SetError(FBN_ERR_ARG, "no timed launch");
+    return s->LastKernelMs(ms);
 }
 
 }  // extern "C"

@@ -3,7 +3,6 @@
 // (jt_mpe_host.cpp) and the kernel (jt_mpe.hip).  MPE has no counterpart in the reference.
 #include <hip/hip_runtime.h>
 
-#include <set>
 #include <vector>
 
 #include "fbn_device.h"
@@ -22,20 +21,12 @@ static constexpr int kMpeWavesPerCu = 8;
 // most doubles fbn_mpe_debug_messages returns
 static constexpr int64_t kMpeDebugMax = (int64_t)1 << 26;
 
-struct fbn_mpe {
+struct fbn_mpe : fbn::DeviceHandle {
     fbn::JTProgramMpe P;
-    int device = -1, num_cu = 0;
     int64_t store_bytes_max = kMpeStoreDefault;
     int max_workgroups = 0;
-    DevBuf cl, aux, initv, dig, collect, trace, dom, evcheck, store;
+    DevBuf cl, aux, initv, dig, collect, trace, store;
     DevBuf evid, assign, value, dmsg, dexp;  // staging of the host-buffer entries
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    std::set<hipStream_t> streams_used;
-    ~fbn_mpe() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
     int64_t wave_bytes() const { return P.store_rows * 64 * 8; }
 };
 
@@ -50,17 +41,13 @@ int CheckBudget(const fbn_mpe *s, int64_t budget) {
 
 int MpeDevice(fbn_mpe *s, const int8_t *d_ev, int64_t ncases, int8_t *d_assign, double *d_value, double *d_msg,
               int32_t *d_exp, hipStream_t st) {
-    s->streams_used.insert(st);
+    s->Note(st);
     // as fbn_jt_run_device's check: on the device, before anything indexes with a code; one stream sync
-    if (int rc = fbn::EvidenceCheckDevice(d_ev, ncases, s->P.V, s->dom.as<int32_t>(), s->P.dom.data(),
-                                          s->evcheck.as<unsigned long long>(), st))
-        return rc;
+    if (int rc = s->evidence.Run(d_ev, ncases, st)) return rc;
     int64_t grid = std::min<int64_t>((ncases + 63) / 64, (int64_t)s->num_cu * kMpeWavesPerCu);
     grid = std::min<int64_t>(grid, s->store_bytes_max / s->wave_bytes());
     // never more than half of the free device memory (beside what the handle holds already)
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        grid = std::min<int64_t>(grid, (int64_t)((free_b / 2 + s->store.bytes) / (size_t)s->wave_bytes()));
+    grid = fbn::ClampGridToFreeMemory(grid, (size_t)s->wave_bytes(), s->store.bytes, fbn::kMemShareHalf);
     if (s->max_workgroups > 0) grid = std::min<int64_t>(grid, s->max_workgroups);
     grid = std::max<int64_t>(grid, 1);
     if (int rc = s->store.ensure((size_t)grid * (size_t)s->wave_bytes())) return rc;
@@ -72,11 +59,7 @@ int MpeDevice(fbn_mpe *s, const int8_t *d_ev, int64_t ncases, int8_t *d_assign, 
     a.ncases = ncases, a.store_rows = s->P.store_rows;
     a.nc = (int)s->P.cl.size(), a.V = s->P.V, a.msg_rows = (int)s->P.msg_rows, a.nsep = s->P.nsep;
     a.grid = (int)grid;
-    FBN_HIP(hipEventRecord(s->ev0, st));
-    FBN_HIP(fbn_mpe_launch(&a, st));
-    FBN_HIP(hipEventRecord(s->ev1, st));
-    s->timed = true;
-    return FBN_OK;
+    return s->Timed(st, [&] { return fbn_mpe_launch(&a, st); });
 }
 
 int MpeHostBuffers(fbn_mpe *s, const int8_t *evidence, int64_t ncases, int8_t *assignment, double *value,
@@ -116,44 +99,21 @@ int fbn_mpe_create(const fbn_network *net, int device, fbn_mpe **out) {
     if (!net || !out) return SetError(FBN_ERR_ARG, "null pointer");
     *out = nullptr;
     if ((int)fbn::TopoOrder(net->net).size() != net->net.n()) return SetError(FBN_ERR_ARG, "network has a cycle");
-    fbn_mpe *s = new fbn_mpe;
-    int rc = [&]() -> int {
+    return fbn::CreateHandle(net, out, [&](fbn_mpe *s) -> int {
         fbn::JTPlanHost plan;
-        if (int r = fbn::BuildJTPlan(net->net, plan, /*forest=*/true)) return r;
-        if (int r = fbn::CompileJTProgramMpe(plan, s->P)) return r;
-        return CheckBudget(s, s->store_bytes_max);
-    }();
-    if (rc == FBN_OK && device >= 0) {
-        s->device = device;
-        rc = [&]() -> int {
-            int r;
-            if ((r = fbn::CheckDevice(device, &s->num_cu)) || (r = Upload(s->cl, s->P.cl)) ||
-                (r = Upload(s->aux, s->P.aux)) || (r = Upload(s->initv, s->P.initv)) || (r = Upload(s->dig, s->P.dig)) ||
-                (r = Upload(s->collect, s->P.collect)) || (r = Upload(s->trace, s->P.trace)) ||
-                (r = Upload(s->dom, s->P.dom)) || (r = s->evcheck.ensure(8)))
-                return r;
-            FBN_HIP(hipEventCreate(&s->ev0));
-            FBN_HIP(hipEventCreate(&s->ev1));
-            return FBN_OK;
-        }();
-    }
-    if (rc) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return FBN_OK;
+        int r;
+        if ((r = fbn::BuildJTPlan(net->net, plan, /*forest=*/true)) || (r = fbn::CompileJTProgramMpe(plan, s->P)) ||
+            (r = CheckBudget(s, s->store_bytes_max)) || device < 0)
+            return r;
+        if ((r = s->Attach(device)) || (r = Upload(s->cl, s->P.cl)) || (r = Upload(s->aux, s->P.aux)) ||
+            (r = Upload(s->initv, s->P.initv)) || (r = Upload(s->dig, s->P.dig)) ||
+            (r = Upload(s->collect, s->P.collect)) || (r = Upload(s->trace, s->P.trace)))
+            return r;
+        return s->evidence.Attach(s->P.dom);
+    });
 }
 
-int fbn_mpe_destroy(fbn_mpe *s) {
-    if (!s) return FBN_OK;
-    if (s->device >= 0) {  // runs are queued on caller streams: drain those before the buffers go
-        (void)hipSetDevice(s->device);
-        for (hipStream_t st : s->streams_used) (void)hipStreamSynchronize(st);
-    }
-    delete s;
-    return FBN_OK;
-}
+int fbn_mpe_destroy(fbn_mpe *s) { return fbn::DestroyHandle(s); }
 
 int fbn_mpe_info(const fbn_mpe *s, int64_t *cliques, int64_t *entries, int64_t *store_rows, int *components) {
     if (!s) return SetError(FBN_ERR_ARG, "null pointer");
@@ -200,10 +160,8 @@ int fbn_mpe_set_tuning(fbn_mpe *s, int max_workgroups, int64_t store_bytes_max) 
 }
 
 int fbn_mpe_last_kernel_ms(const fbn_mpe *s, float *ms) {
-    if (!s || !ms || !s->timed) return SetError(FBN_ERR_ARG, "no timed launch");
-    FBN_HIP(hipEventSynchronize(s->ev1));
-    FBN_HIP(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    return FBN_OK;
+    if (!s) return SetError(FBN_ERR_ARG, "no timed launch");
+    return s->LastKernelMs(ms);
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@ int ForwardDevice(fbn_sampler *s, int64_t n, uint64_t seed, uint8_t *d_cols, hip
     a.n = n;
     a.cols = d_cols;
     if ((n + 63) / 64 > 0x7fffffffll) return SetError(FBN_ERR_LIMIT, "forward sampling: %lld samples in one call", (long long)n);
-    s->streams_used.insert(st);
+    s->Note(st);
     return s->Timed(st, [&] { return fbn_sample_forward_launch(&a, st); });
 }
 
@@ -64,10 +64,10 @@ int LwHostBuffers(fbn_sampler *s, int method, const int8_t *evidence, int64_t nc
 extern "C" {
 
 int fbn_sampler_create(const fbn_network *net, int device, fbn_sampler **out) {
-    return fbn::CreateSamplerHandle(net, out, [&](fbn_sampler *s) { return s->Create(net->net, device, true, nullptr); });
+    return fbn::CreateHandle(net, out, [&](fbn_sampler *s) { return s->Create(net->net, device, true); });
 }
 
-int fbn_sampler_destroy(fbn_sampler *s) { return fbn::DestroySamplerHandle(s); }
+int fbn_sampler_destroy(fbn_sampler *s) { return fbn::DestroyHandle(s); }
 
 int fbn_sample_forward_device(fbn_sampler *s, int64_t n, uint64_t seed, uint8_t *d_cols, void *hip_stream) {
     if (!s || n < 0 || (n > 0 && !d_cols)) return SetError(FBN_ERR_ARG, "bad argument");
@@ -120,7 +120,7 @@ int fbn_lw_debug_samples(fbn_sampler *s, int method, const int8_t *evidence, int
 }
 
 int fbn_sampler_last_kernel_ms(const fbn_sampler *s, float *ms) {
-    if (!s || !ms || !s->timed) return SetError(FBN_ERR_ARG, "no timed launch");
+    if (!s) return SetError(FBN_ERR_ARG, "no timed launch");
     return s->LastKernelMs(ms);
 }
 

@@ -1,7 +1,8 @@
 // capi_sampler.h -- the base of the case-sampling handles fbn_sampler (capi_sample.hip), fbn_epis
 // (capi_epis.hip) and fbn_ais (capi_ais.hip): the flattened network and its uploaded tables, the
-// staging buffers of the host-buffer entries, the timing events, and the steps every device run and
-// every host-buffer run of the three takes.  What is specific to a sampler stays in its handle.
+// staging buffers of the host-buffer entries, and the steps every device run and every host-buffer run
+// of the three takes.  The device, events and streams are DeviceHandle's (fbn_device.h).  What is
+// specific to a sampler stays in its handle.
 // Internal to libfastbn.
 #ifndef FBN_CAPI_SAMPLER_H
 #define FBN_CAPI_SAMPLER_H
@@ -9,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <set>
 
 #include "fbn_device.h"
 #include "fbn_internal.h"
@@ -18,42 +18,24 @@
 
 namespace fbn {
 
-struct SamplerHandle {
+struct SamplerHandle : DeviceHandle {
     SamplerModel M;
-    int device = -1;
-    DevBuf nodes, par, prob, cdf, ent, dom, evcheck;
+    DevBuf nodes, par, prob, cdf, ent;
     DevBuf evid, labels, marg, stats, dv, dm, de, scratch;  // staging of the host-buffer entries; labels-only accumulators
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    std::set<hipStream_t> streams_used;
-    ~SamplerHandle() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
 
     // device >= 0: check it, upload the tables (the cdf rows only for the handles that read them), create
     // the events; device < 0: a host-only handle
-    int Attach(int dev, bool with_cdf, int *num_cu) {
+    int AttachTables(int dev, bool with_cdf) {
         if (dev < 0) return FBN_OK;
-        device = dev;
         int r;
-        if ((r = CheckDevice(dev, num_cu)) || (r = Upload(nodes, M.nodes)) || (r = Upload(par, M.par)) ||
-            (r = Upload(prob, M.prob)) || (with_cdf && (r = Upload(cdf, M.cdf))) || (r = Upload(ent, M.ent)) ||
-            (r = Upload(dom, M.dom)) || (r = evcheck.ensure(8)))
+        if ((r = Attach(dev)) || (r = Upload(nodes, M.nodes)) || (r = Upload(par, M.par)) ||
+            (r = Upload(prob, M.prob)) || (with_cdf && (r = Upload(cdf, M.cdf))) || (r = Upload(ent, M.ent)))
             return r;
-        FBN_HIP(hipEventCreate(&ev0));
-        FBN_HIP(hipEventCreate(&ev1));
-        return FBN_OK;
+        return evidence.Attach(M.dom);
     }
-    int Create(const Network &net, int dev, bool with_cdf, int *num_cu) {
+    int Create(const Network &net, int dev, bool with_cdf) {
         if (int rc = BuildSamplerModel(net, M)) return rc;
-        return Attach(dev, with_cdf, num_cu);
-    }
-    // runs are queued on caller streams: drain those before the buffers go
-    void Drain() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        for (hipStream_t st : streams_used) (void)hipStreamSynchronize(st);
+        return AttachTables(dev, with_cdf);
     }
     DeviceModel View() const {
         return DeviceModel{nodes.as<SampleNode>(), par.as<int32_t>(), prob.as<double>(), cdf.as<double>(),
@@ -65,10 +47,8 @@ struct SamplerHandle {
     // accumulator rows in the handle.
     int OpenRun(const int8_t *d_ev, int64_t ncases, double **d_marg, hipStream_t st) {
         if (ncases > 0x7fffffffll) return SetError(FBN_ERR_LIMIT, "%lld cases in one call", (long long)ncases);
-        streams_used.insert(st);
-        if (int rc = EvidenceCheckDevice(d_ev, ncases, M.V, dom.as<int32_t>(), M.dom.data(),
-                                         evcheck.as<unsigned long long>(), st))
-            return rc;
+        Note(st);
+        if (int rc = evidence.Run(d_ev, ncases, st)) return rc;
         if (!*d_marg) {
             if (int rc = scratch.ensure((size_t)ncases * M.sum_dom * 8)) return rc;
             *d_marg = scratch.as<double>();
@@ -89,20 +69,6 @@ struct SamplerHandle {
         a.ncases = ncases, a.S = S, a.case0 = case_offset;
         a.labels = d_labels, a.marg = d_marg, a.stats = d_stats;
         a.dv = d_dv, a.dm = d_dm, a.de = d_de;
-    }
-    // launch() -> hipError_t between the handle's two events
-    template <class Launch>
-    int Timed(hipStream_t st, Launch launch) {
-        FBN_HIP(hipEventRecord(ev0, st));
-        FBN_HIP(launch());
-        FBN_HIP(hipEventRecord(ev1, st));
-        timed = true;
-        return FBN_OK;
-    }
-    int LastKernelMs(float *ms) const {
-        FBN_HIP(hipEventSynchronize(ev1));
-        FBN_HIP(hipEventElapsedTime(ms, ev0, ev1));
-        return FBN_OK;
     }
 
     // A run on host buffers (device >= 0): stage the evidence, run, copy back.  stats_doubles: the width of
@@ -140,27 +106,6 @@ struct SamplerHandle {
         return FBN_OK;
     }
 };
-
-// the fbn_*_create / fbn_*_destroy entries of a handle H derived from SamplerHandle; init(H *) builds it
-template <class H, class Init>
-int CreateSamplerHandle(const fbn_network *net, H **out, Init init) {
-    if (!net || !out) return SetError(FBN_ERR_ARG, "null pointer");
-    *out = nullptr;
-    H *s = new H;
-    if (int rc = init(s)) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return FBN_OK;
-}
-template <class H>
-int DestroySamplerHandle(H *s) {
-    if (!s) return FBN_OK;
-    s->Drain();
-    delete s;
-    return FBN_OK;
-}
 
 }  // namespace fbn
 

@@ -18,61 +18,65 @@ struct CiBatchStats;  // pc_internal.h
 }
 using fbn::DevBuf;
 
-struct fbn_jt_plan {
+// device (host-only plans: < 0, runs fail with FBN_ERR_NODEV), events, kernel timing
+// (fbn_jt_set_kernel_timing), caller streams and the evidence check are DeviceHandle's (fbn_device.h)
+struct fbn_jt_plan : fbn::DeviceHandle {
     fbn::JTPlanHost host;
-    fbn::JTProgram prog;      // variant 1: whole case state in a global workspace
-    fbn::JTProgramLDS lprog;  // variant 0 (default): clique in flight resident in LDS
-    fbn::JTProgramV vprog;    // variant 4: streamed (virtual) tables, large trees
-    bool v_ok = false;
-    DevBuf vcl, vaux, viv, vdig, vorder, vsched, vsel;
-    fbn::JTProgramT tprog;    // variant 5: tiled, JT_T_C cases x JT_T_L entry slots per wave (fast order)
-    bool t_ok = false;
-    DevBuf tpass, ttab, tiv;
-    int device = 0, num_cu = 0, waves_per_cu = 0, variant = -1, last_variant = -1;
-    // plan-specialized kernel (variant 3)
-    bool gen_eligible = false;
-    // one loaded module (and initial-potential buffer) per arithmetic order, [0] exact, [1] fast:
-    // switching the order never unloads a module or rewrites a buffer a queued run may still use
-    struct GenKernel {
-        int state = 0;  // 0 not tried, 1 loaded, -1 failed
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        int64_t we = 0, lds = 0;
-        DevBuf iv;
-    } gen[4];  // [fast + 2 * variable-major output]
-    int64_t last_nblk = 0;  // 64-case blocks of the last run (flags of variants 3-5)
-    DevBuf flags, ws_fix;
-    bool force_fixup = false;
+    // One group per kernel variant: its host program, whether the plan is eligible, its device tables.
+    struct Interp {  // variant 1: whole case state in a global workspace
+        fbn::JTProgram prog;
+        DevBuf ops, aux, initv, dig;
+    } interp;
+    struct Lds {  // variants 0 (default interpreter) / 2, and the exact fixup of 3-5: clique in flight resident in LDS
+        fbn::JTProgramLDS prog;
+        DevBuf ops, aux, initv, dig;
+    } lds;
+    struct Streamed {  // variant 4: streamed (virtual) tables, large trees
+        fbn::JTProgramV prog;
+        bool ok = false;
+        DevBuf cl, aux, initv, dig, order, sched, sel;
+    } streamed;
+    struct Tiled {  // variant 5: tiled, JT_T_C cases x JT_T_L entry slots per wave (fast order)
+        fbn::JTProgramT prog;
+        bool ok = false;
+        DevBuf passes, tab, initv;
+    } tiled;
+    struct Gen {  // variant 3: plan-specialized kernel
+        bool eligible = false;
+        // one loaded module (and initial-potential buffer) per arithmetic order, [0] exact, [1] fast:
+        // switching the order never unloads a module or rewrites a buffer a queued run may still use
+        struct Kernel {
+            int state = 0;  // 0 not tried, 1 loaded, -1 failed
+            hipModule_t mod = nullptr;
+            hipFunction_t fn = nullptr;
+            int64_t we = 0, lds = 0;
+            DevBuf iv;
+        } k[4];  // [fast + 2 * variable-major output]
+    } gen;
+
+    // switches (the fbn_jt_set_* entries)
+    int waves_per_cu = 0, variant = -1;
     // arithmetic order of the specialized / streamed kernels: 1 = the reference's (bit-identical),
     // 0 = fast (normalizations that cancel left out, within 1e-12), -1 = auto (fast)
     int exact = -1;
-    DevBuf ops, aux, initv, dig;
-    DevBuf lops, laux, linitv, ldig;
-    DevBuf prof;       // diagnostic per-op-type cycle counters
-    bool prof_on = false;
-    int last_grid = 0;
-    DevBuf evid, labels, marg, ws;
     // fbn_jt_set_output_layout: 1 = d_marginals variable-major [SD][ncases]; kernels without a
     // variable-major store path (4, 5) write case-major into mtmp, transposed into place after
     int out_layout = 0;
-    DevBuf mtmp;
-    DevBuf ddom, evcheck;  // device-side evidence range check (fbn_jt_run, fbn_jt_run_device)
     bool ev_check = true;  // fbn_jt_set_evidence_check
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false, ktiming = true;
-    // the caller streams runs were queued on (fbn_jt_run_device returns before its kernels end):
-    // fbn_jt_plan_destroy drains these, not the whole device
-    std::vector<hipStream_t> streams_used;
-    void note_stream(hipStream_t s) {
-        for (hipStream_t u : streams_used)
-            if (u == s) return;
-        streams_used.push_back(s);
-    }
+    bool force_fixup = false;
+    // outputs and staging of fbn_jt_run; default outputs of fbn_jt_run_device
+    DevBuf evid, labels, marg, mtmp;
+    DevBuf ws;             // the main kernel's per-wave workspace
+    DevBuf ws_fix, flags;  // the fixup's workspace; one flag per 64-case block (variants 3-5)
+    // the last run
+    int last_variant = -1;
+    int64_t last_nblk = 0;  // its 64-case blocks (flags of variants 3-5)
+    DevBuf prof;            // diagnostic per-op-type cycle counters
+    bool prof_on = false;
+    int last_grid = 0;
     ~fbn_jt_plan() {
-        for (auto &k : gen)
+        for (auto &k : gen.k)
             if (k.mod) (void)hipModuleUnload(k.mod);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
     }
 };
 

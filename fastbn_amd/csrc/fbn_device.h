@@ -1,5 +1,7 @@
 // fbn_device.h -- device plumbing shared by the files that own device memory (capi_*.hip):
-// the HIP error macro, the growable buffers, the table upload, the gfx950 device check, the evidence range check.
+// the HIP error macro, the growable buffers, the table upload, the gfx950 device check, the grid clamp
+// against free memory, the evidence range check, and DeviceHandle, the base of every handle that
+// queues work on caller streams (device, timing events, streams seen, create / destroy).
 // Internal to libfastbn.
 #ifndef FBN_DEVICE_H
 #define FBN_DEVICE_H
@@ -8,6 +10,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -85,24 +88,126 @@ inline int PinnedEnsure(void *&ptr, size_t &have, size_t want) {
     return FBN_OK;
 }
 
+// the LDS of one CU: what bounds the workgroups resident on it by their LDS use
+constexpr int64_t kCuLdsBytes = 160 * 1024;
+
+// A persistent grid whose units (waves or workgroups) each own unit_bytes of workspace, kept within a
+// share (num / den) of the free device memory beside the held_bytes the workspace has already; at
+// least 1.  A unit of no bytes, or a device that does not report its memory, never clamps.
+struct MemShare {
+    size_t num, den;
+};
+constexpr MemShare kMemShare80{8, 10}, kMemShareHalf{1, 2};
+inline int64_t ClampGridToFreeMemory(int64_t grid, size_t unit_bytes, size_t held_bytes, MemShare share) {
+    size_t free_b = 0, total_b = 0;
+    if (unit_bytes == 0 || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return grid;
+    const size_t have = free_b / share.den * share.num + held_bytes;
+    return std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(have / unit_bytes)));
+}
+
 // out-of-domain evidence has no reference meaning (a code >= the node's state count would shift
 // bits into the neighbouring digit fields of the kernels' evidence masks): checked on the device
 // before any kernel indexes with it; one stream sync (the host loop cost ~1 ns per value).
-// d_ev [ncases][V]; d_dom / host_dom: the V state counts; d_word: 8 bytes of device scratch
-inline int EvidenceCheckDevice(const int8_t *d_ev, int64_t ncases, int V, const int32_t *d_dom,
-                               const int32_t *host_dom, unsigned long long *d_word, hipStream_t s) {
-    FBN_HIP(hipMemsetAsync(d_word, 0xFF, 8, s));
-    hipError_t e = fbn_jt_evidence_check(d_ev, (long long)ncases * V, V, d_dom, d_word, s);
-    if (e != hipSuccess) return SetError(FBN_ERR_HIP, "evidence check: %s", hipGetErrorString(e));
-    unsigned long long first = 0;
-    FBN_HIP(hipMemcpyAsync(&first, d_word, 8, hipMemcpyDeviceToHost, s));
-    FBN_HIP(hipStreamSynchronize(s));
-    if (first == ~0ull) return FBN_OK;
-    int8_t code = 0;
-    FBN_HIP(hipMemcpy(&code, d_ev + first, 1, hipMemcpyDeviceToHost));
-    const long long c = (long long)(first / V);
-    const int v = (int)(first % V);
-    return SetError(FBN_ERR_ARG, "case %lld: evidence %d for node %d (domain %d)", c, (int)code, v, host_dom[v]);
+// Attached once to the handle's host state counts (which outlive it); dom is their device copy.
+struct EvidenceCheck {
+    DevBuf dom, word;  // the V state counts; 8 bytes: the first offending index
+    const std::vector<int32_t> *host_dom = nullptr;
+    int Attach(const std::vector<int32_t> &h) {
+        host_dom = &h;
+        if (int rc = Upload(dom, h)) return rc;
+        return word.ensure(8);
+    }
+    // d_ev [ncases][V]
+    int Run(const int8_t *d_ev, int64_t ncases, hipStream_t s) const {
+        const int V = (int)host_dom->size();
+        unsigned long long *d_word = word.as<unsigned long long>();
+        FBN_HIP(hipMemsetAsync(d_word, 0xFF, 8, s));
+        hipError_t e = fbn_jt_evidence_check(d_ev, (long long)ncases * V, V, dom.as<int32_t>(), d_word, s);
+        if (e != hipSuccess) return SetError(FBN_ERR_HIP, "evidence check: %s", hipGetErrorString(e));
+        unsigned long long first = 0;
+        FBN_HIP(hipMemcpyAsync(&first, d_word, 8, hipMemcpyDeviceToHost, s));
+        FBN_HIP(hipStreamSynchronize(s));
+        if (first == ~0ull) return FBN_OK;
+        int8_t code = 0;
+        FBN_HIP(hipMemcpy(&code, d_ev + first, 1, hipMemcpyDeviceToHost));
+        const long long c = (long long)(first / V);
+        const int v = (int)(first % V);
+        return SetError(FBN_ERR_ARG, "case %lld: evidence %d for node %d (domain %d)", c, (int)code, v, (*host_dom)[v]);
+    }
+};
+
+// The base of a handle that owns device state: its device (-1: a host-only handle), the two events around
+// its last kernel, the evidence check, and the caller streams its runs were queued on.  A run returns
+// before its kernels end, so every entry that enqueues on a caller's stream notes it, and destroy drains
+// the noted streams (not the whole device) before the buffers go.
+struct DeviceHandle {
+    int device = -1, num_cu = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false, timing = true;  // a timed launch is recorded; launches are timed at all
+    std::set<hipStream_t> streams;
+    EvidenceCheck evidence;
+    ~DeviceHandle() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+
+    int Attach(int dev) {
+        device = dev;
+        if (int rc = CheckDevice(dev, &num_cu)) return rc;
+        FBN_HIP(hipEventCreate(&ev0));
+        FBN_HIP(hipEventCreate(&ev1));
+        return FBN_OK;
+    }
+    void Note(hipStream_t st) { streams.insert(st); }
+    void Drain() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        for (hipStream_t st : streams) (void)hipStreamSynchronize(st);
+    }
+    // the timed interval of a run: everything enqueued on st between Begin and End
+    int Begin(hipStream_t st) {
+        if (timing) FBN_HIP(hipEventRecord(ev0, st));
+        return FBN_OK;
+    }
+    int End(hipStream_t st) {
+        if (timing) FBN_HIP(hipEventRecord(ev1, st));
+        timed = timing;
+        return FBN_OK;
+    }
+    // launch() -> hipError_t between the two events
+    template <class Launch>
+    int Timed(hipStream_t st, Launch launch) {
+        if (int rc = Begin(st)) return rc;
+        FBN_HIP(launch());
+        return End(st);
+    }
+    int LastKernelMs(float *ms) const {
+        if (!ms || !timed) return SetError(FBN_ERR_ARG, "no timed launch");
+        FBN_HIP(hipEventSynchronize(ev1));
+        FBN_HIP(hipEventElapsedTime(ms, ev0, ev1));
+        return FBN_OK;
+    }
+};
+
+// the fbn_*_create / fbn_*_destroy entries of a handle H derived from DeviceHandle; init(H *) builds it
+template <class H, class Init>
+int CreateHandle(const fbn_network *net, H **out, Init init) {
+    if (!net || !out) return SetError(FBN_ERR_ARG, "null pointer");
+    *out = nullptr;
+    H *s = new H;
+    if (int rc = init(s)) {
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return FBN_OK;
+}
+template <class H>
+int DestroyHandle(H *s) {
+    if (!s) return FBN_OK;
+    s->Drain();
+    delete s;
+    return FBN_OK;
 }
 
 }  // namespace fbn
