@@ -394,7 +394,7 @@ static int CiTableCheck(const fbn_ci_ctx *c, const int32_t *it, int d, long long
 }
 
 // tests with <= 1 conditioning variable over variables with <= 4 states: popcounts of bit-sliced
-// columns (ci_bits.hip).  From kCiBitsMinSamples samples up (ALARM-5000 included: 0.46 -> 0.40 ms per
+// columns (ci_bits_count.hip).  From kCiBitsMinSamples samples up (ALARM-5000 included: 0.46 -> 0.40 ms per
 // PC run with the pair-table level 1); below, the byte-column kernel (untuned regime).
 bool CiBitsEligible(const fbn_ci_ctx *c, int maxdim) {
     return maxdim <= 4 && !fbn::KnobSet("FBN_CI_NO_BITS") &&
@@ -442,7 +442,7 @@ static int CiLaunchBits(fbn_ci_ctx *c, const CiBatchReq &q, int64_t dim_rows, hi
         pmode = 2;
     }
     // mask rows the count kernel reads: the last value of x and y (and z with pair tables)
-    // is derived, not read (ci_bits.hip)
+    // is derived, not read (ci_bits_count.hip)
     const int64_t skipped = d == 0 ? 2 : (pmode == 2 ? 3 : 0);
     S.last_bytes = (dim_rows - skipped * n) * c->bits_W * 4;
     const double *band = nullptr;  // decisions only: p evaluated inside the band

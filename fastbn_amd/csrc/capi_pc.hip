@@ -407,7 +407,7 @@ void CiSetPairsRecorded(fbn_ci_ctx *c) {
     c->pair_mode = 2;
     c->pairs_recorded = true;
 }
-// A PC run's level 1 (group size 1) entirely on the device: ci_bits.hip's ci_l1_* kernels keep every
+// A PC run's level 1 (group size 1) entirely on the device: ci_l1.hip's ci_l1_* kernels keep every
 // edge's search state in device memory, generate each round's tests from the adjacency, count them
 // from the bit-sliced store + pair tables, decide and resolve each edge's prefix in order; the host
 // enqueues rounds (next chunk x4, FBN_PC_ROUND0 / FBN_PC_GROWTH as the host driver) and reads one
@@ -753,7 +753,7 @@ int CiPCSmall(fbn_ci_ctx *c, double alpha, int depth, PCResultHost &res, Skeleto
     a.phase_base = c->small_phase;
     a.acc = reinterpret_cast<unsigned long long *>(scr + acc_off);
     a.pairtab = reinterpret_cast<int32_t *>(scr + pt_off);
-    // the level-1 information screen (exact, see ci_bits.hip; FBN_PC_NO_MISCREEN=1: off)
+    // the level-1 information screen (exact, see ci_l1.hip; FBN_PC_NO_MISCREEN=1: off)
     a.pg2 = band && !fbn::KnobSet("FBN_PC_NO_MISCREEN") ? reinterpret_cast<unsigned long long *>(scr + pg_off) : nullptr;
     a.ctx_stats = c->stats.as<unsigned long long>();
     a.dout = reinterpret_cast<PcSmallOut *>(scr + dout_off);

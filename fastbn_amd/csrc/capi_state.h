@@ -106,7 +106,7 @@ struct fbn_ci_ctx {
     std::vector<int32_t> dims;
     DevBuf cols, ddims, g2, p, counts;
     DevBuf stats;  // decision-margin log: {min |p - alpha| bits, #tests within 1e-9 of alpha}
-    // bit-sliced columns for marginal tests (ci_bits.hip), built on first use
+    // bit-sliced columns for marginal tests (ci_bits_count.hip), built on first use
     DevBuf bits, brow, browcnt;  // masks, first row of each variable, sample count per row
     DevBuf pack2;                // 2-bit packed columns (every state count <= 4), built on first use
     bool pack2_ready = false;
@@ -119,7 +119,7 @@ struct fbn_ci_ctx {
     int64_t ptask_t0 = -1, ptask_t1 = -1, ptask_n = 0;
     int pair_mode = 0;
     bool pairs_recorded = false;
-    // row Grams (ci_bits.hip ci_bits_gram): leading rows = values 0..d-2 of every variable;
+    // row Grams (ci_bits_gram.hip ci_bits_gram): leading rows = values 0..d-2 of every variable;
     // lead0[v] = v's first leading row, leadrows[r] = the bits row of leading row r
     std::vector<int32_t> row0_host, lead0_host, leadrows_host;
     DevBuf lead0, leadrows;
@@ -132,7 +132,7 @@ struct fbn_ci_ctx {
     // counts (pinned mirror), round events
     DevBuf l1pairs, l1adj, l1adjoff, l1ed, l1pos, l1st, l1sep, l1cnt, l1len, l1off, l1scal, l1open;
     DevBuf l1items, l1counts, l1df, l1indep, l1sstat;  // l1sstat: the offset scan's per-tile status words
-    // the level-1 information screen (ci_bits.hip): pairwise I of the complete graph, the kept
+    // the level-1 information screen (ci_l1.hip): pairwise I of the complete graph, the kept
     // candidates' positions, the screen's scan status words
     DevBuf l1mi, l1pcnt, l1plist, l1sstat2;
     // level 0's G^2 of every pair written into l1mi by the recording batches (pairs [0, covered) in

@@ -1,7 +1,7 @@
 // ci_args.h -- the argument records of the CI kernels' launchers (launchers.h): what capi_ci.hip and
-// capi_pc.hip fill, field by field, and ci_kernels.hip / ci_bits.hip read.  CiArgs is also the
-// histogram kernel's by-value parameter; the other two are host-only (their kernels keep flat
-// parameter lists).  Internal to libfastbn.
+// capi_pc.hip fill, field by field, and ci_kernels.hip / ci_bits_*.hip / ci_l1.hip read.  CiArgs,
+// CiG2Args and CiL1Args are also by-value kernel parameters (the histogram kernel, the bit-sliced
+// G^2 passes, the level-1 setup and resolve); CiBitsArgs is host-only.  Internal to libfastbn.
 #ifndef FBN_CI_ARGS_H
 #define FBN_CI_ARGS_H
 
@@ -46,7 +46,7 @@ struct CiArgs {
     long long tstride;
     int split;
     // MODE 3 (d = 2, bit-sliced, derived): the pair tables of this PC run's level 0 (every pair u < v
-    // of the nvars variables, [value of u][value of v], ci_bits.hip pair_table)
+    // of the nvars variables, [value of u][value of v], ci_bits_count.hip pair_table)
     const int32_t *pairtab;
     int nvars;
     int dbg;  // diagnostic ablations, 0 from every launcher: bit 0 = MODE 3 skips its counting
@@ -77,8 +77,28 @@ struct CiBitsArgs {
     int nband;
 };
 
+// ci_bits_g2 / ci_bits_g2q's parameter (ci_bits_g2.hip): the G^2 pass over n count records
+struct CiG2Args {
+    const int32_t *counts;  // [n][64]
+    const int32_t *dims;
+    const int32_t *items;  // [n][2+d]; null (d = 0): test t is pair t0 + t of the complete graph over nvars
+    long long n, t0;
+    int nvars;
+    double alpha;
+    double *g2;  // optional outputs: g2, p, counts0 (the table of test 0)
+    int32_t *df;
+    double *p;
+    uint8_t *indep;
+    int32_t *counts0;
+    unsigned long long *stats;  // optional: the decision-margin log
+    const double *band;         // optional, used when p == nullptr
+    int nband;
+    const long long *n_dev;  // non-null: the test count is read on the device (batches generated there)
+};
+
 // fbn_ci_l1_setup and fbn_ci_l1_round: the device-resident level-1 search.  Filled once per level;
-// what changes per round (open_cnt, open_next, next_chunk, epoch) is passed beside it.
+// what changes per round (open_cnt, open_next, next_chunk, epoch) is passed beside it.  Also the
+// parameter of ci_l1_setup and ci_l1_resolve (ci_l1.hip).
 struct CiL1Args {
     // the level's edges and adjacency (CSR)
     const int32_t *pairs;

@@ -1,4 +1,4 @@
-// ci_chisq.h -- the chi-square p-value of a G^2 test, shared by ci_kernels.hip and ci_bits.hip.
+// ci_chisq.h -- the chi-square p-value of a G^2 test, evaluated through ci_g2.h by every CI kernel.
 //
 // The reference computes p = 1.0 - stats::pchisq(g2, df) (src/IndependenceTest.cpp:146,268,355);
 // pchisq lives in the un-vendored lib/stats submodule (parity unpinned).  Restated

@@ -3,7 +3,7 @@
 // Level 0 of the skeleton search tests every pair of the complete graph marginally
 // (reference: src/PCStable.cpp level-0 loop -> IndependenceTest::IsIndependent -> Counts2D::FillTable,
 // src/CellTable.cpp:23-91).  Every pair's table follows from popcount(r_i & r_j) over the leading
-// value rows r of the two variables (ci_bits.hip), i.e. from the Gram G = O O^T of the 0/1 matrix
+// value rows r of the two variables (ci_bits_count.hip), i.e. from the Gram G = O O^T of the 0/1 matrix
 // O[leading row][sample].  Here O is stored as FP4 (E2M1: 1.0 = nibble 0x2, 0.0 = 0x0, two
 // samples per byte) and G is formed with v_mfma_scale_f32_32x32x64_f8f6f4 (FP4 x FP4, fp32
 // accumulate: products are 0/1 and a K-slice of <= 65535 samples sums exactly in fp32), the

@@ -19,7 +19,8 @@
 
 #include <algorithm>
 
-#include "ci_chisq.h"
+#include "ci_g2.h"
+#include "ci_wave.h"
 #include "fbn_device.h"
 #include "launchers.h"
 
@@ -60,12 +61,6 @@ __device__ __forceinline__ int pair_at(const int32_t *__restrict__ pairtab, int 
     const int i = u < v ? u : v, j = u < v ? v : u;
     const int32_t *T = pairtab + 16 * fbn_pair_index(i, j, nvars);
     return u < v ? T[a * dims[v] + b] : T[b * dims[u] + a];
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // the leading cells of one test (see above) for MX = dx - 1, MY = dy - 1, M2 = dz2 - 1 values: wave
@@ -433,9 +428,7 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
 #pragma unroll
                         for (int b = 0; b < 4; ++b) {
                             if (c >= dl || a >= dx || b >= dy) continue;
-                            uint32_t v = cnt[c][a * 4 + b];
-#pragma unroll
-                            for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+                            const uint32_t v = wave_sum(cnt[c][a * 4 + b]);
                             if (lane == 0) hist[(pfx * dl + c) * dxy + a * dy + b] = (int32_t)v;
                         }
             }
@@ -547,9 +540,7 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
         if (packed) {  // wave reduction of the packed counters, one LDS add per cell per wave
             for (int c = 0; c < cells; ++c) {
                 const unsigned long long w = (c >> 2) == 0 ? a0 : (c >> 2) == 1 ? a1 : (c >> 2) == 2 ? a2 : a3;
-                int v = (int)((w >> ((c & 3) << 4)) & 0xFFFFull);
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+                const int v = wave_sum((int)((w >> ((c & 3) << 4)) & 0xFFFFull));
                 if (lane == 0 && v) atomicAdd(&hist[c], v);
             }
         }
@@ -591,9 +582,7 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
             int alx = 0, aly = 0, total = 0;
             for (int i = 0; i < dx; ++i) alx += ni[k * dx + i] > 0, total += ni[k * dx + i];
             for (int j = 0; j < dy; ++j) aly += nj[k * dy + j] > 0;
-            alx = alx >= 1 ? alx : 1;
-            aly = aly >= 1 ? aly : 1;
-            dfp[k] = (alx - 1) * (aly - 1);
+            dfp[k] = fbn_g2_slice_df(alx, aly);
             nk[k] = total;
         }
         __syncthreads();
@@ -604,13 +593,7 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
         // rest (near alpha) add in order below.
         auto term_of = [&](int c) {
             const int k = c / dxy, i = (c / dy) % dx, j = c % dy;
-            const long total = nk[k], sum_row = ni[k * dx + i], sum_col = nj[k * dy + j], observed = hist[c];
-            double t = 0.0;
-            if (total != 0 && sum_row != 0 && sum_col != 0 && observed != 0) {
-                const double expected = (double)sum_col * (double)sum_row / (double)total;
-                t = 2.0 * observed * log(observed / expected);
-            }
-            return t;
+            return fbn_g2_term(hist[c], ni[k * dx + i], nj[k * dy + j], nk[k]);
         };
         __shared__ double sred[2 * NW];
         __shared__ int sdf[NW], sdec;
@@ -623,12 +606,7 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
                 pa += fabs(t);
             }
             for (int k = tid; k < dimz; k += BS) pdf += dfp[k];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                ps += __shfl_xor(ps, o);
-                pa += __shfl_xor(pa, o);
-                pdf += __shfl_xor(pdf, o);
-            }
+            ps = wave_sum(ps), pa = wave_sum(pa), pdf = wave_sum(pdf);
             if (lane == 0) sred[2 * (tid >> 6)] = ps, sred[2 * (tid >> 6) + 1] = pa, sdf[tid >> 6] = pdf;
             __syncthreads();
             if (tid == 0) {
@@ -637,7 +615,9 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
                 int df = sdf[0] + sdf[1] + sdf[2] + sdf[3];
 #pragma unroll
                 for (int w = 4; w < NW; ++w) gs += sred[2 * w], ga += sred[2 * w + 1], df += sdf[w];
-                const double err = (cells + 64) * 2.3e-16 * ga;
+                // (fbn_g2_decide_tree written out: through the helper every instantiation takes 2 more
+                // VGPRs, and six of the 2-bit-column ones drop from 6 to 5 waves per SIMD)
+                const double err = fbn_g2_tree_err(cells, ga);
                 int dec = -1;  // 0 dependent, 1 independent, -1 in-order sum
                 double pd = -1.0;  // p of a decision past the band's df range
                 if (df == 0) dec = 1;  // src/IndependenceTest.cpp:140-142
@@ -647,20 +627,17 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
                     // p decreases in G^2 and the in-order sum lies in [gs - err, gs + err]: p at
                     // both ends on the same side of alpha (by a relative 1e-12 more than the
                     // evaluation's own rounding) decides as the in-order sum would
-                    const double phi = fbn_chisq_pvalue(gs - err > 0.0 ? gs - err : 0.0, df), plo = fbn_chisq_pvalue(gs + err, df);
+                    const double phi = fbn_g2_pvalue(gs - err > 0.0 ? gs - err : 0.0, df), plo = fbn_g2_pvalue(gs + err, df);
                     if (plo > A.alpha * (1.0 + 1e-12)) dec = 1, pd = plo;
                     else if (phi < A.alpha * (1.0 - 1e-12)) dec = 0, pd = phi;
                 }
                 if (dec >= 0) {
+                    // (a band decision's margin as this kernel logs it: |(alpha +- delta) - alpha|)
                     const double p = df == 0 ? 1.0 : pd >= 0.0 ? pd
                                                  : dec ? A.alpha + A.band[2 * A.nband] : A.alpha - A.band[2 * A.nband];
                     if (A.df) A.df[it] = df;
                     if (A.indep) A.indep[it] = dec;
-                    if (A.stats) {
-                        const double m = fabs(p - A.alpha);
-                        atomicMin(A.stats, (unsigned long long)__double_as_longlong(m));
-                        if (m < 1e-9) atomicAdd(A.stats + 1, 1ull);
-                    }
+                    if (A.stats) fbn_margin_log(A.stats, fabs(p - A.alpha));
                 }
                 sdec = dec;
             }
@@ -693,30 +670,12 @@ __global__ __launch_bounds__(BS, der2_waves(MODE)) void ci_g2_kernel(CiArgs A) {
         if (tid == 0) {
             int df = 0;
             for (int k = 0; k < dimz; ++k) df += dfp[k];
-            double p;
-            bool ind;
-            if (df == 0) {  // src/IndependenceTest.cpp:140-142, 349-351
-                p = 1.0;
-                ind = true;
-            } else if (!A.p && A.band && df <= A.nband && g2 < A.band[2 * df - 2]) {
-                p = A.alpha + A.band[2 * A.nband];  // p > alpha + delta: logged as margin delta
-                ind = true;
-            } else if (!A.p && A.band && df <= A.nband && g2 > A.band[2 * df - 1]) {
-                p = A.alpha - A.band[2 * A.nband];
-                ind = false;
-            } else {
-                p = fbn_chisq_pvalue(g2, df);
-                ind = p > A.alpha;
-            }
+            const G2Decision r = fbn_g2_decide(g2, df, A.alpha, A.band, A.nband, A.p != nullptr);
             if (A.g2) A.g2[it] = g2;
             if (A.df) A.df[it] = df;
-            if (A.p) A.p[it] = p;
-            if (A.indep) A.indep[it] = ind;
-            if (A.stats) {
-                const double m = fabs(p - A.alpha);
-                atomicMin(A.stats, (unsigned long long)__double_as_longlong(m));
-                if (m < 1e-9) atomicAdd(A.stats + 1, 1ull);
-            }
+            if (A.p) A.p[it] = r.p;
+            if (A.indep) A.indep[it] = r.ind;
+            if (A.stats) fbn_margin_log(A.stats, fabs(r.p - A.alpha));
         }
         __syncthreads();
     }

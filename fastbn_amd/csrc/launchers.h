@@ -1,8 +1,8 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
-// defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits.hip,
+// defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
 // ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
-// takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiL1Args),
+// takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
 // Internal to libfastbn.  (pc_small.h and param_counts.h carry their own kernels' launchers.)
 #ifndef FBN_LAUNCHERS_H

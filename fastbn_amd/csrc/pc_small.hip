@@ -37,7 +37,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "ci_chisq.h"
+#include "ci_g2.h"
 #include "pc_small.h"
 
 using namespace fbn;
@@ -300,39 +300,12 @@ __device__ __forceinline__ double wave_inorder_add(double g, double t) {
     return g;
 }
 
-// ---- G^2 decision, shared by the wave and workgroup paths.  The reference (src/IndependenceTest.cpp
-// :94-155, 295-364) forms G^2 as one running sum over cells z -> x -> y and p = 1 - pchisq(G^2, df),
-// independent iff p > alpha (df == 0: independent, p = 1).  `gs` / `ga` = tree sum of the terms and
-// of their magnitudes: with the decision band [lo, hi] (ci_chisq.h) a tree sum clearing it by the
-// tree-vs-in-order error bound decides exactly; otherwise *need_inorder and the caller sums in order.
-struct Decision {
-    int ind;        // -1: undecided (in-order sum needed)
-    double margin;  // |p - alpha| as logged
-};
-
-__device__ __forceinline__ Decision decide_tree(double gs, double ga, int df, int cells, const PcSmallArgs &A,
-                                                const double *band) {
-    if (df == 0) return Decision{1, fabs(1.0 - A.alpha)};
-    if (A.band && df <= A.nband) {
-        const double err = (cells + 64) * 2.3e-16 * ga;
-        if (gs + err < band[2 * df - 2]) return Decision{1, band[2 * A.nband]};
-        if (gs - err > band[2 * df - 1]) return Decision{0, band[2 * A.nband]};
-    }
-    return Decision{-1, 0.0};
-}
-
-__device__ __noinline__ Decision decide_exact(double g2, int df, const PcSmallArgs &A, const double *band) {
-    if (df == 0) return Decision{1, fabs(1.0 - A.alpha)};
-    if (A.band && df <= A.nband && g2 < band[2 * df - 2]) return Decision{1, band[2 * A.nband]};
-    if (A.band && df <= A.nband && g2 > band[2 * df - 1]) return Decision{0, band[2 * A.nband]};
-    const double p = fbn_chisq_pvalue(g2, df);
-    return Decision{p > A.alpha ? 1 : 0, fabs(p - A.alpha)};
-}
-
-__device__ __forceinline__ double g2_term(long observed, long sum_row, long sum_col, long total) {
-    if (total == 0 || sum_row == 0 || sum_col == 0 || observed == 0) return 0.0;
-    const double expected = (double)sum_col * (double)sum_row / (double)total;
-    return 2.0 * observed * log(observed / expected);
+// ---- G^2 decision, shared by the wave and workgroup paths: ci_g2.h's.  A test first tries the tree
+// sum `gs` of its terms (`ga`: of their magnitudes) against the decision band (fbn_g2_decide_tree);
+// undecided, it sums in order and decides exactly (fbn_g2_decide; p itself is never returned here).
+// The band is read from its LDS copy; A.band == nullptr means none.
+__device__ __forceinline__ const double *band_of(const PcSmallArgs &A, const Lds &L) {
+    return A.band ? L.band : nullptr;
 }
 
 // ---- one test per wave on the bit-sliced store (d = 0: marginal; d = 1: one conditioning
@@ -351,7 +324,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 template <int D>
-__device__ __forceinline__ Decision wave_test(const PcSmallArgs &A, const Lds &L, int x, int y, int z, int lane,
+__device__ __forceinline__ G2Decision wave_test(const PcSmallArgs &A, const Lds &L, int x, int y, int z, int lane,
                                            bool record_pair, int32_t *tab, int32_t *aux, unsigned long long *ph) {
     const unsigned long long c0 = A.trace ? clock64() : 0;
     const int n = A.nvars;
@@ -480,7 +453,7 @@ __device__ __forceinline__ Decision wave_test(const PcSmallArgs &A, const Lds &L
     for (int k = 0; k < dz; ++k) {  // wave-uniform
         const int alx = __popcll((nzx >> (k * dx)) & ((1ull << dx) - 1)),
                   aly = __popcll((nzy >> (k * dy)) & ((1ull << dy) - 1));
-        df += ((alx >= 1 ? alx : 1) - 1) * ((aly >= 1 ? aly : 1) - 1);
+        df += fbn_g2_slice_df(alx, aly);
     }
     double t = 0.0;
     if (live) {
@@ -493,15 +466,15 @@ __device__ __forceinline__ Decision wave_test(const PcSmallArgs &A, const Lds &L
             for (int i = 0; i < 4; ++i) q[i] = i < dx ? nxz(i, c) : 0;  // independent loads
             tot = (long)q[0] + q[1] + q[2] + q[3];
         }
-        t = g2_term(ob, nxz(a, c), nyz(b, c), tot);
+        t = fbn_g2_term(ob, nxz(a, c), nyz(b, c), tot);
     }
     const double gs = wsum_f64(t), ga = wsum_f64(fabs(t));
     if (D == 0 && record_pair && A.pg2 && lane == 0)  // G^2 = 2N I(X;Y): the level-1 screen's input
         __hip_atomic_store(A.pg2 + pair_index(n, x, y), (unsigned long long)__double_as_longlong(gs), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
-    Decision r = decide_tree(gs, ga, df, cells, A, L.band);
+    G2Decision r = fbn_g2_decide_tree(gs, ga, df, cells, A.alpha, band_of(A, L), A.nband);
     if (r.ind < 0) {  // in the band: the reference's in-order running sum, then p
-        r = decide_exact(wave_inorder_add(0.0, t), df, A, L.band);  // lane l = cell l (t = 0 beyond)
+        r = fbn_g2_decide(wave_inorder_add(0.0, t), df, A.alpha, band_of(A, L), A.nband, false);  // lane l = cell l (t = 0 beyond)
     }
     wave_lds_sync();  // the slot is reused by the wave's next test
     if (A.trace && lane == 0) {
@@ -511,7 +484,7 @@ __device__ __forceinline__ Decision wave_test(const PcSmallArgs &A, const Lds &L
     return r;
 }
 
-// ---- the level-1 information screen (the argument: ci_bits.hip, l1_plausible).  In G^2 units:
+// ---- the level-1 information screen (the argument: ci_l1.hip, l1_plausible).  In G^2 units:
 // with G^2_uv = 2N I(U;V) from level 0, the test (x, y | z) can be independent only if G^2_xz and
 // G^2_yz are both >= G^2_xy - hi(df) - margins, df = (dx-1)(dy-1)dz (hi: the decision band's upper
 // end, which every independent test's G^2 stays below).  false = certainly dependent (not run).
@@ -532,7 +505,7 @@ __device__ __forceinline__ bool screen_plausible(const PcSmallArgs &A, const Lds
 // nk[64] dfp[64]); z index with the LAST conditioning variable fastest (src/CellTable.cpp:39-51,
 // 277-281); G^2 as block_test, the in-order fallback 64 terms at a time
 template <int D>
-__device__ __noinline__ Decision wave_hist_test(const PcSmallArgs &A, const Lds &L, int x, int y, const int *z,
+__device__ __noinline__ G2Decision wave_hist_test(const PcSmallArgs &A, const Lds &L, int x, int y, const int *z,
                                                 int lane, int32_t *wh, unsigned long long *ph) {
     const unsigned long long c0 = A.trace ? clock64() : 0;
     const int dx = L.dims[x], dy = L.dims[y];
@@ -619,14 +592,14 @@ __device__ __noinline__ Decision wave_hist_test(const PcSmallArgs &A, const Lds 
         int alx = 0, aly = 0, tot = 0;
         for (int i = 0; i < dx; ++i) alx += ni[k * dx + i] > 0, tot += ni[k * dx + i];
         for (int j = 0; j < dy; ++j) aly += nj[k * dy + j] > 0;
-        dfp[k] = ((alx >= 1 ? alx : 1) - 1) * ((aly >= 1 ? aly : 1) - 1);
+        dfp[k] = fbn_g2_slice_df(alx, aly);
         nk[k] = tot;
     }
     wave_lds_sync();
     const unsigned long long c2 = A.trace ? clock64() : 0;
     auto term_of = [&](int c) {
         const int k = c / dxy, i = (c / dy) % dx, j = c % dy;
-        return g2_term(hist[c], ni[k * dx + i], nj[k * dy + j], nk[k]);
+        return fbn_g2_term(hist[c], ni[k * dx + i], nj[k * dy + j], nk[k]);
     };
     double ps = 0.0, pa = 0.0;
     int df = 0;
@@ -639,14 +612,14 @@ __device__ __noinline__ Decision wave_hist_test(const PcSmallArgs &A, const Lds 
     ps = wsum_f64(ps);
     pa = wsum_f64(pa);
     df = wsum_i32(df);
-    Decision r = decide_tree(ps, pa, df, cells, A, L.band);
+    G2Decision r = fbn_g2_decide_tree(ps, pa, df, cells, A.alpha, band_of(A, L), A.nband);
     if (r.ind < 0) {  // in-order running sum over z -> x -> y, 64 terms at a time
         double g2 = 0.0;
         for (int c0 = 0; c0 < cells; c0 += 64) {
             const double t = c0 + lane < cells ? term_of(c0 + lane) : 0.0;
             g2 = wave_inorder_add(g2, t);
         }
-        r = decide_exact(g2, df, A, L.band);
+        r = fbn_g2_decide(g2, df, A.alpha, band_of(A, L), A.nband, false);
     }
     wave_lds_sync();  // the region is reused by the wave's next test
     if (A.trace && lane == 0) {
@@ -659,7 +632,7 @@ __device__ __noinline__ Decision wave_hist_test(const PcSmallArgs &A, const Lds 
 // ---- one test per workgroup (d >= 2): LDS histogram of the 2-bit packed columns.  z index with
 // the LAST conditioning variable fastest (src/CellTable.cpp:39-51, 277-281).
 template <int D>
-__device__ __noinline__ Decision block_test(const PcSmallArgs &A, int x, int y, const int *z, Lds &L) {
+__device__ __noinline__ G2Decision block_test(const PcSmallArgs &A, int x, int y, const int *z, Lds &L) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const unsigned long long c0 = A.trace ? clock64() : 0;
     const int dx = L.dims[x], dy = L.dims[y];
@@ -733,14 +706,14 @@ __device__ __noinline__ Decision block_test(const PcSmallArgs &A, int x, int y, 
         int alx = 0, aly = 0, tot = 0;
         for (int i = 0; i < dx; ++i) alx += L.ni[k * dx + i] > 0, tot += L.ni[k * dx + i];
         for (int j = 0; j < dy; ++j) aly += L.nj[k * dy + j] > 0;
-        L.dfp[k] = ((alx >= 1 ? alx : 1) - 1) * ((aly >= 1 ? aly : 1) - 1);
+        L.dfp[k] = fbn_g2_slice_df(alx, aly);
         L.nk[k] = tot;
     }
     __syncthreads();
     const unsigned long long c2 = A.trace ? clock64() : 0;
     auto term_of = [&](int c) {
         const int k = c / dxy, i = (c / dy) % dx, j = c % dy;
-        return g2_term(hist[c], L.ni[k * dx + i], L.nj[k * dy + j], L.nk[k]);
+        return fbn_g2_term(hist[c], L.ni[k * dx + i], L.nj[k * dy + j], L.nk[k]);
     };
     double ps = 0.0, pa = 0.0;
     int pdf = 0;
@@ -759,7 +732,7 @@ __device__ __noinline__ Decision block_test(const PcSmallArgs &A, int x, int y, 
     int df = 0;
 #pragma unroll
     for (int w = 0; w < NWAVE; ++w) gs += L.red[2 * w], ga += L.red[2 * w + 1], df += L.redi[w];
-    Decision r = decide_tree(gs, ga, df, cells, A, L.band);
+    G2Decision r = fbn_g2_decide_tree(gs, ga, df, cells, A.alpha, band_of(A, L), A.nband);
     if (r.ind < 0) {  // in-order running sum over z -> x -> y, chunk by chunk (terms in LDS)
         double g2 = 0.0;
         for (int c0 = 0; c0 < cells; c0 += kTermChunk) {
@@ -772,7 +745,7 @@ __device__ __noinline__ Decision block_test(const PcSmallArgs &A, int x, int y, 
         }
         if (tid == 0) L.g2 = g2;
         __syncthreads();
-        r = decide_exact(L.g2, df, A, L.band);
+        r = fbn_g2_decide(L.g2, df, A.alpha, band_of(A, L), A.nband, false);
     }
     if (A.trace && tid == 0) {
         const unsigned long long c3 = clock64();
@@ -969,7 +942,7 @@ __global__ __launch_bounds__(BS) void pc_small_kernel(PcSmallArgs Ak, Barrier B)
                     if ((fg != ~0u && fg < (unsigned)k) || (fl != ~0u && fl < (unsigned)k)) continue;
                 }
                 const int x = L.ex[e], y = L.ey[e];
-                Decision r;
+                G2Decision r;
                 if (d == 0) {
                     r = wave_test<0>(A, L, x, y, 0, lane, true, L.wtab[wv], L.waux[wv], L.ph[wv]);
                 } else {
@@ -1003,7 +976,7 @@ __global__ __launch_bounds__(BS) void pc_small_kernel(PcSmallArgs Ak, Barrier B)
                 const int x = L.ex[e], y = L.ey[e];
                 int zz[kSmallMaxD];
                 unrank(L, x, y, d, k, zz);
-                Decision r;
+                G2Decision r;
                 r = d == 3 ? block_test<3>(A, x, y, zz, L) : block_test<4>(A, x, y, zz, L);
                 if (tid == 0) {
                     ++launched;

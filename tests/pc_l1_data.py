@@ -1,4 +1,4 @@
-"""Seeded datasets that steer the device level-1 search of PC-stable (ci_bits.hip's round machine:
+"""Seeded datasets that steer the device level-1 search of PC-stable (ci_l1.hip's round machine:
 ci_l1_setup / ci_l1_gen / ci_l1_resolve / l1_tile_scan, and the level 0 -> 1 hand-off ci_kept_*)
 to its round, clip, tile and 1,024-variable edges.  Plain numpy: no project library, no GPU.
 

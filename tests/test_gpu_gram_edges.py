@@ -1,4 +1,4 @@
-"""The level-0 Gram kernels at their own edges (ci_gram_mfma.hip, ci_bits.hip; shapes, reference and
+"""The level-0 Gram kernels at their own edges (ci_gram_mfma.hip, ci_bits_gram.hip; shapes, reference and
 restated split rule: tests/gram_edges.py).  Every pair table of the complete graph, through the
 poisoned debug entry (IndependenceTest.level0_range_counts: an unwritten Gram entry reads -1), equals
 the float64 one-hot matmul reference exactly, and level0_info() confirms the kernel and the split

@@ -241,7 +241,7 @@ def test_decision_margin_log(alarm_ds, alarm_paths):
 
 @pytest.mark.parametrize("ns", [1, 31, 32, 33, 5000, 100003])
 def test_bit_sliced_marginal_tests_match_histogram_kernel(ns):
-    """Tests with <= 1 conditioning variable go through the bit-sliced popcount kernel (ci_bits.hip)
+    """Tests with <= 1 conditioning variable go through the bit-sliced popcount kernels (ci_bits_count.hip, ci_bits_g2.hip)
     when every variable has <= 4 states; the byte-column histogram kernel (FBN_CI_NO_BITS) must give identical counts,
     df, G^2 and p, and both must match the oracle.  Ragged sample counts, constant columns and
     1..4-state variables."""
@@ -498,7 +498,7 @@ def test_level0_to_level1_on_device_matches_host_path(nvars, ns, monkeypatch):
 
 
 def test_level1_information_screen_config5(monkeypatch):
-    """The level-1 information screen (ci_bits.hip l1_plausible: a candidate z with I(X;Z) or I(Y;Z)
+    """The level-1 information screen (ci_l1.hip l1_plausible: a candidate z with I(X;Z) or I(Y;Z)
     below I(X;Y) - hi(df) / 2N is certainly dependent and not run) on config 5 at full size: the same
     counted tests, skeleton, sepsets and orientation as every candidate run (FBN_PC_NO_MISCREEN), both
     equal to the fixture; level 1 runs far fewer tests than it counts."""

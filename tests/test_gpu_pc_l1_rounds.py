@@ -1,4 +1,4 @@
-"""The device-resident level-1 search of PC-stable (ci_bits.hip ci_l1_setup / ci_l1_gen /
+"""The device-resident level-1 search of PC-stable (ci_l1.hip ci_l1_setup / ci_l1_gen /
 ci_l1_resolve / l1_tile_scan, driven by capi_pc.hip CiLevel1Run) and the level 0 -> 1 hand-off
 (ci_kept_count / ci_kept_scan / ci_kept_fill) at their round, clip, tile and 1,024-variable edges,
 against the restatement at depth 2 (levels 0 and 1): tests per level, skeleton and sepsets.

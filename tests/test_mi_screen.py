@@ -1,4 +1,4 @@
-"""The level-1 information screen (ci_bits.hip `l1_plausible`) checked against the oracle's own test
+"""The level-1 information screen (ci_l1.hip `l1_plausible`) checked against the oracle's own test
 log, on the CPU: every level-1 test the reference's algorithm finds INDEPENDENT passes the screen,
 so the candidates the screen skips are dependent and the device's counted tests, edges and sepsets
 stay the reference's (src/PCStable.cpp:465-551).  The screen's argument: with plug-in mutual
@@ -21,7 +21,7 @@ def _crit(df):
 
 
 def _plausible(mi, dims, n, x, y, z):
-    """The device predicate (ci_bits.hip l1_plausible) with the chi-square quantile for the band's hi."""
+    """The device predicate (ci_l1.hip l1_plausible) with the chi-square quantile for the band's hi."""
     df = (dims[x] - 1) * (dims[y] - 1) * dims[z]
     if df <= 0:
         return True
