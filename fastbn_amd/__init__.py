@@ -25,6 +25,8 @@ reference's names and argument meaning:
   :149-160): samplers that learn their importance function from their own weighted samples
 * ``MostProbableExplanation(network).infer(evidence)`` -- the complete assignment argmax_x P(x, e) and its
   log-probability, exact, by max-product on the junction forest (no reference counterpart)
+* ``ExpectationMaximization(network).fit(data)`` -- the CPTs of a known structure from rows with missing
+  cells (-1), by EM with exact junction-forest E-steps on the device (no reference counterpart)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -45,6 +47,7 @@ from .api import (  # noqa: F401
     AISBN,
     SelfImportanceSampling,
     MostProbableExplanation,
+    ExpectationMaximization,
     score_marginals,
     family_sizes,
     pdag_to_dag,
@@ -59,6 +62,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

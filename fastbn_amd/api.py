@@ -20,6 +20,8 @@ _SIGS = {
     "fbn_network_load_xmlbif": [_cstr, _pp],
     "fbn_network_create": [C.c_int, _vp, _vp, _vp, _vp, _vp, _pp],
     "fbn_network_node_counts": [_vp, C.c_int, _vp, _vp, _vp, _vp],
+    "fbn_network_create_cpt": [C.c_int, _vp, _vp, _vp, _vp, _vp, _pp],
+    "fbn_network_node_probs": [_vp, C.c_int, _vp, _vp, _vp, _vp],
     "fbn_network_num_nodes": [_vp, _vp],
     "fbn_network_dims": [_vp, _vp],
     "fbn_network_name": [_vp, C.c_int, C.c_char_p, C.c_int],
@@ -154,6 +156,17 @@ _SIGS = {
     "fbn_mpe_debug_messages": [_vp, _vp, _i64, _vp, _vp],
     "fbn_mpe_set_tuning": [_vp, C.c_int, _i64],
     "fbn_mpe_last_kernel_ms": [_vp, _vp],
+    "fbn_em_create": [_vp, C.c_int, _pp],
+    "fbn_em_destroy": [_vp],
+    "fbn_em_info": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "fbn_em_estep": [_vp, _vp, _i64, _vp, _vp],
+    "fbn_em_estep_device": [_vp, _vp, _i64, _vp, _vp, _vp],
+    "fbn_em_run": [_vp, _vp, _i64, C.c_int, _dbl, _dbl, _vp, _vp],
+    "fbn_em_set_parameters": [_vp, _vp],
+    "fbn_em_network": [_vp, _pp],
+    "fbn_em_debug_posteriors": [_vp, _vp, _i64, _vp],
+    "fbn_em_set_tuning": [_vp, C.c_int, _i64],
+    "fbn_em_last_kernel_ms": [_vp, _vp],
 }
 
 
@@ -214,6 +227,7 @@ lib = _Lib()
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
                 "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2, "MostProbableExplanation": 2,
+                "ExpectationMaximization": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -311,6 +325,36 @@ class Network(_Handle):
         lib.fbn_network_create(n, _p(d), _p(off), _p(par), _p(cnt), C.cast(nm, C.c_void_p) if nm is not None else None,
                                C.byref(h))
         return cls(_handle=h)
+
+    @classmethod
+    def from_cpts(cls, dims, parents, cpts, names=None):
+        """A network that holds probabilities (fbn_network_create_cpt): as from_counts with cpts[v] = fp64
+        [dims[v]][parent configs]; every entry finite and > 0, every column summing to 1 within 1e-9."""
+        n = len(dims)
+        d = np.ascontiguousarray(dims, np.int32)
+        off = np.zeros(n + 1, np.int32)
+        for v in range(n):
+            off[v + 1] = off[v] + len(parents[v])
+        par = np.ascontiguousarray([q for ps in parents for q in ps] or [0], np.int32)
+        tab = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float64).reshape(-1) for c in cpts]), np.float64)
+        nm = None
+        if names is not None:
+            enc = [os.fsencode(x) for x in names]
+            nm = (C.c_char_p * n)(*enc)
+        h = C.c_void_p()
+        lib.fbn_network_create_cpt(n, _p(d), _p(off), _p(par), _p(tab),
+                                   C.cast(nm, C.c_void_p) if nm is not None else None, C.byref(h))
+        return cls(_handle=h)
+
+    def node_probs(self, v):
+        """(parents ascending, probabilities fp64 [dims[v]][parent configs]) of node v: a probability
+        network's entries, or a count network's (count + 1) / (total + dims[v])."""
+        npar, n = C.c_int(), C.c_int64()
+        lib.fbn_network_node_probs(self._h, int(v), None, None, C.byref(npar), C.byref(n))
+        par = np.zeros(max(1, npar.value), np.int32)
+        pr = np.zeros(max(1, n.value), np.float64)
+        lib.fbn_network_node_probs(self._h, int(v), _p(par), _p(pr), C.byref(npar), C.byref(n))
+        return par[:npar.value], pr[:n.value].reshape(int(self.dims[v]), -1)
 
     def node_counts(self, v):
         """(parents ascending, counts [dims[v]][parent configs]) of node v."""
@@ -1327,4 +1371,104 @@ class MostProbableExplanation(_Handle):
     def last_kernel_ms(self):
         ms = C.c_float()
         lib.fbn_mpe_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+
+class ExpectationMaximization(_Handle):
+    """Parameter learning from incomplete data (fbn_em): expectation-maximisation over the junction forest
+    of `network`, whose structure is kept and whose probabilities are the starting parameters.  Data rows
+    are int8 [ncases][num_nodes], -1 = missing.  The E-step runs exact junction-tree inference per row (one
+    row per GPU lane) and sums the family posteriors; the M-step is (N + pseudo_count) / (T + pseudo_count
+    * states).  The reference has no counterpart.  device < 0: the host twin (the same per-case bytes)."""
+
+    _destroy = "fbn_em_destroy"
+
+    def __init__(self, network, pseudo_count=1.0, device=0):
+        if not pseudo_count > 0:
+            err = FastBNError(f"ExpectationMaximization: the pseudo-count must be > 0 (got {pseudo_count})")
+            err.code = -1
+            raise err
+        self.network_start = network
+        self.pseudo_count = float(pseudo_count)
+        self.num_nodes = network.num_nodes
+        self.dims = network.dims.copy()
+        self._npc = [network.node_probs(v)[1].shape[1] for v in range(self.num_nodes)]
+        h = C.c_void_p()
+        lib.fbn_em_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def info(self):
+        """dict(cliques, entries, store_rows, cells, components)."""
+        c, e, r, n, k = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+        lib.fbn_em_info(self._h, C.byref(c), C.byref(e), C.byref(r), C.byref(n), C.byref(k))
+        return {"cliques": c.value, "entries": e.value, "store_rows": r.value, "cells": n.value, "components": k.value}
+
+    def _split(self, flat):
+        """the flat cell array as one [dims[v], parent configs] view per node"""
+        out, off = [], 0
+        for v in range(self.num_nodes):
+            n = int(self.dims[v]) * self._npc[v]
+            out.append(flat[off:off + n].reshape(int(self.dims[v]), self._npc[v]))
+            off += n
+        return out
+
+    def estep_flat(self, data):
+        """-> (counts fp64 [cells], value fp64 [ncases][2] = (m, ex), P(e) = m * 2^ex)."""
+        d = np.ascontiguousarray(data, dtype=np.int8)
+        n = d.shape[0]
+        counts = np.zeros(self.info()["cells"], np.float64)
+        value = np.zeros((n, 2), np.float64)
+        lib.fbn_em_estep(self._h, _p(d), n, _p(counts), _p(value))
+        return counts, value
+
+    def estep(self, data):
+        """One E-step at the current parameters -> (counts: one [dims[v], parent configs] array per node,
+        value [ncases][2])."""
+        counts, value = self.estep_flat(data)
+        return self._split(counts), value
+
+    def estep_device(self, d_data_ptr, ncases, d_counts_ptr, d_value_ptr, stream_ptr=None):
+        """Device-resident E-step (asynchronous on the stream after the data check)."""
+        lib.fbn_em_estep_device(self._h, C.c_void_p(d_data_ptr), int(ncases), C.c_void_p(d_counts_ptr),
+                                C.c_void_p(d_value_ptr) if d_value_ptr else None, stream_ptr)
+
+    def fit(self, data, max_iters=50, tol=1e-6):
+        """Iterate E-step and M-step -> objective fp64 [iters_done][2] = (log-likelihood, Q) at the
+        parameters each iteration's E-step ran with.  tol = 0 never stops early."""
+        d = np.ascontiguousarray(data, dtype=np.int8)
+        obj = np.zeros((max(int(max_iters), 1), 2), np.float64)
+        done = C.c_int()
+        lib.fbn_em_run(self._h, _p(d), d.shape[0], int(max_iters), float(tol), self.pseudo_count, _p(obj), C.byref(done))
+        return obj[:done.value].copy()
+
+    def network(self):
+        """The current parameters as a probability network."""
+        h = C.c_void_p()
+        lib.fbn_em_network(self._h, C.byref(h))
+        return Network(_handle=h)
+
+    def set_parameters(self, net):
+        """Take net's probabilities (same structure, else an error)."""
+        lib.fbn_em_set_parameters(self._h, net._h)
+
+    def debug_posteriors(self, data):
+        """The per-case family posteriors fp64 [ncases][cells]."""
+        d = np.ascontiguousarray(data, dtype=np.int8)
+        post = np.zeros((d.shape[0], self.info()["cells"]), np.float64)
+        lib.fbn_em_debug_posteriors(self._h, _p(d), d.shape[0], _p(post))
+        return post
+
+    def log_likelihood(self, data):
+        """log P(e) per case fp64 [ncases] at the current parameters."""
+        _, value = self.estep_flat(data)
+        return np.log(value[:, 0]) + value[:, 1] * np.log(2.0)
+
+    def set_tuning(self, max_workgroups=0, store_bytes_max=0):
+        """fbn_em_set_tuning, as MostProbableExplanation.set_tuning.  Per-case results do not change."""
+        lib.fbn_em_set_tuning(self._h, int(max_workgroups), int(store_bytes_max))
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_em_last_kernel_ms(self._h, C.byref(ms))
         return ms.value

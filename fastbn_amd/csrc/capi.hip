@@ -50,6 +50,21 @@ int fbn_network_create(int nvars, const int32_t *dims, const int32_t *parent_off
     *out = h.release();
     return FBN_OK;
 }
+int fbn_network_create_cpt(int nvars, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                           const double *cpt, const char *const *names, fbn_network **out) {
+    if (!out) return SetError(FBN_ERR_ARG, "null pointer");
+    auto h = std::unique_ptr<fbn_network>(new (std::nothrow) fbn_network());
+    if (!h) return SetError(FBN_ERR_NOMEM, "out of memory");
+    int rc = fbn::BuildNetworkCpt(nvars, dims, parent_off, parents, cpt, names, h->net);
+    if (rc) return rc;
+    *out = h.release();
+    return FBN_OK;
+}
+int fbn_network_node_probs(const fbn_network *net, int node, int32_t *parents, double *probs, int *nparents,
+                           int64_t *nprobs) {
+    if (!net) return SetError(FBN_ERR_ARG, "null pointer");
+    return fbn::NodeProbs(net->net, node, parents, probs, nparents, nprobs);
+}
 int fbn_network_node_counts(const fbn_network *net, int node, int32_t *parents, int64_t *counts, int *nparents,
                             int64_t *ncounts) {
     if (!net) return SetError(FBN_ERR_ARG, "null pointer");

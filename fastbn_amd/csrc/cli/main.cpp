@@ -1,4 +1,4 @@
-// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|6|7|8|10|12 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
+// main.cpp -- drop-in for `./BayesianNetwork -a 0|2|4|5|6|7|8|10|12|13 ...` (src/main.cpp:17-201, src/Parameter.cpp:6-107):
 // same flags, defaults and "../dataset/" path prefix; -a 0 (PC-stable), -a 2 (junction tree), -a 4
 // (probabilistic logic sampling), -a 5 (likelihood weighting; -q samples per case, the reference's
 // default 10000), -a 6 (EPIS-BN; -q samples per case after -d iterations of LBP) and -a 7 (loopy belief
@@ -12,6 +12,10 @@
 // reference's -a stops at 11 and it has no MPE, so there is no reference output to match: the header
 // block is in the house style, the result lines are the case count, the mean log P(x*, e) and the kernel
 // time; --out FILE writes the assignments as LIBSVM rows (label = the value of variable 0).
+// -a 13 is this build's own as well: expectation-maximisation (EM) of the CPTs of -f0's structure, from
+// -f0's parameters, on the rows of -f3 (LIBSVM; a variable a row does not list is missing): -d iterations,
+// --tol the relative stopping tolerance, pseudo-count 1; one line per iteration with the log-likelihood and
+// Q; --out FILE writes the learned CPTs as text, one line per node and parent configuration.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +51,7 @@ int main(int argc, char **argv) {
         if (a == "--out" && i + 1 < argc) { out_file = argv[++i]; continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
                          "[--tol T] [--damping L] [--eps E] [--out FILE] [--prefix DIR]"
@@ -371,12 +375,77 @@ int main(int argc, char **argv) {
         }
         fbn_mpe_destroy(mpe);
         fbn_network_destroy(net);
+    } else if (algorithm == 13) {
+        // expectation-maximisation: no counterpart in the reference (its parameter learning assumes complete data)
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: expectation-maximisation (EM) for parameter learning from incomplete data, #threads = "
+                  << num_threads << std::endl
+                  << "iterations = " << propagation_length << ", tolerance = " << tol << std::endl
+                  << "\tBN (structure and starting parameters): " << net_file << std::endl
+                  << "\tdata set (unlisted variables are missing): " << test_set_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        fbn_network *net = nullptr;
+        if (fbn_network_load_xmlbif(net_file.c_str(), &net)) return die();
+        int n = 0;
+        fbn_network_num_nodes(net, &n);
+        TestSet tester;
+        if (tester.Load(test_set_file, n)) return die();
+        const int64_t nc = tester.num_instances();
+        fbn_em *em = nullptr;
+        if (fbn_em_create(net, device, &em)) return die();
+        const int iters = propagation_length;
+        std::vector<double> objective((size_t)(iters > 0 ? iters : 1) * 2);
+        int done = 0;
+        if (fbn_em_run(em, tester.evidence.data(), nc, iters, tol, 1.0, objective.data(), &done)) return die();
+        std::cout << "cases = " << nc << std::endl;
+        for (int t = 0; t < done; ++t) {
+            char buf[128];
+            snprintf(buf, sizeof buf, "iteration %d: log-likelihood = %.17g, Q = %.17g", t, objective[2 * t], objective[2 * t + 1]);
+            std::cout << buf << std::endl;
+        }
+        float kms = 0.f;
+        if (fbn_em_last_kernel_ms(em, &kms) == 0)  // not on the host path (--device -1)
+            std::cout << "em: last E-step kernel " << kms * 1e-3 << " s, " << nc / (kms * 1e-3) << " cases/s" << std::endl;
+        if (!out_file.empty()) {
+            // one line per node and parent configuration: node, configuration, the probability of each state
+            fbn_network *learned = nullptr;
+            if (fbn_em_network(em, &learned)) return die();
+            FILE *f = fopen(out_file.c_str(), "w");
+            if (!f) {
+                fprintf(stderr, "Error: cannot write %s\n", out_file.c_str());
+                return 1;
+            }
+            std::vector<int32_t> dims(n);
+            fbn_network_dims(learned, dims.data());
+            for (int v = 0; v < n; ++v) {
+                int npar = 0;
+                int64_t np = 0;
+                if (fbn_network_node_probs(learned, v, nullptr, nullptr, &npar, &np)) return die();
+                std::vector<double> probs((size_t)np);
+                if (fbn_network_node_probs(learned, v, nullptr, probs.data(), &npar, &np)) return die();
+                const int64_t npc = np / dims[v];
+                for (int64_t pc = 0; pc < npc; ++pc) {
+                    fprintf(f, "%d %lld", v, (long long)pc);
+                    for (int q = 0; q < dims[v]; ++q) fprintf(f, " %.17g", probs[(size_t)(q * npc + pc)]);
+                    fprintf(f, "\n");
+                }
+            }
+            fclose(f);
+            fbn_network_destroy(learned);
+            std::cout << "CPTs written to " << out_file << std::endl;
+        }
+        fbn_em_destroy(em);
+        fbn_network_destroy(net);
     } else if (algorithm == 9) {
         // SISv1 (ALGSISV1, src/main.cpp:162-173): the reference names it and defines it nowhere, in code or papers
         std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
                   << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10 and 12)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12 and 13)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

@@ -27,6 +27,7 @@ struct Network {
     std::vector<std::vector<int>> parents_asc;  // parents in ascending index order
     std::vector<std::vector<int64_t>> counts;   // [v][q * npc + pc]
     std::vector<std::vector<int64_t>> totals;   // [v][pc], pc over parents_asc, last fastest
+    std::vector<std::vector<double>> cpt;       // a probability network (else empty): [v][q * npc + pc]
     int n() const { return (int)dom.size(); }
     double Prob(int v, int q, const int *parent_vals_asc) const;
 };
@@ -34,6 +35,11 @@ int LoadXmlbif(const std::string &path, Network &net);
 int BuildNetwork(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents, const int64_t *counts,
                  const char *const *names, Network &net);
 int NodeCounts(const Network &net, int v, int32_t *parents_asc, int64_t *counts, int *nparents, int64_t *ncounts);
+// a network that holds probabilities (BuildNetwork's validation; every entry finite and > 0, every
+// column summing to 1 within 1e-9), and node v's table as Prob returns it, for either kind of network
+int BuildNetworkCpt(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents, const double *cpt,
+                    const char *const *names, Network &net);
+int NodeProbs(const Network &net, int v, int32_t *parents_asc, double *probs, int *nparents, int64_t *nprobs);
 
 // parameter learning, host side (param_learn.cpp): family sizing / validation and the PDAG -> DAG
 // extension behind fbn_param_family_sizes / fbn_pdag_to_dag (no device, no other part of the library)

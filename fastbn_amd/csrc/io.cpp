@@ -1,6 +1,7 @@
 // io.cpp -- host-side inputs of the hot paths: XMLBIF networks, CSV training sets, LIBSVM test
 // sets, plus the thread-local error channel.  Semantics follow the reference loaders (cited per
 // function); the implementations are single-pass scanners over the file bytes.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -94,6 +95,7 @@ double Network::Prob(int v, int q, const int *pv) const {
     int64_t pc = 0;
     for (size_t j = 0; j < parents_asc[v].size(); ++j) pc = pc * dom[parents_asc[v][j]] + pv[j];
     int64_t npc = (int64_t)totals[v].size();
+    if (!cpt.empty()) return cpt[v][q * npc + pc];  // a probability network: the entry as it is
     return ((double)counts[v][q * npc + pc] + 1.0) / ((double)totals[v][pc] + 1.0 * (double)dom[v]);
 }
 
@@ -104,9 +106,11 @@ double Network::Prob(int v, int q, const int *pv) const {
 // ascending index order, last fastest (a DiscreteConfig is an ordered set of (var, value) pairs).
 // map_total_count_under_parents_config is the sum over the values, as AddCount keeps it; the
 // probabilities follow GetProbability (:154-164) with laplace_smooth = 1, as for the XMLBIF path.
-int BuildNetwork(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents, const int64_t *counts,
-                 const char *const *names, Network &net) {
-    if (n < 1 || !dims || !parent_off || (!parents && parent_off[n] > 0) || !counts)
+namespace {
+// counts != nullptr: a count network; else a probability network from cpt (counts and totals all zero)
+int BuildNetworkFrom(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents, const int64_t *counts,
+                     const double *cpt, const char *const *names, Network &net) {
+    if (n < 1 || !dims || !parent_off || (!parents && parent_off[n] > 0) || (!counts && !cpt))
         return SetError(FBN_ERR_ARG, "network: bad arguments");
     net = Network();
     net.dom.assign(dims, dims + n);
@@ -131,8 +135,28 @@ int BuildNetwork(int n, const int32_t *dims, const int32_t *parent_off, const in
         net.parents_asc[v].assign(ps.begin(), ps.end());
         int64_t npc = 1;
         for (int q : net.parents_asc[v]) npc *= net.dom[q];
-        net.counts[v].assign(counts + off, counts + off + net.dom[v] * npc);
         net.totals[v].assign((size_t)npc, 0);
+        if (!counts) {
+            net.counts[v].assign((size_t)(net.dom[v] * npc), 0);
+            net.cpt.resize(n);
+            net.cpt[v].assign(cpt + off, cpt + off + net.dom[v] * npc);
+            for (int64_t pc = 0; pc < npc; ++pc) {
+                double sum = 0.0;
+                for (int q = 0; q < net.dom[v]; ++q) {
+                    const double x = net.cpt[v][q * npc + pc];
+                    if (!(x > 0.0) || !std::isfinite(x))
+                        return SetError(FBN_ERR_ARG, "node %d: probability %g (value %d, parent configuration %lld) is not finite and > 0",
+                                        v, x, q, (long long)pc);
+                    sum += x;
+                }
+                if (!(std::fabs(sum - 1.0) <= 1e-9))
+                    return SetError(FBN_ERR_ARG, "node %d: the probabilities under parent configuration %lld sum to %.17g, not 1",
+                                    v, (long long)pc, sum);
+            }
+            off += net.dom[v] * npc;
+            continue;
+        }
+        net.counts[v].assign(counts + off, counts + off + net.dom[v] * npc);
         for (int q = 0; q < net.dom[v]; ++q)
             for (int64_t pc = 0; pc < npc; ++pc) {
                 const int64_t c = net.counts[v][q * npc + pc];
@@ -154,10 +178,45 @@ int BuildNetwork(int n, const int32_t *dims, const int32_t *parent_off, const in
     if ((int)order.size() != n) return SetError(FBN_ERR_ARG, "network: the parent lists form a cycle");
     return FBN_OK;
 }
+}  // namespace
+
+int BuildNetwork(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents, const int64_t *counts,
+                 const char *const *names, Network &net) {
+    if (!counts) return SetError(FBN_ERR_ARG, "network: bad arguments");
+    return BuildNetworkFrom(n, dims, parent_off, parents, counts, nullptr, names, net);
+}
+
+// A network that holds probabilities: BuildNetwork's structure and validation, the table entries kept as
+// they are (Prob returns them); its count map is all zero and is not handed out (NodeCounts).
+int BuildNetworkCpt(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents, const double *cpt,
+                    const char *const *names, Network &net) {
+    if (!cpt) return SetError(FBN_ERR_ARG, "network: bad arguments");
+    return BuildNetworkFrom(n, dims, parent_off, parents, nullptr, cpt, names, net);
+}
+
+// node v's probability table (layout as BuildNetwork's), parents in ascending order: what Prob returns
+int NodeProbs(const Network &net, int v, int32_t *parents_asc, double *probs, int *nparents, int64_t *nprobs) {
+    if (v < 0 || v >= net.n()) return SetError(FBN_ERR_ARG, "node %d out of range", v);
+    const std::vector<int> &pa = net.parents_asc[v];
+    if (nparents) *nparents = (int)pa.size();
+    if (nprobs) *nprobs = (int64_t)net.counts[v].size();
+    if (parents_asc) std::copy(pa.begin(), pa.end(), parents_asc);
+    if (probs) {
+        const int64_t npc = (int64_t)net.totals[v].size();
+        std::vector<int> pv(pa.size());
+        for (int64_t pc = 0; pc < npc; ++pc) {
+            int64_t r = pc;
+            for (int j = (int)pa.size() - 1; j >= 0; --j) pv[j] = (int)(r % net.dom[pa[j]]), r /= net.dom[pa[j]];
+            for (int q = 0; q < net.dom[v]; ++q) probs[q * npc + pc] = net.Prob(v, q, pv.data());
+        }
+    }
+    return FBN_OK;
+}
 
 // the count map of node v (layout as BuildNetwork's), parents in ascending order
 int NodeCounts(const Network &net, int v, int32_t *parents_asc, int64_t *counts, int *nparents, int64_t *ncounts) {
     if (v < 0 || v >= net.n()) return SetError(FBN_ERR_ARG, "node %d out of range", v);
+    if (!net.cpt.empty()) return SetError(FBN_ERR_ARG, "node %d: a probability network holds no counts (use fbn_network_node_probs)", v);
     if (nparents) *nparents = (int)net.parents_asc[v].size();
     if (ncounts) *ncounts = (int64_t)net.counts[v].size();
     if (parents_asc) std::copy(net.parents_asc[v].begin(), net.parents_asc[v].end(), parents_asc);

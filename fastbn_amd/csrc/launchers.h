@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -102,5 +102,14 @@ extern "C" hipError_t fbn_ais_launch(const fbn::AisDeviceArgs *a, int lds_state,
 // workgroups, 64 cases each per round, a->store_rows rows of a->store per workgroup.
 struct JtMpeArgs;
 extern "C" hipError_t fbn_mpe_launch(const JtMpeArgs *a, hipStream_t stream);
+// The expectation-maximisation kernels (jt_em_program.h's arguments): the E-step, a persistent grid of
+// a->grid one-wave workgroups as the max-product kernel's; the reduction of the waves' accumulators in
+// wave order; the M-step with the rebuild of the initial potentials (one workgroup).
+struct JtEmArgs;
+struct JtEmReduceArgs;
+struct JtEmMstepArgs;
+extern "C" hipError_t fbn_em_estep_launch(const JtEmArgs *a, hipStream_t stream);
+extern "C" hipError_t fbn_em_reduce_launch(const JtEmReduceArgs *a, hipStream_t stream);
+extern "C" hipError_t fbn_em_mstep_launch(const JtEmMstepArgs *a, hipStream_t stream);
 
 #endif

@@ -59,9 +59,22 @@ int fbn_network_load_xmlbif(const char *path, fbn_network **out);
 int fbn_network_create(int nvars, const int32_t *dims, const int32_t *parent_off /* [nvars+1] */,
                        const int32_t *parents, const int64_t *counts, const char *const *names,
                        fbn_network **out);
-/* Node v's parents (ascending) and count map in fbn_network_create's layout; NULL buffers: sizes only. */
+/* Node v's parents (ascending) and count map in fbn_network_create's layout; NULL buffers: sizes only.
+ * A probability network (fbn_network_create_cpt) has no counts: FBN_ERR_ARG. */
 int fbn_network_node_counts(const fbn_network *net, int node, int32_t *parents, int64_t *counts, int *nparents,
                             int64_t *ncounts);
+/* A network that holds probabilities instead of counts (what expectation-maximisation produces: its
+ * expected counts are fractional).  Arguments and validation as fbn_network_create, with cpt in its
+ * layout: fp64 cpt[value][config of the ascending parents, last fastest], node after node.  Every entry
+ * must be finite and > 0 and every column (the values under one parent configuration) must sum to 1
+ * within 1e-9, else FBN_ERR_ARG naming the node.  Every consumer of a network reads such a network's
+ * entries as they are (no smoothing); a count network behaves as before. */
+int fbn_network_create_cpt(int nvars, const int32_t *dims, const int32_t *parent_off /* [nvars+1] */,
+                           const int32_t *parents, const double *cpt, const char *const *names, fbn_network **out);
+/* Node v's parents (ascending) and probability table in fbn_network_create's layout, for either kind of
+ * network: the stored entries, or (count + 1) / (total + dims[v]).  NULL buffers: sizes only. */
+int fbn_network_node_probs(const fbn_network *net, int node, int32_t *parents, double *probs, int *nparents,
+                           int64_t *nprobs);
 int fbn_network_num_nodes(const fbn_network *net, int *n);
 int fbn_network_dims(const fbn_network *net, int32_t *dims /* [n] */);
 int fbn_network_name(const fbn_network *net, int node, char *buf, int cap);
@@ -806,6 +819,91 @@ int fbn_mpe_debug_messages(fbn_mpe *s, const int8_t *evidence, int64_t ncases, d
 int fbn_mpe_set_tuning(fbn_mpe *s, int max_workgroups, int64_t store_bytes_max);
 /* Device kernel time (ms, hipEvent) of the handle's last launch. */
 int fbn_mpe_last_kernel_ms(const fbn_mpe *s, float *ms);
+
+/* ------------------------------------------------------------------ expectation-maximisation
+ * EM: the CPTs of a network of known structure from data with missing cells (a hidden variable is a column
+ * of missing cells).  The reference has no counterpart: ParameterLearning.cpp assumes complete data.
+ *
+ * Data: int8 [ncases][V], -1 = missing, otherwise a state code -- the evidence format, validated as
+ * fbn_mpe_run validates.  Plan: the forest plan of fbn_jt_forest_plan_create (any DAG); a data row is
+ * applied as evidence by masking, as in MPE.  theta: the current parameters, fp64 [cells] in
+ * fbn_param_counts' layout ([value][config of the ascending parents, last fastest], family after family,
+ * offsets of fbn_param_family_sizes).  Every theta > 0, so every row that passes validation has P(e) > 0.
+ * Collect (sum-product): cliques deepest level first, plan order within a level.  For an unmasked entry
+ *     v(e) = (((init_c[e] * M_1[map_1(e)]) * M_2[map_2(e)]) ...) over the children in clique_down order.
+ *   A non-root keeps msg[s] = sum of v(e) over its unmasked entries with up(e) = s, in ascending e, from
+ *   0.0; then mx = max_s msg[s], frexp(mx) = f * 2^k, the stored message is M_c[s] = ldexp(msg[s], -k) and
+ *   the clique's integer exponent is E_c = k + sum over children E_child.  Only powers of two rescale.
+ *   A root sums its unmasked v(e) in ascending e from 0.0: sum_r = f_r * 2^(k_r), total exponent
+ *   k_r + sum E_child.  The case's evidence probability is the product over the roots in ascending
+ *   component order from (m, ex) = (1.0, 0): m = m * f_r, re-frexp after each multiply, exponents added.
+ *   value[case] = {m, ex}, m in [0.5, 1), P(e) = m * 2^ex.  No log is taken here.
+ * Distribute: cliques levels ascending, plan order within a level.  For clique c with parent p the
+ *   downward message on c's upstream separator is D_c[s] = sum over p's unmasked entries e with
+ *   map_{p->c}(e) = s, in ascending e from 0.0, of
+ *     t(e) = ((init_p[e] * M_j[map_j(e)]) ... over p's children j != c in clique_down order) * D_p[up_p(e)],
+ *   the last factor only where p is not a root (for a root D_p = 1).  Then mx = max_s D_c[s], frexp(mx) gives
+ *   k and the stored message is ldexp(D_c[s], -k); its exponent is not kept (a belief is normalised by its
+ *   own clique's sum).  The message is division-free: nothing is ever divided by a message.
+ * Family posteriors: node v's family {v} + parents is hosted by the first clique in plan order that
+ *   contains it.  For a hosting clique the belief of an unmasked entry is b(e) = v(e) * D_c[up(e)] (b = v for
+ *   a root), Z_c = the sum of b(e) in ascending e from 0.0, and the posterior of family cell f is the sum of
+ *   b(e) / Z_c over the unmasked entries that map to f, in ascending e from 0.0: a true division by the
+ *   clique's own sum, so a fully observed row contributes exactly 1.0 to one cell per family, and a cell the
+ *   row rules out gets exactly 0.0.
+ * E-step output: N[cell] = the sum over the cases of the posterior (fp64); value [ncases][2].  The host
+ *   twin adds the cases in order.  The device adds the 64 cases of a block (cases 64 b .. 64 b + 63) in
+ *   butterfly order (lane i adds lane i ^ off, off = 32 .. 1), then the blocks of a wave in order (blocks w,
+ *   w + g, ... for wave w of g), then the waves in wave order: no atomics, so two runs with the same inputs
+ *   and the same grid give identical bytes, while the counts of two grid sizes, and of the twin, may differ
+ *   by the rounding of a sum of n non-negative terms (relative n * 2^-53).  Per-case posteriors and values are
+ *   the twin's bytes at every grid size.
+ * M-step: theta_v[q | pc] = (N[q, pc] + alpha) / (T[pc] + alpha * dims[v]), T[pc] = the sum of N[q, pc] in
+ *   ascending q from 0.0.  alpha > 0 is the pseudo-count (1.0 is the project's own (count + 1) / (total + |dom|)).
+ * Potentials of the next iteration: init_c[e] = ((1.0 * theta_a[..]) * theta_b[..]) ... over the families the
+ *   clique hosts in ascending node order -- with theta a network's own CPTs, the plan's potentials to the byte.
+ * Objective of iteration t, at the parameters its E-step ran with: log-likelihood L_t = the sum in case
+ *   order of log(m) + ex * log(2), formed on the host; Q_t = L_t + alpha * (the sum over the cells in order of
+ *   log theta[cell]).  EM with this M-step never decreases Q.
+ * Stopping: an iteration is E-step, objective, M-step.  After max_iters iterations; or after the iteration
+ *   t >= 1 with Q_t - Q_(t-1) <= tol * |Q_t| (its M-step is still taken).  tol = 0 never stops early.
+ * Limits: as MPE's (a clique of more than 32 variables, tables beyond int32 indexing, one wave's state --
+ *   store_rows * 512 + cells * 8 bytes -- past the handle's budget), or more than FBN_PARAM_MAX_CELLS cells:
+ *   FBN_ERR_LIMIT at create.  A cyclic network: FBN_ERR_ARG. */
+typedef struct fbn_em fbn_em;
+/* `start` gives the structure and the starting parameters (its Prob: a count network's smoothed CPTs, or a
+ * probability network's entries).  device < 0: a host-only handle running the host twin. */
+int fbn_em_create(const fbn_network *start, int device, fbn_em **out);
+int fbn_em_destroy(fbn_em *s);
+/* cliques, the sum of their entries, the rows of one case's store (2 * separator entries + separators),
+ * the family cells (a wave also owns an accumulator of one fp64 per cell) and the forest's components. */
+int fbn_em_info(const fbn_em *s, int64_t *cliques, int64_t *entries, int64_t *store_rows, int64_t *cells,
+                int *components);
+/* One E-step at the current parameters.  Host arrays, synchronous; a bad code is FBN_ERR_ARG naming the
+ * case and node. */
+int fbn_em_estep(fbn_em *s, const int8_t *data, int64_t ncases, double *counts /* [cells] */,
+                 double *value /* [ncases][2] or NULL */);
+/* The same with device-resident buffers; asynchronous on hip_stream after the data check (one stream sync). */
+int fbn_em_estep_device(fbn_em *s, const int8_t *d_data, int64_t ncases, double *d_counts, double *d_value,
+                        void *hip_stream);
+/* The loop, on the device for a device handle: the data is uploaded once; an iteration launches the E-step,
+ * the cross-wave reduction and one kernel for the M-step and the potential rebuild; the per-case values
+ * and theta (for the objective's logs) are all that comes back.  objective [max_iters][2] = {L_t, Q_t} for
+ * the iterations done.  pseudo_count <= 0, max_iters < 1 or tol < 0: FBN_ERR_ARG.  Leaves the theta, byte for
+ * byte, of a caller chaining fbn_em_estep, the stated M-step and fbn_em_set_parameters. */
+int fbn_em_run(fbn_em *s, const int8_t *data, int64_t ncases, int max_iters, double tol, double pseudo_count,
+               double *objective, int *iters_done);
+/* theta = net's probabilities; net must have the handle's structure (states, parent sets), else FBN_ERR_ARG. */
+int fbn_em_set_parameters(fbn_em *s, const fbn_network *net);
+/* The current theta as a probability network (fbn_network_create_cpt). */
+int fbn_em_network(const fbn_em *s, fbn_network **out);
+/* Testing interface: the per-case family posteriors [ncases][cells]; at most 2^26 doubles.  Host arrays. */
+int fbn_em_debug_posteriors(fbn_em *s, const int8_t *data, int64_t ncases, double *post);
+/* Kernel tuning, as fbn_mpe_set_tuning.  Per-case results never depend on either; the summed counts depend
+ * on the grid within the rounding stated above. */
+int fbn_em_set_tuning(fbn_em *s, int max_workgroups, int64_t store_bytes_max);
+/* Device time (ms, hipEvent) of the handle's last E-step kernel. */
+int fbn_em_last_kernel_ms(const fbn_em *s, float *ms);
 
 #ifdef __cplusplus
 }
