@@ -1333,7 +1333,8 @@ class MostProbableExplanation(_Handle):
 
     def value_parts(self, evidence):
         """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (assignment int8 [ncases][num_nodes],
-        value fp64 [ncases][2] = (m, ex) with P(x*, e) = m * 2^ex, m in [0.5, 1))."""
+        value fp64 [ncases][2] = (m, ex) with P(x*, e) = m * 2^ex, m in [0.5, 1)).  A case whose value
+        underflows inside a clique (m would be 0) raises FastBNError (FBN_ERR_LIMIT) naming it."""
         ev = np.ascontiguousarray(evidence, dtype=np.int8)
         n = ev.shape[0]
         assign = np.zeros((n, self.network.num_nodes), np.int8)

@@ -91,15 +91,21 @@ int UploadParameters(fbn_em *s) {
     return Upload(s->initv, s->P.M.initv);
 }
 
+// a row with m == 0 has NaN posteriors: an error, never a result (jt_mpe_program.h: CheckCaseValues)
+int CheckValues(const double *value, int64_t ncases) { return fbn::CheckCaseValues("em", value, ncases); }
+
 int EstepHostBuffers(fbn_em *s, const int8_t *data, int64_t ncases, double *counts, double *value, double *post) {
     const int64_t cells = s->P.cells;
     if (ncases == 0) {
         if (counts) std::fill(counts, counts + cells, 0.0);
         return FBN_OK;
     }
+    std::vector<double> vbuf;
+    if (!value) vbuf.resize((size_t)ncases * 2), value = vbuf.data();
     if (s->device < 0) {
         if (int rc = fbn::CheckMpeEvidence(s->P.M, data, ncases)) return rc;
-        return fbn::HostEmEstep(s->P, data, ncases, counts, value, post);
+        if (int rc = fbn::HostEmEstep(s->P, data, ncases, counts, value, post)) return rc;
+        return CheckValues(value, ncases);
     }
     FBN_HIP(hipSetDevice(s->device));
     const int V = s->P.M.V;
@@ -112,10 +118,10 @@ int EstepHostBuffers(fbn_em *s, const int8_t *data, int64_t ncases, double *coun
                      post ? s->post.as<double>() : nullptr, true, nullptr);
     if (rc) return rc;
     if (counts) FBN_HIP(hipMemcpy(counts, s->counts.p, (size_t)cells * 8, hipMemcpyDeviceToHost));
-    if (value) FBN_HIP(hipMemcpy(value, s->value.p, (size_t)ncases * 16, hipMemcpyDeviceToHost));
+    FBN_HIP(hipMemcpy(value, s->value.p, (size_t)ncases * 16, hipMemcpyDeviceToHost));
     if (post) FBN_HIP(hipMemcpy(post, s->post.p, (size_t)ncases * cells * 8, hipMemcpyDeviceToHost));
     FBN_HIP(hipDeviceSynchronize());
-    return FBN_OK;
+    return CheckValues(value, ncases);
 }
 
 // {L, Q} at theta from the per-case values: the logs on the host, in case order and in cell order
@@ -203,7 +209,7 @@ int fbn_em_run(fbn_em *s, const int8_t *data, int64_t ncases, int max_iters, dou
     } else if ((rc = fbn::CheckMpeEvidence(s->P.M, data, ncases))) {
         return rc;
     }
-    int done = 0;
+    std::vector<double> prev;
     for (int t = 0; t < max_iters; ++t) {
         if (!dev) {
             if ((rc = fbn::HostEmEstep(s->P, data, ncases, counts.data(), value.data(), nullptr))) return rc;
@@ -215,10 +221,11 @@ int fbn_em_run(fbn_em *s, const int8_t *data, int64_t ncases, int max_iters, dou
         } else {
             FBN_HIP(hipMemset(s->counts.p, 0, (size_t)cells * 8));
         }
+        if ((rc = CheckValues(value.data(), ncases))) return rc;  // theta is still the last one accepted
         Objective(value.data(), ncases, s->P.theta, pseudo_count, objective + 2 * t);
+        prev = s->P.theta;
         if (!dev) {
             fbn::EmMstep(s->P, counts.data(), pseudo_count, s->P.theta.data());
-            fbn::EmRebuildPotentials(s->P, s->P.theta.data(), s->P.M.initv.data());
         } else {
             JtEmMstepArgs m;
             m.counts = s->counts.as<double>(), m.theta = s->theta.as<double>(), m.initv = s->initv.as<double>();
@@ -229,11 +236,18 @@ int fbn_em_run(fbn_em *s, const int8_t *data, int64_t ncases, int max_iters, dou
             FBN_HIP(fbn_em_mstep_launch(&m, nullptr));
             FBN_HIP(hipMemcpy(s->P.theta.data(), s->theta.p, (size_t)cells * 8, hipMemcpyDeviceToHost));
         }
-        done = t + 1;
+        // the host copy of the potentials follows theta (the device's own come from the M-step kernel, the
+        // same products); a theta they underflow under is refused and the handle goes back one M-step
+        fbn::EmRebuildPotentials(s->P, s->P.theta.data(), s->P.M.initv.data());
+        if ((rc = fbn::EmCheckPotentials(s->P, s->P.M.initv.data()))) {
+            s->P.theta.swap(prev);
+            fbn::EmRebuildPotentials(s->P, s->P.theta.data(), s->P.M.initv.data());
+            if (int up = UploadParameters(s)) return up;
+            return rc;
+        }
+        if (iters_done) *iters_done = t + 1;
         if (t >= 1 && objective[2 * t + 1] - objective[2 * t - 1] <= tol * std::fabs(objective[2 * t + 1])) break;
     }
-    if (dev) fbn::EmRebuildPotentials(s->P, s->P.theta.data(), s->P.M.initv.data());  // the host copy follows
-    if (iters_done) *iters_done = done;
     return FBN_OK;
 }
 
@@ -241,8 +255,11 @@ int fbn_em_set_parameters(fbn_em *s, const fbn_network *net) {
     if (!s || !net) return SetError(FBN_ERR_ARG, "null pointer");
     std::vector<double> theta;
     if (int rc = fbn::EmThetaFromNetwork(s->P, s->structure, net->net, theta)) return rc;
+    std::vector<double> initv(s->P.M.initv.size());
+    fbn::EmRebuildPotentials(s->P, theta.data(), initv.data());
+    if (int rc = fbn::EmCheckPotentials(s->P, initv.data())) return rc;  // the handle keeps its parameters
     s->P.theta.swap(theta);
-    fbn::EmRebuildPotentials(s->P, s->P.theta.data(), s->P.M.initv.data());
+    s->P.M.initv.swap(initv);
     return UploadParameters(s);
 }
 

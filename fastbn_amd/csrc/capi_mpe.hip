@@ -68,7 +68,8 @@ int MpeHostBuffers(fbn_mpe *s, const int8_t *evidence, int64_t ncases, int8_t *a
     const int V = s->P.V;
     if (s->device < 0) {
         if (int rc = fbn::CheckMpeEvidence(s->P, evidence, ncases)) return rc;
-        return fbn::HostMpe(s->P, evidence, ncases, assignment, value, messages, exponents);
+        if (int rc = fbn::HostMpe(s->P, evidence, ncases, assignment, value, messages, exponents)) return rc;
+        return fbn::CheckCaseValues("mpe", value, ncases);
     }
     FBN_HIP(hipSetDevice(s->device));
     const size_t mbytes = (size_t)ncases * (size_t)std::max<int64_t>(s->P.msg_rows, 1) * 8;
@@ -88,7 +89,7 @@ int MpeHostBuffers(fbn_mpe *s, const int8_t *evidence, int64_t ncases, int8_t *a
         FBN_HIP(hipMemcpy(messages, s->dmsg.p, (size_t)ncases * s->P.msg_rows * 8, hipMemcpyDeviceToHost));
     if (exponents && s->P.nsep > 0)
         FBN_HIP(hipMemcpy(exponents, s->dexp.p, (size_t)ncases * s->P.nsep * 4, hipMemcpyDeviceToHost));
-    return FBN_OK;
+    return fbn::CheckCaseValues("mpe", value, ncases);
 }
 
 }  // namespace

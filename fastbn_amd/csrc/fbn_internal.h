@@ -98,6 +98,13 @@ struct JTPlanHost {
 };
 // forest = false: a disconnected moral graph is an error (FBN_ERR_ARG)
 int BuildJTPlan(const Network &net, JTPlanHost &plan, bool forest = false);
+// An initial clique potential is the plain fp64 product of the CPT entries of the families the clique
+// hosts.  A count network's entries keep it far from the bottom of the range; a probability network's
+// (any finite entry > 0) can take it to a subnormal or to zero, which every engine would then read as
+// an impossible configuration.  FBN_ERR_LIMIT naming the clique and one of its nodes for an entry
+// below DBL_MIN; the program compilers of every engine over the plan call it.
+int CheckCliquePotential(int clique, const int *vars, int nvars, const double *pot, int64_t n);
+int CheckPlanPotentials(const JTPlanHost &plan);
 
 // device program (see jt_program.h) compiled from the host plan
 struct JTProgram {

@@ -160,6 +160,14 @@ void EmRebuildPotentials(const JTProgramEm &P, const double *theta, double *init
     }
 }
 
+int EmCheckPotentials(const JTProgramEm &P, const double *initv) {
+    for (size_t c = 0; c < P.M.cl.size(); ++c) {
+        const JtMClique &m = P.M.cl[c];
+        if (int rc = CheckCliquePotential((int)c, &P.M.aux[m.vars_off], m.nv, initv + m.iv_off, m.T)) return rc;
+    }
+    return FBN_OK;
+}
+
 void EmMstep(const JTProgramEm &P, const double *counts, double alpha, double *theta) {
     for (int64_t cell = 0; cell < P.cells; ++cell) {
         const int32_t *r = &P.node_rec[3 * P.cell_node[(size_t)cell]];

@@ -95,6 +95,8 @@ int CompileJTProgramEm(const Network &net, const JTPlanHost &plan, JTProgramEm &
 int EmThetaFromNetwork(const JTProgramEm &P, const Network &structure, const Network &net, std::vector<double> &theta);
 // init_c[e] = ((1.0 * theta_a[..]) * theta_b[..]) ... over the families the clique hosts, ascending node
 void EmRebuildPotentials(const JTProgramEm &P, const double *theta, double *initv);
+// CheckCliquePotential over rebuilt potentials: FBN_ERR_LIMIT for an entry below DBL_MIN
+int EmCheckPotentials(const JTProgramEm &P, const double *initv);
 // theta from counts: (N + alpha) / (T + alpha * states), T the sum over the states in ascending order
 void EmMstep(const JTProgramEm &P, const double *counts, double alpha, double *theta);
 // The host twin of the E-step: counts [cells] (or NULL) summed in case order, value [ncases][2] (or

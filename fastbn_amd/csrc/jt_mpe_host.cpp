@@ -21,6 +21,15 @@ int CheckMpeEvidence(const JTProgramMpe &P, const int8_t *ev, int64_t ncases) {
     return FBN_OK;
 }
 
+int CheckCaseValues(const char *what, const double *value, int64_t ncases) {
+    for (int64_t c = 0; c < ncases; ++c)
+        if (!(value[2 * c] > 0.0))
+            return SetError(FBN_ERR_LIMIT,
+                            "%s: case %lld: the value underflows inside a clique (potential times messages; reported {%g, %g})",
+                            what, (long long)c, value[2 * c], value[2 * c + 1]);
+    return FBN_OK;
+}
+
 namespace {
 
 // the evidence pattern of one clique for one case: mask / value words over the digit slots

@@ -12,6 +12,7 @@ namespace fbn {
 
 int CompileJTProgramMpe(const JTPlanHost &plan, JTProgramMpe &prog) {
     prog = JTProgramMpe();
+    if (int rc = CheckPlanPotentials(plan)) return rc;
     const int nc = (int)plan.cliques.size(), ns = (int)plan.seps.size();
     prog.V = plan.num_nodes;
     prog.nsep = ns;

@@ -77,6 +77,12 @@ struct JTProgramMpe {
 int CompileJTProgramMpe(const JTPlanHost &plan, JTProgramMpe &prog);
 // FBN_ERR_ARG naming the first case / node whose code is neither -1 nor a state of the node
 int CheckMpeEvidence(const JTProgramMpe &P, const int8_t *ev, int64_t ncases);
+// value [ncases][2] = {m, ex} as MPE or the E-step reports it.  A case whose every unmasked v(e) of some
+// clique underflowed to 0 has m == 0 (NaN posteriors in the E-step): the quantity is > 0 and {m, ex} could
+// hold it, but a clique's potential times its messages is formed in plain fp64.  Normal potentials do not
+// exclude it: messages are scaled by their row's largest entry, so a potential of 2^-920 beside one message
+// entry 2^-300 below its row's largest is enough.  FBN_ERR_LIMIT naming the first such case.
+int CheckCaseValues(const char *what, const double *value, int64_t ncases);
 // The host twin: assignment [ncases][V], value [ncases][2]; messages [ncases][msg_rows] and exponents
 // [ncases][nsep] (or NULL) as Collect leaves them.  Cases spread over HostThreads() threads.
 int HostMpe(const JTProgramMpe &P, const int8_t *ev, int64_t ncases, int8_t *assign, double *value,

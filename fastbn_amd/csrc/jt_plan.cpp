@@ -14,6 +14,7 @@
 // No separator crosses components, so no compiler sees an empty separator, a forest costs the sum
 // of its trees, and the product of the components' evidence likelihoods is never formed.
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include <cstdio>
 #include <numeric>
@@ -56,6 +57,24 @@ int LocOf(const Table &t, int v) {
 }
 
 }  // namespace
+
+int CheckCliquePotential(int clique, const int *vars, int nvars, const double *pot, int64_t n) {
+    for (int64_t e = 0; e < n; ++e)
+        if (!(pot[e] >= DBL_MIN))
+            return SetError(FBN_ERR_LIMIT,
+                            "clique %d (%d variables, node %d among them): the initial potential of entry %lld is %g, "
+                            "below the smallest normal double -- the product of its CPT entries underflows",
+                            clique, nvars, nvars > 0 ? vars[0] : -1, (long long)e, pot[e]);
+    return FBN_OK;
+}
+
+int CheckPlanPotentials(const JTPlanHost &plan) {
+    for (size_t c = 0; c < plan.cliques.size(); ++c) {
+        const Table &t = plan.cliques[c];
+        if (int rc = CheckCliquePotential((int)c, t.vars.data(), (int)t.vars.size(), t.pot.data(), t.size())) return rc;
+    }
+    return FBN_OK;
+}
 
 int BuildJTPlan(const Network &net, JTPlanHost &plan, bool forest) {
     const int n = net.n();
@@ -337,6 +356,7 @@ int BuildJTPlan(const Network &net, JTPlanHost &plan, bool forest) {
 // program compiler
 int CompileJTProgram(const JTPlanHost &plan, JTProgram &prog) {
     prog = JTProgram();
+    if (int rc = CheckPlanPotentials(plan)) return rc;
     const int nc = (int)plan.cliques.size(), ns = (int)plan.seps.size();
     std::vector<int64_t> coff(nc), soff(ns);
     int64_t off = 0;

@@ -102,6 +102,22 @@ def prebuild_count_maps():
     return out
 
 
+def prebuild_prob_nets():
+    """The probability networks whose specialized kernel tests/test_gpu_probnet.py requests (generators in
+    tests/prob_nets.py): the skewed 7-node network, the votes network, ALARM's structure with learned
+    tables, and the 7-node network split into a forest -- both orders, case-major."""
+    P = _load_tests_module("prob_nets")
+    out = []
+    for cls, net in ((api.JunctionTree, P.small("skewed")), (api.JunctionTree, P.votes("guard")),
+                     (api.JunctionTree, P.learned(ALARM_XML)), (api.JunctionForest, P.small_forest("skewed"))):
+        jt = cls(api.Network.from_cpts(*net), device=-1)
+        assert jt.info["specialized_eligible"]
+        for exact in (None, True):
+            jt.set_exact(exact)
+            out.append(jt.build_kernel())
+    return out
+
+
 # code-generation options the GPU tests run ALARM under (tests/test_gpu_jt_fast.py)
 ALARM_TEST_OPTIONS = ({"FBN_JT_LEAF_RC": "1"}, {"FBN_JT_LDS_POOL": "0"}, {"FBN_JT_MARG_V2": "0"},
                       {"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"})
@@ -147,6 +163,7 @@ def prebuild_default(clean=True):
     built += prebuild_options(ALARM_XML, ({"FBN_JT_REG_POOL": "0"}, {"FBN_JT_REG_POOL": "256"}), layout=1)
     # (the exact-order kernels of the conflict networks and of the 32-state network take 5 .. 20 s each)
     built += prebuild_count_maps()
+    built += prebuild_prob_nets()
     if clean:
         keep = {os.path.basename(p) for p in built}
         kdir = os.path.join(REPO, "fastbn_amd", "kcache")

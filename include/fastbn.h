@@ -134,7 +134,10 @@ typedef struct {
 /* Build the case-independent schedule (JunctionTree ctor, src/JunctionTree.cpp:3-46:
  * JunctionTreeStructure src/JunctionTreeStructure.cpp:12-348, root/levels/reorganization
  * :137-281), compile it to a device program and upload it to `device`.  device < 0 builds a
- * host-only plan (info / dump; runs return FBN_ERR_NODEV). */
+ * host-only plan (info / dump; runs return FBN_ERR_NODEV).
+ * A clique's initial potential is the plain fp64 product of the CPT entries it hosts.  A probability
+ * network's entries can take one below DBL_MIN (zero or subnormal); such a plan is refused with
+ * FBN_ERR_LIMIT naming the clique and one of its nodes, here and in fbn_jt_forest_plan_create. */
 int fbn_jt_plan_create(const fbn_network *net, int device, fbn_jt_plan **out);
 /* The same plan for any DAG: where the moral graph is disconnected (fbn_jt_plan_create: FBN_ERR_ARG)
  * this builds a junction FOREST -- per component exactly the tree fbn_jt_plan_create builds for that
@@ -766,8 +769,19 @@ int fbn_ais_eta(int method, int m, double *eta);
  * Plan: the forest plan -- cliques with initial potentials init_c (plain products of CPT entries; the
  * product over all cliques is the joint), separators, clique_up / clique_down, levels, one root per
  * component.  Evidence is applied by masking: a clique entry that disagrees with an observed variable is
- * skipped.  Every CPT entry is (count + 1) / (total + |dom|) > 0, so P(x, e) > 0 for every evidence row that
- * passes validation; no zero-probability branch exists beyond a guard.
+ * skipped.  Every CPT entry is > 0 -- (count + 1) / (total + |dom|), or a probability network's finite
+ * entry, which may be as small as a subnormal -- and init_c is formed as a plain fp64 product, so
+ * fbn_mpe_create returns FBN_ERR_LIMIT, naming the clique and one of its nodes, when an init_c[e] is below
+ * DBL_MIN (zero or subnormal: the product underflowed).  Normal potentials do not make every v(e) below
+ * normal: a message is scaled by its row's largest entry alone, so v(e) = init_c[e] times message entries
+ * that lie far below their rows' largest can underflow with ordinary tables -- a potential of 2^-921 and a
+ * single message entry 2^-300 below its row's largest are enough (four children that each cost one value of
+ * their parent 2^-300 or 2^-920, all observed).  When every unmasked v(e) of a clique is 0 the case's value
+ * comes out as {0, 0} although P(x*, e) > 0 and {m, ex} could hold it: fbn_mpe_run and
+ * fbn_mpe_debug_messages read every case's value and return FBN_ERR_LIMIT naming the first such case, never
+ * FBN_OK with m == 0.  fbn_mpe_run_device is asynchronous and leaves that check to the caller (m of d_value).
+ * A v(e) that underflows while a larger one of its clique does not is a loss of relative accuracy below
+ * 2^-1022 of the clique's largest, as in any fp64 table.  No zero-probability branch exists beyond a guard.
  * Collect: cliques deepest level first, plan order within a level.  For clique c scan its entries
  *   e = 0 .. T-1 ascending, skipping masked ones:
  *     v(e) = (((init_c[e] * M^_1[map_1(e)]) * M^_2[map_2(e)]) ...) over the children in clique_down order;
@@ -828,7 +842,15 @@ int fbn_mpe_last_kernel_ms(const fbn_mpe *s, float *ms);
  * fbn_mpe_run validates.  Plan: the forest plan of fbn_jt_forest_plan_create (any DAG); a data row is
  * applied as evidence by masking, as in MPE.  theta: the current parameters, fp64 [cells] in
  * fbn_param_counts' layout ([value][config of the ascending parents, last fastest], family after family,
- * offsets of fbn_param_family_sizes).  Every theta > 0, so every row that passes validation has P(e) > 0.
+ * offsets of fbn_param_family_sizes).  Every theta > 0, but init_c is a plain fp64 product of thetas and a
+ * probability network's may be tiny: fbn_em_create and fbn_em_set_parameters return FBN_ERR_LIMIT, naming
+ * the clique and one of its nodes, when an init_c[e] is below DBL_MIN (zero or subnormal), and
+ * fbn_em_set_parameters then leaves the handle as it was.  A row's P(e) can still leave the range inside a
+ * clique, with ordinary tables (as stated above fbn_mpe_create: normal potentials times message entries far
+ * below their rows' largest): when every unmasked v(e) of a clique is 0 its value has m == 0 and its
+ * posteriors are NaN.  fbn_em_estep, fbn_em_debug_posteriors and fbn_em_run read every case's value and
+ * return FBN_ERR_LIMIT naming the first such case instead of FBN_OK; fbn_em_estep_device is asynchronous
+ * and leaves that check to the caller (m of d_value).
  * Collect (sum-product): cliques deepest level first, plan order within a level.  For an unmasked entry
  *     v(e) = (((init_c[e] * M_1[map_1(e)]) * M_2[map_2(e)]) ...) over the children in clique_down order.
  *   A non-root keeps msg[s] = sum of v(e) over its unmasked entries with up(e) = s, in ascending e, from
@@ -890,7 +912,12 @@ int fbn_em_estep_device(fbn_em *s, const int8_t *d_data, int64_t ncases, double 
  * the cross-wave reduction and one kernel for the M-step and the potential rebuild; the per-case values
  * and theta (for the objective's logs) are all that comes back.  objective [max_iters][2] = {L_t, Q_t} for
  * the iterations done.  pseudo_count <= 0, max_iters < 1 or tol < 0: FBN_ERR_ARG.  Leaves the theta, byte for
- * byte, of a caller chaining fbn_em_estep, the stated M-step and fbn_em_set_parameters. */
+ * byte, of a caller chaining fbn_em_estep, the stated M-step and fbn_em_set_parameters.
+ * Range: after every M-step the host rebuilds the initial potentials from the theta that came back (the
+ * products the device formed) and checks them as fbn_em_set_parameters does; before every objective it
+ * checks the per-case values for m == 0.  Either failure is FBN_ERR_LIMIT: the handle keeps the last theta
+ * that passed (the one before the refused M-step), *iters_done counts the M-steps kept, and no count, theta
+ * or value of the refused step is reported. */
 int fbn_em_run(fbn_em *s, const int8_t *data, int64_t ncases, int max_iters, double tol, double pseudo_count,
                double *objective, int *iters_done);
 /* theta = net's probabilities; net must have the handle's structure (states, parent sets), else FBN_ERR_ARG. */

@@ -33,6 +33,7 @@ double BayesNet::Prob(int v, int q, const std::vector<int> &pv) const {
     // src/DiscreteNode.cpp:152-161: (frequency_count + 1) / (total + 1 * |dom|), int counts
     long long pc = 0;
     for (size_t j = 0; j < parents_asc[v].size(); ++j) pc = pc * dom[parents_asc[v][j]] + pv[j];
+    if (!cpt.empty()) return cpt[v][q * ((long long)cpt[v].size() / dom[v]) + pc];
     long long npc = (long long)totals[v].size();
     long long fc = counts[v][q * npc + pc];
     long long tot = totals[v][pc];
@@ -60,6 +61,30 @@ BayesNet FromCounts(int n, const int32_t *dims, const int32_t *parent_off, const
         bn.totals[v].assign((size_t)npc, 0);
         for (int q = 0; q < bn.dom[v]; ++q)
             for (long long pc = 0; pc < npc; ++pc) bn.totals[v][pc] += bn.counts[v][q * npc + pc];
+        off += bn.dom[v] * npc;
+    }
+    return bn;
+}
+
+BayesNet FromCpts(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                  const double *cpt) {
+    BayesNet bn;
+    bn.n = n;
+    bn.dom.assign(dims, dims + n);
+    bn.given.assign(n, {});
+    bn.parents_asc.assign(n, {});
+    bn.counts.assign(n, {});
+    bn.totals.assign(n, {});
+    bn.cpt.assign(n, {});
+    int64_t off = 0;
+    for (int v = 0; v < n; ++v) {
+        bn.names.push_back("X" + std::to_string(v));
+        bn.given[v].assign(parents + parent_off[v], parents + parent_off[v + 1]);
+        std::set<int> ps(bn.given[v].begin(), bn.given[v].end());
+        bn.parents_asc[v].assign(ps.begin(), ps.end());
+        long long npc = 1;
+        for (int p : bn.parents_asc[v]) npc *= bn.dom[p];
+        bn.cpt[v].assign(cpt + off, cpt + off + bn.dom[v] * npc);
         off += bn.dom[v] * npc;
     }
     return bn;

@@ -23,6 +23,9 @@ struct BayesNet {
     // counts[v][q * npc + pc] with pc = mixed radix over parents_asc (last fastest)
     std::vector<std::vector<long long>> counts;
     std::vector<std::vector<long long>> totals;  // totals[v][pc]
+    // optional probability tables in counts' layout (as fbn::Network::cpt): when non-empty, Prob
+    // returns cpt[v][q * npc + pc] as it is and counts/totals stay empty
+    std::vector<std::vector<double>> cpt;
 
     // P(v = q | parents_asc values) exactly as DiscreteNode::GetProbability computes it
     double Prob(int v, int q, const std::vector<int> &parent_vals_asc) const;
@@ -34,6 +37,10 @@ struct BayesNet {
 // last fastest (DiscreteNode::AddCount, src/DiscreteNode.cpp:114-147).  The caller passes a DAG.
 BayesNet FromCounts(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
                     const int64_t *counts);
+// The same with probabilities in the place of counts (fbn_network_create_cpt's layout); the entries
+// are taken as they are, neither smoothed nor checked.
+BayesNet FromCpts(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                  const double *cpt);
 
 // XMLBIF reader; exits the process on malformed input (the reference does the same)
 BayesNet LoadXmlbif(const std::string &path);

@@ -27,6 +27,7 @@ def _load():
         "or_jt_dims": ([_vp, _vp], C.c_int), "or_jt_dump_plan": ([_vp, C.c_char_p, C.c_char_p], C.c_int),
         "or_jt_infer": ([_vp, _vp, _i64, _vp, _vp], C.c_int),
         "or_jt_create": ([C.c_int, _vp, _vp, _vp, _vp], _vp),
+        "or_jt_create_cpt": ([C.c_int, _vp, _vp, _vp, _vp], _vp),
         "or_jt_infer_stats": ([_vp, _vp, _i64, _vp, _vp, _vp], C.c_int), "or_round7": ([_dbl], _dbl),
         "or_libsvm_load": ([C.c_char_p, C.c_int, _vp, _vp, _i64], _i64),
         "or_csv_load": ([C.c_char_p], _vp), "or_ds_from_columns": ([_vp, C.c_int, _i64, _vp], _vp),
@@ -78,6 +79,21 @@ class OracleJT:
         h = L().or_jt_create(len(d), d.ctypes.data, off.ctypes.data, par.ctypes.data, cnt.ctypes.data)
         if not h:
             raise ValueError("or_jt_create: bad arguments")
+        return cls(None, _handle=h)
+
+    @classmethod
+    def from_cpts(cls, dims, parents, cpts):
+        """A network given as probability tables in Network.from_cpts' layout: parents[v] in the node's
+        own order, cpts[v] = fp64 [dims[v]][parent configurations] over the parents in ascending index
+        order, last fastest.  The entries are used as they are."""
+        d = np.ascontiguousarray(dims, np.int32)
+        off = np.zeros(len(d) + 1, np.int32)
+        off[1:] = np.cumsum([len(ps) for ps in parents])
+        par = np.ascontiguousarray([q for ps in parents for q in ps] or [0], np.int32)
+        cpt = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float64).reshape(-1) for c in cpts]))
+        h = L().or_jt_create_cpt(len(d), d.ctypes.data, off.ctypes.data, par.ctypes.data, cpt.ctypes.data)
+        if not h:
+            raise ValueError("or_jt_create_cpt: bad arguments")
         return cls(None, _handle=h)
 
     def dump_plan(self, plan, init):

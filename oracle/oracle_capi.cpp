@@ -27,6 +27,14 @@ void *or_jt_create(int n, const int32_t *dims, const int32_t *parent_off, const 
     t->Build(FromCounts(n, dims, parent_off, parents, counts));
     return t;
 }
+// the same with probability tables (fbn_network_create_cpt's layout; bn_model.h: FromCpts)
+void *or_jt_create_cpt(int n, const int32_t *dims, const int32_t *parent_off, const int32_t *parents,
+                       const double *cpt) {
+    if (n < 1 || !dims || !parent_off || !cpt || (!parents && parent_off[n] > 0)) return nullptr;
+    auto *t = new JTree();
+    t->Build(FromCpts(n, dims, parent_off, parents, cpt));
+    return t;
+}
 void or_jt_destroy(void *h) { delete static_cast<JTree *>(h); }
 int or_jt_nvars(void *h) { return static_cast<JTree *>(h)->bn.n; }
 int or_jt_dims(void *h, int *out) {
