@@ -27,6 +27,9 @@ reference's names and argument meaning:
   log-probability, exact, by max-product on the junction forest (no reference counterpart)
 * ``ExpectationMaximization(network).fit(data)`` -- the CPTs of a known structure from rows with missing
   cells (-1), by EM with exact junction-forest E-steps on the device (no reference counterpart)
+* ``HillClimbing(score, max_parents, allowed, start).learn(source)`` -- score-based structure learning: greedy
+  hill climbing under BIC / AIC / log-likelihood, family scores batched on the device and bit-identical to
+  a host twin (no reference counterpart); ``family_scores(ci, families, penalty)`` scores arbitrary families
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -48,6 +51,10 @@ from .api import (  # noqa: F401
     SelfImportanceSampling,
     MostProbableExplanation,
     ExpectationMaximization,
+    HillClimbing,
+    family_scores,
+    hc_penalty,
+    hc_table_bytes,
     score_marginals,
     family_sizes,
     pdag_to_dag,
@@ -62,6 +69,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "HillClimbing", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -167,6 +167,18 @@ _SIGS = {
     "fbn_em_debug_posteriors": [_vp, _vp, _i64, _vp],
     "fbn_em_set_tuning": [_vp, C.c_int, _i64],
     "fbn_em_last_kernel_ms": [_vp, _vp],
+    "fbn_hc_table_bytes": [_i64, _vp],
+    "fbn_hc_penalty": [_cstr, _i64, _vp],
+    "fbn_score_families": [_vp, _dbl, _i64, _vp, _vp, _vp, _vp],
+    "fbn_score_families_host": [C.c_int, _vp, _vp, _i64, _dbl, _i64, _vp, _vp, _vp, _vp],
+    "fbn_hc_set_tuning": [_vp, _i64],
+    "fbn_hc_run": [_vp, _vp, _pp],
+    "fbn_hc_run_host": [C.c_int, _vp, _vp, _i64, _vp, _pp],
+    "fbn_hc_result_info": [_vp, _vp],
+    "fbn_hc_result_parents": [_vp, _vp, _vp],
+    "fbn_hc_result_node_scores": [_vp, _vp, _vp],
+    "fbn_hc_result_trace": [_vp, _vp, _vp],
+    "fbn_hc_result_destroy": [_vp],
 }
 
 
@@ -639,6 +651,7 @@ class IndependenceTest(_Handle):
     def __init__(self, dataset, alpha=0.05, device=0):
         self.alpha = alpha
         self.dims = np.ascontiguousarray(dataset.dims, np.int32)
+        self.num_samples = int(dataset.num_instance)
         h = C.c_void_p()
         lib.fbn_ci_dataset_upload(_p(dataset.columns), dataset.num_vars, dataset.num_instance,
                                   _p(dataset.dims), device, C.byref(h))
@@ -653,6 +666,7 @@ class IndependenceTest(_Handle):
         self.alpha = alpha
         dims = np.ascontiguousarray(dims, np.int32)
         self.dims = dims
+        self.num_samples = int(nsamples)
         h = C.c_void_p()
         lib.fbn_ci_dataset_from_device(C.c_void_p(d_cols_ptr), int(nvars), int(nsamples), _p(dims), device,
                                        C.byref(h))
@@ -960,6 +974,138 @@ class ParameterLearning:
 
     def last_kernel_ms(self):
         return self.ci.last_kernel_ms()
+
+
+def hc_penalty(score, nsamples):
+    """fbn_hc_penalty: the penalty of a named score ("bic", "aic", "loglik"), or a number as it is."""
+    if isinstance(score, str):
+        p = C.c_double()
+        lib.fbn_hc_penalty(score.encode(), int(nsamples), C.byref(p))
+        return p.value
+    return float(score)
+
+
+def hc_table_bytes(nsamples):
+    """fbn_hc_table_bytes: bytes of the n ln n table of `nsamples` samples (code -6 past 2^24).  Host only."""
+    b = C.c_int64()
+    lib.fbn_hc_table_bytes(int(nsamples), C.byref(b))
+    return b.value
+
+
+def _csr_families(families):
+    """[(child, parents...)] -> (fam_off int64 [n+1], fam_cols int32) for the C-ABI."""
+    off = np.zeros(len(families) + 1, np.int64)
+    for f, fam in enumerate(families):
+        off[f + 1] = off[f] + len(fam)
+    cols = np.ascontiguousarray([int(v) for fam in families for v in fam] or [0], np.int32)
+    return off, cols
+
+
+def family_scores(source, families, penalty=0.0):
+    """fbn_score_families: (loglik, score) float64 arrays of the families [(child, parent, ...), ...] from
+    the column store resident in `source` (an IndependenceTest: on the device), or, for a Dataset,
+    fbn_score_families_host: the host twin, bit-identical, no device."""
+    off, cols = _csr_families(families)
+    n = len(families)
+    ll, sc = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    if isinstance(source, IndependenceTest):
+        lib.fbn_score_families(source._h, float(penalty), n, _p(off), _p(cols), _p(ll), _p(sc))
+    else:
+        lib.fbn_score_families_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
+                                    float(penalty), n, _p(off), _p(cols), _p(ll), _p(sc))
+    return ll[:n], sc[:n]
+
+
+class _HcOptions(C.Structure):
+    _fields_ = [("penalty", C.c_double), ("max_parents", C.c_int32), ("max_iter", C.c_int32),
+                ("max_family_cells", C.c_int64), ("allowed", C.c_void_p), ("allowed_len", C.c_int64),
+                ("start_off", C.c_void_p), ("start_parents", C.c_void_p)]
+
+
+class _HcInfo(C.Structure):
+    _fields_ = [("nvars", C.c_int32), ("narcs", C.c_int32), ("iterations", C.c_int32), ("pad", C.c_int32),
+                ("families_scored", C.c_int64), ("batches", C.c_int64), ("score", C.c_double), ("loglik", C.c_double),
+                ("kernel_ms", C.c_double), ("first_sweep_kernel_ms", C.c_double), ("first_sweep_wall_ms", C.c_double),
+                ("score_wall_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+class HillClimbing:
+    """Score-based structure learning: greedy hill climbing over arc additions, deletions and reversals
+    (fbn_hc_run; no reference counterpart).  score: "bic" | "aic" | "loglik" or an explicit non-negative
+    penalty per free parameter.  allowed: [n][n] mask, allowed[x][y] lets the search add x -> y; start: a DAG
+    as parent lists.  learn(source): a Dataset (uploaded here), or an IndependenceTest, whose context is
+    shared (`.ci`, as PCStable.ci: ParameterLearning(hc.ci) learns from the same upload); host=True runs
+    the host twin (fbn_hc_run_host) on a Dataset, without a device.  Results: .parents (ascending parent
+    lists), .score, .loglik, .node_scores, .trace [(type, from, to, delta)] (type 0 add, 1 delete,
+    2 reverse), .iterations, .families_scored, .kernel_ms, .info."""
+
+    OPS = ("add", "delete", "reverse")
+
+    def __init__(self, score="bic", max_parents=None, max_family_cells=0, max_iter=None, allowed=None, start=None,
+                 device=0):
+        self.score_name, self.device = score, device
+        self.max_parents, self.max_family_cells, self.max_iter = max_parents, max_family_cells, max_iter
+        self.allowed, self.start = allowed, start
+        self.ci = None
+
+    def _options(self, nvars, nsamples):
+        o = _HcOptions()
+        o.penalty = hc_penalty(self.score_name, nsamples)
+        o.max_parents = -1 if self.max_parents is None else int(self.max_parents)
+        o.max_iter = -1 if self.max_iter is None else int(self.max_iter)
+        o.max_family_cells = int(self.max_family_cells)
+        keep = []
+        if self.allowed is not None:
+            a = np.ascontiguousarray(np.asarray(self.allowed) != 0, np.uint8)
+            keep.append(a)
+            o.allowed, o.allowed_len = a.ctypes.data, a.size
+        if self.start is not None:
+            off, par = _csr_parents(self.start, nvars)
+            keep += [off, par]
+            o.start_off, o.start_parents = off.ctypes.data, par.ctypes.data
+        return o, keep
+
+    def learn(self, source, host=False):
+        r = C.c_void_p()
+        if host:
+            o, keep = self._options(source.num_vars, source.num_instance)
+            lib.fbn_hc_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance, C.byref(o),
+                                C.byref(r))
+        else:
+            ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
+            self.ci = ci
+            o, keep = self._options(len(ci.dims), ci.num_samples)
+            lib.fbn_hc_run(ci._h, C.byref(o), C.byref(r))
+        del keep
+        try:
+            info = _HcInfo()
+            lib.fbn_hc_result_info(r, C.byref(info))
+            n, it = info.nvars, info.iterations
+            off, par = np.zeros(n + 1, np.int32), np.zeros(max(info.narcs, 1), np.int32)
+            lib.fbn_hc_result_parents(r, _p(off), _p(par))
+            ns_, nl = np.zeros(n), np.zeros(n)
+            lib.fbn_hc_result_node_scores(r, _p(ns_), _p(nl))
+            ops, delta = np.zeros((max(it, 1), 3), np.int32), np.zeros(max(it, 1))
+            lib.fbn_hc_result_trace(r, _p(ops), _p(delta))
+        finally:
+            lib.fbn_hc_result_destroy(r)
+        self.parents = [[int(q) for q in par[off[v]:off[v + 1]]] for v in range(n)]
+        self.score, self.loglik = info.score, info.loglik
+        self.node_scores, self.node_logliks = ns_, nl
+        self.trace = [(int(ops[k, 0]), int(ops[k, 1]), int(ops[k, 2]), float(delta[k])) for k in range(it)]
+        self.iterations, self.families_scored, self.kernel_ms = it, info.families_scored, info.kernel_ms
+        self.info = {k: getattr(info, k) for k, _ in _HcInfo._fields_ if k != "pad"}
+        return self
+
+    @property
+    def oriented(self):
+        """The learned arcs as (from, to, 1) triples, the form shd_bif and pdag_to_dag take."""
+        return [(q, v, 1) for v, ps in enumerate(self.parents) for q in ps]
+
+    @staticmethod
+    def set_tuning(ci, chunk_cells_max=0):
+        """fbn_hc_set_tuning on a context: the most table cells per chunk of a batch; 0 = default."""
+        lib.fbn_hc_set_tuning(ci._h, int(chunk_cells_max))
 
 
 def score_marginals(network, marginals, golden):

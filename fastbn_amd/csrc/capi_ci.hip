@@ -901,15 +901,8 @@ int fbn_param_counts(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *pa
     if (!counts) return FBN_OK;
     if (cap < total) return SetError(FBN_ERR_ARG, "counts holds %lld cells, %lld needed", (long long)cap, (long long)total);
     if (c->N >= (1ll << 31)) return SetError(FBN_ERR_LIMIT, "%lld samples: the device accumulators are 32-bit", (long long)c->N);
-    // slices: by default enough (family, slice) items for every CU to hold several workgroups, each
-    // slice at least 1024 samples (4 steps of the workgroup's 256 threads), a multiple of the 16
-    // samples a thread takes per step
     int64_t slice = c->par_slice;
-    if (slice <= 0) {
-        const int64_t want = (16ll * c->num_cu + V - 1) / V;  // slices per family to aim for
-        const int64_t ns = std::max<int64_t>(1, std::min<int64_t>(want, c->N / 1024));
-        slice = ((c->N + ns - 1) / ns + kParamUnit - 1) / kParamUnit * kParamUnit;
-    }
+    if (slice <= 0) slice = fbn_param_default_slice(c->N, c->num_cu, V);
     const int64_t nslices = (c->N + slice - 1) / slice;
     if ((int64_t)V * nslices > 0x7fffffffll)
         return SetError(FBN_ERR_LIMIT, "%d families x %lld slices exceed one launch", V, (long long)nslices);
@@ -942,6 +935,8 @@ int fbn_param_counts(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *pa
         return rc;
     hipStream_t s = c->stream;
     CiSlot &S = c->slot[0];
+    std::vector<uint32_t> h((size_t)total);
+    fbn::StreamDrain drain(s);  // after fam, fcol, fstr and h: an early return waits for the copies that use them
     FBN_HIP(hipMemcpyAsync(c->par_fam.p, fam.data(), fam.size() * sizeof(FbnParamFamily), hipMemcpyHostToDevice, s));
     FBN_HIP(hipMemcpyAsync(c->par_col.p, fcol.data(), fcol.size() * 4, hipMemcpyHostToDevice, s));
     FBN_HIP(hipMemcpyAsync(c->par_str.p, fstr.data(), fstr.size() * 4, hipMemcpyHostToDevice, s));
@@ -952,9 +947,9 @@ int fbn_param_counts(fbn_ci_ctx *c, const int32_t *parent_off, const int32_t *pa
                                     lds_ints * 4, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "param counts launch: %s", hipGetErrorString(e));
     if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
-    std::vector<uint32_t> h((size_t)total);
     FBN_HIP(hipMemcpyAsync(h.data(), c->par_tab.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
     FBN_HIP(hipStreamSynchronize(s));
+    drain.done();
     c->last_ms = 0.f;
     if (c->timing) FBN_HIP(hipEventElapsedTime(&c->last_ms, S.ev0, S.ev1));
     for (int64_t i = 0; i < total; ++i) counts[i] = (int64_t)h[i];

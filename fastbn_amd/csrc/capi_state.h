@@ -188,6 +188,12 @@ struct fbn_ci_ctx {
     // 32-bit family tables (zeroed by every fbn_param_counts), fbn_param_set_tuning (0 = default)
     DevBuf par_fam, par_col, par_str, par_tab;
     int64_t par_slice = 0, par_lds = 0;
+    // score-based structure learning (capi_hc.hip, hc_score.hip): L[n] = n ln n for n <= N (built on the
+    // host and uploaded by the first scoring call), the penalty terms and the two results per family of a
+    // chunk, fbn_hc_set_tuning's chunk cap (0 = FBN_PARAM_MAX_CELLS)
+    DevBuf hc_L, hc_pen, hc_out;
+    bool hc_table_ready = false;
+    int64_t hc_chunk = 0;
     ~fbn_ci_ctx() {
         if (h_open) (void)hipHostFree(h_open);
         if (h_margin) (void)hipHostFree(h_margin);

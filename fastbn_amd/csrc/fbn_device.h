@@ -55,6 +55,21 @@ struct DevBuf {
     }
 };
 
+// Declared AFTER the host buffers that asynchronous copies on `s` read or write: an early error return
+// then drains the stream before those buffers are destroyed.  The success path synchronises itself and
+// calls done().
+struct StreamDrain {
+    hipStream_t s;
+    bool armed = true;
+    explicit StreamDrain(hipStream_t st) : s(st) {}
+    void done() { armed = false; }
+    ~StreamDrain() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+    StreamDrain(const StreamDrain &) = delete;
+    StreamDrain &operator=(const StreamDrain &) = delete;
+};
+
 // a host table into b (grown to fit; never empty, so its pointer is always valid)
 template <class T>
 int Upload(DevBuf &b, const std::vector<T> &v) {

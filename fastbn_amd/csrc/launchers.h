@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, hc_score.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -111,5 +111,18 @@ struct JtEmMstepArgs;
 extern "C" hipError_t fbn_em_estep_launch(const JtEmArgs *a, hipStream_t stream);
 extern "C" hipError_t fbn_em_reduce_launch(const JtEmReduceArgs *a, hipStream_t stream);
 extern "C" hipError_t fbn_em_mstep_launch(const JtEmMstepArgs *a, hipStream_t stream);
+// The family-score reduction of the hill-climbing learner (hc_score.hip): the counted tables of
+// families [0, nfam) (param_counts.h's descriptors and key strides; tab as fbn_param_launch left it)
+// -> out[2 f] = log-likelihood, out[2 f + 1] = log-likelihood - pen[f]; L[n] = n ln n for n <= N.
+struct FbnParamFamily;
+struct HcScoreArgs {
+    const uint32_t *tab;
+    const FbnParamFamily *fam;
+    const int32_t *fstr;
+    const double *pen, *L;
+    double *out;
+    long long nfam;
+};
+extern "C" hipError_t fbn_hc_score_launch(const HcScoreArgs *a, hipStream_t stream);
 
 #endif

@@ -17,6 +17,16 @@ constexpr int kParamBlock = 256;        // threads per workgroup
 constexpr int kParamUnit = 16;          // samples per thread and step (one 16-byte load per column)
 constexpr int kParamLdsCellsMax = 8192; // largest table counted in LDS (32 KB)
 
+// the default slice length for nfam families of N samples on num_cu CUs: enough (family, slice) items
+// for every CU to hold several workgroups, each slice at least 1024 samples (4 steps of the
+// workgroup's 256 threads), a multiple of the 16 samples a thread takes per step
+inline long long fbn_param_default_slice(long long N, int num_cu, long long nfam) {
+    const long long want = (16ll * num_cu + nfam - 1) / nfam;  // slices per family to aim for
+    long long ns = N / 1024 < want ? N / 1024 : want;
+    if (ns < 1) ns = 1;
+    return ((N + ns - 1) / ns + kParamUnit - 1) / kParamUnit * kParamUnit;
+}
+
 // LDS ints a family of `cells` (<= kParamLdsCellsMax) cells needs
 extern "C" size_t fbn_param_lds_ints(int cells);
 // families [0, nfam) x slices [0, nslices) of `slice` samples, one workgroup each; tab zeroed by the

@@ -932,6 +932,85 @@ int fbn_em_set_tuning(fbn_em *s, int max_workgroups, int64_t store_bytes_max);
 /* Device time (ms, hipEvent) of the handle's last E-step kernel. */
 int fbn_em_last_kernel_ms(const fbn_em *s, float *ms);
 
+/* ------------------------------------------------------------------ score-based structure learning
+ * Greedy hill climbing over arc additions, deletions and reversals under a decomposable score (-a 14).
+ * The reference learns structure by constraint tests only, so there is no reference output to match: the
+ * device path is held bit for bit to a host twin in this library (fbn_hc_run_host, fbn_score_families_host).
+ *
+ * Score of a family (child v with r states, parents P with q joint configurations, counts N_jk in
+ * fbn_param_counts' layout):  loglik = sum_jk L[N_jk] - sum_j L[N_j],  score = loglik - penalty (r - 1) q,
+ * L[n] = n ln n.  L is a table of N + 1 doubles filled once on the host with the C library's log; both
+ * sides gather from it and add in one fixed order (hc_score.h), so a family's score is a pure function of
+ * (child, parent set, data): never of the batch, the chunk, the slices or the counting path.
+ * The table costs 8 (N + 1) bytes: more than 2^24 samples is FBN_ERR_LIMIT. */
+/* Host-only: the bytes of the score table of N samples; FBN_ERR_LIMIT past 2^24 samples, FBN_ERR_ARG for N < 1. */
+int fbn_hc_table_bytes(int64_t nsamples, int64_t *bytes);
+/* Host-only: the penalty of a named score for N samples: "bic" ln(N) / 2, "aic" 1, "loglik" 0; else FBN_ERR_ARG. */
+int fbn_hc_penalty(const char *score, int64_t nsamples, double *penalty);
+/* Scores of arbitrary families from the context's resident column store.  Family f is the columns
+ * fam_cols[fam_off[f] .. fam_off[f+1]): the child first, then its parents in any order; fam_off[0] = 0.
+ * loglik / score [nfam] doubles on the host (either may be NULL).  Validated on the host before any launch,
+ * as fbn_param_family_sizes validates: FBN_ERR_ARG for an empty family, a column out of range, a self or
+ * repeated parent, a negative or NaN penalty; FBN_ERR_LIMIT for a family above FBN_PARAM_MAX_CELLS.  A batch
+ * whose tables exceed FBN_PARAM_MAX_CELLS in all is counted and reduced in chunks.  Counting is
+ * fbn_param_counts' kernel under fbn_param_set_tuning; only 16 bytes per family return to the host.  Kernel
+ * time (zeroing + counting + reduction, summed over the chunks): fbn_ci_last_kernel_ms. */
+int fbn_score_families(fbn_ci_ctx *c, double penalty, int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols,
+                       double *loglik, double *score);
+/* The host twin of fbn_score_families over a host column store (uint8 [nvars][nsamples]): same validation,
+ * same values bit for bit.  No device. */
+int fbn_score_families_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, double penalty,
+                            int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols, double *loglik,
+                            double *score);
+/* 0 = default (FBN_PARAM_MAX_CELLS).  The most table cells counted per chunk of a batch (a larger family
+ * sits alone in its chunk): a tuning/testing entry, so tests reach multi-chunk batches at small sizes. */
+int fbn_hc_set_tuning(fbn_ci_ctx *c, int64_t chunk_cells_max);
+
+typedef struct fbn_hc_options {
+    double penalty;            /* >= 0 (fbn_hc_penalty); negative or NaN: FBN_ERR_ARG */
+    int32_t max_parents;       /* most parents a node may be GIVEN; < 0: no limit */
+    int32_t max_iter;          /* most operations applied; < 0: no limit */
+    int64_t max_family_cells;  /* an operation whose new table would exceed it is inadmissible, never an
+                                  error; <= 0 or above FBN_PARAM_MAX_CELLS: FBN_PARAM_MAX_CELLS */
+    const uint8_t *allowed;    /* [nvars][nvars]: allowed[x * nvars + y] != 0 lets the search add x -> y
+                                  (also by a reversal); NULL: every arc */
+    int64_t allowed_len;       /* nvars * nvars when allowed != NULL, else FBN_ERR_ARG */
+    const int32_t *start_off;  /* the starting DAG as CSR parent lists (fbn_param_counts' form); NULL: empty. */
+    const int32_t *start_parents; /* A cyclic start is FBN_ERR_ARG; its arcs need not satisfy the limits above */
+} fbn_hc_options;
+
+typedef struct fbn_hc_info {
+    int32_t nvars, narcs, iterations, pad;
+    int64_t families_scored;   /* families handed to the scorer, over all batches */
+    int64_t batches;           /* scorer calls: the first sweep, then one per operation */
+    double score, loglik;      /* sums of the per-node values in node order */
+    double kernel_ms;          /* device time of all batches (0 on the host twin) */
+    double first_sweep_kernel_ms, first_sweep_wall_ms; /* the first batch: device time, host wall time */
+    double score_wall_ms, wall_ms; /* wall time inside the scorer over all batches; of the whole search */
+} fbn_hc_info;
+
+typedef struct fbn_hc_result fbn_hc_result;
+
+/* Hill climbing from options->start.  Every step applies the legal operation with the largest score delta,
+ * provided it is > 0: add x -> y, delete x -> y, or reverse x -> y (delta = the delete delta in y's row plus
+ * the add delta in x's row).  Legal: no directed cycle, max_parents, max_family_cells, allowed.  Exact ties
+ * go to the lowest (type: add 0 < delete 1 < reverse 2, then the arc's head y, then its tail x; a reversal is
+ * keyed by the arc it removes).  After a step only the rows of the nodes whose parent set changed are
+ * rescored (one row, or two after a reversal), in one batch; the first sweep is one batch.  Stops when nothing improves, or at max_iter. */
+int fbn_hc_run(fbn_ci_ctx *c, const fbn_hc_options *options, fbn_hc_result **out);
+/* The same search over the host scorer (fbn_score_families_host): the host twin.  No device. */
+int fbn_hc_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                    const fbn_hc_options *options, fbn_hc_result **out);
+int fbn_hc_result_info(const fbn_hc_result *r, fbn_hc_info *info);
+/* parent_off [nvars+1], parents [narcs] ascending per node */
+int fbn_hc_result_parents(const fbn_hc_result *r, int32_t *parent_off, int32_t *parents);
+/* per-node family scores and log-likelihoods [nvars] (either may be NULL) */
+int fbn_hc_result_node_scores(const fbn_hc_result *r, double *score, double *loglik);
+/* the operation trace: ops [iterations][3] = (type, from, to) of the arc x -> y added, deleted or reversed
+ * (from = x, to = y: the arc as it stood before a reversal), delta [iterations] */
+int fbn_hc_result_trace(const fbn_hc_result *r, int32_t *ops, double *delta);
+int fbn_hc_result_destroy(fbn_hc_result *r);
+
 #ifdef __cplusplus
 }
 #endif
