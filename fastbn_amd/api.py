@@ -167,6 +167,13 @@ _SIGS = {
     "fbn_em_debug_posteriors": [_vp, _vp, _i64, _vp],
     "fbn_em_set_tuning": [_vp, C.c_int, _i64],
     "fbn_em_last_kernel_ms": [_vp, _vp],
+    "fbn_psample_create": [_vp, C.c_int, _pp],
+    "fbn_psample_destroy": [_vp],
+    "fbn_psample_info": [_vp, _vp, _vp, _vp, _vp],
+    "fbn_psample_run": [_vp, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp],
+    "fbn_psample_run_device": [_vp, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp],
+    "fbn_psample_set_tuning": [_vp, C.c_int, _i64, _i64],
+    "fbn_psample_last_kernel_ms": [_vp, _vp],
     "fbn_hc_table_bytes": [_i64, _vp],
     "fbn_hc_penalty": [_cstr, _i64, _vp],
     "fbn_score_families": [_vp, _dbl, _i64, _vp, _vp, _vp, _vp],
@@ -239,7 +246,7 @@ lib = _Lib()
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
                 "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2, "MostProbableExplanation": 2,
-                "ExpectationMaximization": 2,
+                "ExpectationMaximization": 2, "PosteriorSampler": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -1618,4 +1625,60 @@ class ExpectationMaximization(_Handle):
     def last_kernel_ms(self):
         ms = C.c_float()
         lib.fbn_em_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+
+class PosteriorSampler(_Handle):
+    """Exact posterior sampling (fbn_psample): complete assignments distributed as P(x | e) and log P(e), by
+    a sum-product Collect and a sampled top-down trace on the junction forest, so it takes any DAG.  Every
+    draw is independent and weighs 1, however unlikely the evidence.  A sample depends on (seed, case_offset
+    + case, sample index, draws) alone: never on the batch, its split, the grid or the device; changing
+    `draws` changes every sample (the stream position uses it).  The reference has no counterpart.
+    device < 0: the host twin (bit-identical results)."""
+
+    _destroy = "fbn_psample_destroy"
+
+    def __init__(self, network, device=0):
+        self.network = network
+        h = C.c_void_p()
+        lib.fbn_psample_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def info(self):
+        """dict(cliques, entries, store_rows, components): store_rows = rows of one wave's store."""
+        c, e, r, k = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+        lib.fbn_psample_info(self._h, C.byref(c), C.byref(e), C.byref(r), C.byref(k))
+        return {"cliques": c.value, "entries": e.value, "store_rows": r.value, "components": k.value}
+
+    def value_parts(self, evidence, draws=1, seed=0, case_offset=0):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (samples int8 [ncases][draws][num_nodes],
+        value fp64 [ncases][2] = (m, ex) with P(e) = m * 2^ex, m in [0.5, 1)).  A case of probability 0
+        raises FastBNError (FBN_ERR_LIMIT) naming it."""
+        ev = np.ascontiguousarray(evidence, dtype=np.int8)
+        n = ev.shape[0]
+        samples = np.zeros((n, max(int(draws), 0), self.network.num_nodes), np.int8)
+        value = np.zeros((n, 2), np.float64)
+        lib.fbn_psample_run(self._h, _p(ev), n, int(draws), int(seed), int(case_offset), _p(samples), _p(value))
+        return samples, value
+
+    def sample(self, evidence, draws=1, seed=0, case_offset=0):
+        """-> (samples int8 [ncases][draws][num_nodes], log_p fp64 [ncases] = log P(e))."""
+        samples, value = self.value_parts(evidence, draws, seed, case_offset)
+        return samples, np.log(value[:, 0]) + value[:, 1] * np.log(2.0)
+
+    def run_device(self, d_evidence_ptr, ncases, draws, d_samples_ptr, d_value_ptr, seed=0, case_offset=0,
+                   stream_ptr=None):
+        """Device-resident run (asynchronous on the stream after the evidence check)."""
+        lib.fbn_psample_run_device(self._h, C.c_void_p(d_evidence_ptr), int(ncases), int(draws), int(seed),
+                                   int(case_offset), C.c_void_p(d_samples_ptr), C.c_void_p(d_value_ptr), stream_ptr)
+
+    def set_tuning(self, max_workgroups=0, store_bytes_max=0, sample_chunk=0):
+        """fbn_psample_set_tuning: the grid cap and the store budget as MostProbableExplanation.set_tuning;
+        sample_chunk = draws of a case that share one Collect.  0 = default.  Results do not change."""
+        lib.fbn_psample_set_tuning(self._h, int(max_workgroups), int(store_bytes_max), int(sample_chunk))
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_psample_last_kernel_ms(self._h, C.byref(ms))
         return ms.value

@@ -932,6 +932,72 @@ int fbn_em_set_tuning(fbn_em *s, int max_workgroups, int64_t store_bytes_max);
 /* Device time (ms, hipEvent) of the handle's last E-step kernel. */
 int fbn_em_last_kernel_ms(const fbn_em *s, float *ms);
 
+/* ------------------------------------------------------------------ exact posterior sampling
+ * Complete assignments x distributed exactly as P(x | e), S independent draws per evidence case, and P(e):
+ * ancestral sampling on the calibrated junction forest (-a 15).  Multiple imputation of rows with holes,
+ * unbiased estimates of any joint P(Q1, Q2, ... | e) with a binomial error, posterior-predictive checks.
+ * Where the importance samplers above degrade with unlikely evidence, every draw here weighs 1 (ess = S).
+ * The reference has no counterpart.
+ *
+ * Plan and program: the forest plan and the tables of MPE (above fbn_mpe_create), unchanged: evidence by
+ * masking, init_c, children in clique_down order, and after the plan's table reorganisation up(e) = e mod Ts,
+ * so the entries of a clique that share the upstream separator entry s are s, s + Ts, ... ascending.
+ * Collect: the E-step's (above fbn_em_create), to the operation: v(e) = (((init_c[e] * M_1[map_1(e)]) *
+ *   M_2[map_2(e)]) ...) over the children in clique_down order for unmasked entries; a non-root sums v(e) per
+ *   upstream separator entry in ascending e from 0.0, scales the row by the power of two of its largest
+ *   entry (frexp / ldexp) and carries the integer exponent; the roots' sums multiply into {m, ex} from
+ *   (1.0, 0) in ascending component order, re-frexp after each multiply.  value[case] = {m, ex}, m in
+ *   [0.5, 1), P(e) = m * 2^ex: the bytes of fbn_em_estep's value on the same network and rows.
+ * Draw s of case c (S draws per case, all from the one Collect): cliques levels ascending, plan order within
+ *   a level (the back-trace order of MPE); clique number i of that order, i = 0 .. nc - 1:
+ *   1. candidates: all entries of a root, ascending; for a clique with parent p the entries e = s*, s* + Ts,
+ *      ... with s* = map_{p->c}(e*_p), e*_p the entry this draw chose in p;
+ *   2. Z = the sum of v(e) over the unmasked candidates in ascending e from 0.0 (v exactly as in Collect);
+ *   3. t = u * Z, u the draw's uniform number for this clique (below);
+ *   4. e*_c = the first unmasked candidate, ascending, whose running sum (same order, from 0.0) is > t;
+ *   5. u * Z can round up to Z: if no candidate qualifies, e*_c = the last unmasked candidate with v(e) > 0.
+ *      A candidate with v(e) = 0 is never chosen (a running sum it leaves unchanged was not > t before);
+ *   6. the digits of e*_c assign the clique's variables that are not in its upstream separator (those were
+ *      assigned by the parent).  Observed variables keep their evidence code; the row is complete.
+ *   Given the parent's choice, a candidate is chosen with probability v(e) / Z = P(clique | separator, e), so
+ *   the row is a draw from P(x | e) -- exact up to the fp64 rounding of v and of u * Z.
+ * Random numbers: u = PcgDouble of numpy.random.PCG64(seed) at stream position
+ *   ((case_offset + c) * S + s) * nc + i: draw number p of the generator, counted from 0 (the samplers' rule).
+ *   Every clique takes exactly one number, whether or not it has a free variable.  A sample therefore depends
+ *   on (seed, case_offset + c, s, S) alone: never on the batch, its split into calls (with case_offset), the
+ *   grid, the chunk or the device.  S is part of the position: sample s of a run with S draws is not sample s
+ *   of a run with S' != S draws.
+ * Zero probability: a case whose m == 0 (evidence of probability 0 in a probability network, or the
+ *   in-clique underflow stated above fbn_mpe_create) has no posterior: fbn_psample_run returns FBN_ERR_LIMIT
+ *   naming the first such case, as fbn_mpe_run and fbn_em_estep do; fbn_psample_run_device is asynchronous
+ *   and leaves that check to the caller (m of d_value; the rows of such a case mean nothing).
+ * Only *, +, comparisons, frexp and ldexp, in one order, no FMA contraction: two runs, any split, any grid, any
+ * chunk and the host twin give identical bytes.
+ * Limits: as MPE's at create (one wave's store here is store_rows * 512 bytes with store_rows = separator
+ *   entries + separators + 4 * cliques); per call nsamples < 1 or a stream position past 2^63: FBN_ERR_ARG;
+ *   ncases * nsamples past 2^31 - 1, or an output beyond int64 indexing: FBN_ERR_LIMIT. */
+typedef struct fbn_psample fbn_psample;
+/* device < 0: a host-only handle running the host twin (bit-identical); its *_device entry returns FBN_ERR_NODEV. */
+int fbn_psample_create(const fbn_network *net, int device, fbn_psample **out);
+int fbn_psample_destroy(fbn_psample *s);
+/* cliques, the sum of their entries, the rows of one wave's store and the forest's components. */
+int fbn_psample_info(const fbn_psample *s, int64_t *cliques, int64_t *entries, int64_t *store_rows, int *components);
+/* evidence [ncases][V] int8 (-1 = unobserved; checked as fbn_mpe_run checks) -> samples [ncases][nsamples][V]
+ * int8, value [ncases][2] fp64 = {m, ex}.  case_offset: the global index of the batch's first case.  Host
+ * arrays, synchronous. */
+int fbn_psample_run(fbn_psample *s, const int8_t *evidence, int64_t ncases, int64_t nsamples, uint64_t seed,
+                    int64_t case_offset, int8_t *samples, double *value);
+/* The same with device-resident buffers; asynchronous on hip_stream after the evidence check (one stream sync). */
+int fbn_psample_run_device(fbn_psample *s, const int8_t *d_evidence, int64_t ncases, int64_t nsamples, uint64_t seed,
+                           int64_t case_offset, int8_t *d_samples, double *d_value, void *hip_stream);
+/* Kernel tuning, as fbn_mpe_set_tuning, and sample_chunk: the draws of a case that share one Collect on the
+ * device (a unit of work is a 64-case block and one chunk; 0 = default: all of them when the blocks alone fill
+ * the chip, else the largest chunk that still gives every resident wave a unit).  Results never depend on any
+ * of the three. */
+int fbn_psample_set_tuning(fbn_psample *s, int max_workgroups, int64_t store_bytes_max, int64_t sample_chunk);
+/* Device kernel time (ms, hipEvent) of the handle's last launch. */
+int fbn_psample_last_kernel_ms(const fbn_psample *s, float *ms);
+
 /* ------------------------------------------------------------------ score-based structure learning
  * Greedy hill climbing over arc additions, deletions and reversals under a decomposable score (-a 14).
  * The reference learns structure by constraint tests only, so there is no reference output to match: the
