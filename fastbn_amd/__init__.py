@@ -29,6 +29,9 @@ reference's names and argument meaning:
   cells (-1), by EM with exact junction-forest E-steps on the device (no reference counterpart)
 * ``PosteriorSampler(network).sample(evidence, draws)`` -- complete assignments distributed exactly as
   P(x | e), and log P(e), by a sampled trace on the calibrated junction forest (no reference counterpart)
+* ``GibbsSampling(network, chains, sweeps, burn_in, seed).infer(evidence)`` -- posterior marginals by Markov-chain
+  Monte Carlo, for networks whose cliques no junction forest fits and evidence that starves the importance
+  samplers; the chains' last states are approximate draws from P(x | e) (no reference counterpart)
 * ``HillClimbing(score, max_parents, allowed, start).learn(source)`` -- score-based structure learning: greedy
   hill climbing under BIC / AIC / log-likelihood, family scores batched on the device and bit-identical to
   a host twin (no reference counterpart); ``family_scores(ci, families, penalty)`` scores arbitrary families
@@ -54,6 +57,7 @@ from .api import (  # noqa: F401
     MostProbableExplanation,
     ExpectationMaximization,
     PosteriorSampler,
+    GibbsSampling,
     HillClimbing,
     family_scores,
     hc_penalty,
@@ -72,6 +76,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "HillClimbing", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

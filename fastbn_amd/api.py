@@ -174,6 +174,14 @@ _SIGS = {
     "fbn_psample_run_device": [_vp, _vp, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp],
     "fbn_psample_set_tuning": [_vp, C.c_int, _i64, _i64],
     "fbn_psample_last_kernel_ms": [_vp, _vp],
+    "fbn_gibbs_create": [_vp, C.c_int, _pp],
+    "fbn_gibbs_destroy": [_vp],
+    "fbn_gibbs_run": [_vp, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp],
+    "fbn_gibbs_run_device": [_vp, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _vp, _vp, _vp, _vp],
+    "fbn_gibbs_set_tuning": [_vp, _i64, C.c_int, C.c_int],
+    "fbn_gibbs_info": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "fbn_gibbs_last_kernel_ms": [_vp, _vp],
+    "fbn_gibbs_debug_conditionals": [_vp, _vp, _i64, _vp],
     "fbn_hc_table_bytes": [_i64, _vp],
     "fbn_hc_penalty": [_cstr, _i64, _vp],
     "fbn_score_families": [_vp, _dbl, _i64, _vp, _vp, _vp, _vp],
@@ -246,7 +254,7 @@ lib = _Lib()
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
                 "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2, "MostProbableExplanation": 2,
-                "ExpectationMaximization": 2, "PosteriorSampler": 2,
+                "ExpectationMaximization": 2, "PosteriorSampler": 2, "GibbsSampling": 2,
                 "IndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
@@ -1681,4 +1689,72 @@ class PosteriorSampler(_Handle):
     def last_kernel_ms(self):
         ms = C.c_float()
         lib.fbn_psample_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+
+class GibbsSampling(_CaseInference, _Handle):
+    """Gibbs sampling (fbn_gibbs, -a 16), mirroring the samplers: per evidence case `chains` independent
+    chains, each a forward start with the evidence clamped, burn_in discarded sweeps and `sweeps` counted
+    ones over the unobserved variables; the marginals are the Rao-Blackwell average of the conditionals the
+    draws were made from.  Nothing is weighed, so unlikely evidence costs nothing, and only the tables of a
+    variable and its children are read, so any DAG is taken.  Not ergodic where zero table entries
+    disconnect the state space (no network built here has one).  A case's result depends on (seed, global
+    case index, chains, burn_in, sweeps) alone.  The reference has no counterpart.  device < 0: the host
+    twin (bit-identical results)."""
+
+    _destroy = "fbn_gibbs_destroy"
+
+    def __init__(self, network, chains=64, sweeps=256, burn_in=64, seed=0, device=0):
+        self.network = network
+        self.chains, self.sweeps, self.burn_in, self.seed = int(chains), int(sweeps), int(burn_in), int(seed)
+        self.sum_dom = int(np.sum(network.dims))
+        h = C.c_void_p()
+        lib.fbn_gibbs_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def infer(self, evidence, marginals=True, states=False, case_offset=0):
+        """evidence [ncases][num_nodes] int8 (-1 unobserved) -> (labels, marginals or None), and with
+        states=True a third item: the chains' last assignments int8 [ncases][chains][num_nodes], `chains`
+        draws per case from approximately P(x | e).  case_offset: the global index of the first case (a
+        batch split over calls gives the bits of the whole batch)."""
+        ev, n, labels, marg, _ = self._outputs(evidence, marginals, 0)
+        st = np.zeros((n, max(self.chains, 0), self.network.num_nodes), np.int8) if states else None
+        lib.fbn_gibbs_run(self._h, _p(ev), n, self.chains, self.burn_in, self.sweeps, self.seed, int(case_offset),
+                          _p(labels), _p(marg), _p(st))
+        return (labels, marg, st) if states else (labels, marg)
+
+    def run_device(self, d_evidence_ptr, ncases, d_labels_ptr, d_marg_ptr=None, d_states_ptr=None, case_offset=0,
+                   stream_ptr=None):
+        """Device-resident run (asynchronous on the stream after the evidence check); d_states int8
+        [ncases][chains][num_nodes] or None."""
+        lib.fbn_gibbs_run_device(self._h, C.c_void_p(d_evidence_ptr), int(ncases), self.chains, self.burn_in,
+                                 self.sweeps, self.seed, int(case_offset), C.c_void_p(d_labels_ptr),
+                                 C.c_void_p(d_marg_ptr) if d_marg_ptr else None,
+                                 C.c_void_p(d_states_ptr) if d_states_ptr else None, stream_ptr)
+
+    def conditionals(self, states):
+        """states int8 [n][num_nodes], complete assignments -> fp64 [n][sum_dom]: every variable's normalised
+        conditional given all the others, by the function the sweep calls (fbn_gibbs_debug_conditionals)."""
+        st = np.ascontiguousarray(states, dtype=np.int8)
+        out = np.zeros((st.shape[0], self.sum_dom), np.float64)
+        lib.fbn_gibbs_debug_conditionals(self._h, _p(st), st.shape[0], _p(out))
+        return out
+
+    def set_tuning(self, lds_bytes_max=0, max_workgroups=0, pc_cache=-1):
+        """fbn_gibbs_set_tuning: lds_bytes_max < 0 keeps the accumulators in a global workspace instead of
+        LDS; max_workgroups caps the persistent grid; pc_cache 0 / 1 recomputes / caches the children's
+        parent configurations (-1: the default).  Results do not change."""
+        lib.fbn_gibbs_set_tuning(self._h, int(lds_bytes_max), int(max_workgroups), int(pc_cache))
+
+    def info(self, ncases=1):
+        """dict(lds_bytes, path, pc_cache, grid): path 0 = the accumulators in LDS, 1 = in global memory;
+        grid = the workgroups a run of ncases cases launches."""
+        b, p, k, g = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+        lib.fbn_gibbs_info(self._h, int(ncases), max(self.chains, 1), C.byref(b), C.byref(p), C.byref(k), C.byref(g))
+        return {"lds_bytes": b.value, "path": p.value, "pc_cache": k.value, "grid": g.value}
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_gibbs_last_kernel_ms(self._h, C.byref(ms))
         return ms.value

@@ -24,6 +24,8 @@
 // -a 15, this build's own: exact posterior sampling on -a 12's inputs: -q draws per case from P(x | e) under
 // --seed; prints the case count, the average log P(e) and the kernel time; --out FILE writes the drawn rows
 // as LIBSVM, the -q rows of a case one after the other (label = the value of variable 0).
+// -a 16, this build's own: Gibbs sampling on -a 10's inputs and flags: -q chains per case, -m burn-in sweeps,
+// -l counted sweeps (their defaults are -a 10's: 10000, 10, 2500), --seed; prints -a 10's result lines.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -63,7 +65,7 @@ int main(int argc, char **argv) {
         if (a == "--max-parents" && i + 1 < argc) { max_parents = atoi(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
                          "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik] [--max-parents K] [--out FILE] [--prefix DIR]"
@@ -564,12 +566,63 @@ int main(int argc, char **argv) {
         }
         fbn_psample_destroy(ps);
         fbn_network_destroy(net);
+    } else if (algorithm == 16) {
+        // Gibbs sampling: no counterpart in the reference; -a 10's result lines
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: Gibbs sampling for approximate inference, #threads = " << num_threads << std::endl
+                  << "chains = " << num_samples << ", burn-in sweeps = " << max_updating << ", counted sweeps = " << updating_interval
+                  << ", seed = " << seed << std::endl
+                  << "\tBN: " << net_file << std::endl
+                  << "\ttesting set: " << test_set_file << std::endl
+                  << "\treference potential table: " << pt_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        fbn_network *net = nullptr;
+        if (fbn_network_load_xmlbif(net_file.c_str(), &net)) return die();
+        int n = 0;
+        fbn_network_num_nodes(net, &n);
+        TestSet tester;
+        if (tester.Load(test_set_file, n)) return die();
+        const int64_t nc = tester.num_instances();
+        std::vector<int32_t> dims(n);
+        fbn_network_dims(net, dims.data());
+        int sum_dom = 0;
+        for (int d : dims) sum_dom += d;
+        std::vector<double> golden = LoadGroundTruth(pt_file, dims, nc);
+        std::cout << "==================================================" << '\n'
+                  << "Begin testing the trained network." << std::endl;
+        fbn_gibbs *gs = nullptr;
+        if (fbn_gibbs_create(net, device, &gs)) return die();
+        std::vector<int32_t> predictions((size_t)nc);
+        std::vector<double> marginals((size_t)nc * sum_dom);
+        if (fbn_gibbs_run(gs, tester.evidence.data(), nc, num_samples, max_updating, updating_interval, seed, 0,
+                          predictions.data(), marginals.data(), nullptr))
+            return die();
+        float kms = 0.f;
+        const bool timed = fbn_gibbs_last_kernel_ms(gs, &kms) == 0;  // not on the host path (--device -1)
+        double mse = 0, hd = 0;
+        if (fbn_score_marginals(net, marginals.data(), golden.data(), nc, &mse, &hd)) return die();
+        int64_t correct = 0;
+        for (int64_t c = 0; c < nc; ++c) correct += predictions[c] == tester.ground_truths[c];
+        std::cout << "average MSE = " << mse / nc << std::endl;
+        std::cout << "average HD = " << hd / nc << std::endl;
+        std::cout << "==================================================" << std::endl;
+        if (timed)
+            std::cout << "gibbs: device kernel " << kms * 1e-3 << " s, "
+                      << (double)nc * (double)num_samples * (double)(max_updating + updating_interval) / (kms * 1e-3)
+                      << " chain-sweeps/s" << std::endl;
+        std::cout << "accuracy = " << correct / (double)nc << std::endl;
+        fbn_gibbs_destroy(gs);
+        fbn_network_destroy(net);
     } else if (algorithm == 9) {
         // SISv1 (ALGSISV1, src/main.cpp:162-173): the reference names it and defines it nowhere, in code or papers
         std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
                   << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14 and 15)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15 and 16)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, gibbs.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -115,6 +115,17 @@ extern "C" hipError_t fbn_em_mstep_launch(const JtEmMstepArgs *a, hipStream_t st
 // workgroups over the units (64-case block, chunk of a->chunk samples), a->store_rows rows of a->store each.
 struct JtPsampleArgs;
 extern "C" hipError_t fbn_psample_launch(const JtPsampleArgs *a, hipStream_t stream);
+// The Gibbs sampler's kernels (gibbs_model.h's arguments).  fbn_gibbs_launch: a persistent grid of `grid`
+// one-wave workgroups over the a->units (case, 64-chain chunk) units, lds_bytes of dynamic LDS each
+// (lds_acc != 0: the accumulators among them; a->pc_cache: the parent configurations too), then the
+// finish kernel over the cases.  fbn_gibbs_cond_launch: one assignment per lane.
+namespace fbn {
+struct GibbsDeviceArgs;
+struct GibbsCondArgs;
+}
+extern "C" hipError_t fbn_gibbs_launch(const fbn::GibbsDeviceArgs *a, int lds_acc, size_t lds_bytes, int grid,
+                                       hipStream_t stream);
+extern "C" hipError_t fbn_gibbs_cond_launch(const fbn::GibbsCondArgs *a, size_t lds_bytes, hipStream_t stream);
 // The family-score reduction of the hill-climbing learner (hc_score.hip): the counted tables of
 // families [0, nfam) (param_counts.h's descriptors and key strides; tab as fbn_param_launch left it)
 // -> out[2 f] = log-likelihood, out[2 f + 1] = log-likelihood - pen[f]; L[n] = n ln n for n <= N.

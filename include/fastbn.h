@@ -998,6 +998,76 @@ int fbn_psample_set_tuning(fbn_psample *s, int max_workgroups, int64_t store_byt
 /* Device kernel time (ms, hipEvent) of the handle's last launch. */
 int fbn_psample_last_kernel_ms(const fbn_psample *s, float *ms);
 
+/* ------------------------------------------------------------------ Gibbs sampling
+ * Markov-chain Monte Carlo posterior marginals (-a 16) for the case the other engines leave open: cliques
+ * too large for the junction forest and evidence unlikely enough that importance weights collapse.  A
+ * chain moves inside P(x | e) one variable at a time and reads only the tables of a variable and of its
+ * children, so nothing is weighed and any DAG the samplers take is accepted.  The reference has no
+ * counterpart.  Gibbs sampling is not ergodic where zero table entries disconnect the state space; a
+ * network built here has none (fbn_network_create_cpt refuses them, counts are smoothed).
+ *
+ * Per evidence case `chains` >= 1 independent chains, each the start, `burn_in` >= 0 discarded sweeps and
+ * `sweeps` >= 1 counted sweeps: passes = 1 + burn_in + sweeps.
+ * Start: the variables in topological order (the samplers' order); an observed variable is clamped, an
+ *   unobserved one drawn from its cdf row under the values before it, as fbn_lw_run draws (no weight).
+ * Sweep: the unobserved variables in topological order.  For variable v with r states,
+ *   g[k] = P(v = k | pa(v)) * prod_c P(x_c | pa(c) with v = k), k ascending, the children c in ascending
+ *   topological position, the product formed left to right; tot = the sum of g in ascending k from 0.0;
+ *   the new value is the samplers' selection rule over the running sums of g: x = u * tot, the first k
+ *   whose running sum is > x (else r - 1).  tot == 0.0 (a dead end of zero entries; only a hand-built model
+ *   has them): the value stays, the uniform number is consumed.
+ * Estimator, counted sweeps only: entry (v, k) takes g[k] / tot (tot == 0.0: 1.0 for the kept value, else
+ *   0.0), the conditional the draw was made from (Rao-Blackwell).  Sums: the chains of a case in chunks of
+ *   64; within a chunk the butterfly of the samplers (lane i adds lane i ^ off, off = 32 .. 1; the lanes
+ *   past `chains` hold +0.0); across sweeps ascending into the chunk's sum; across chunks ascending; the
+ *   marginal = sum / (double)(chains * sweeps).  Observed variables' rows are zeros; the label is the
+ *   samplers' arg-max of the query's row.
+ * Stream: numpy.random.PCG64(seed); chain i of case c is global chain g = (case_offset + c) * chains + i and
+ *   owns the positions [g * P, (g + 1) * P), P = V * passes; topological position t in pass s draws at
+ *   g * P + s * V + t.  An observed variable skips the draw and keeps the position.  A case's result
+ *   depends on (seed, global case index, chains, burn_in, sweeps) only: never on the batch, its split into
+ *   calls, the grid, the home of the accumulators or the parent-configuration cache.
+ * Only +, *, / and comparisons in one order, no FMA contraction: the device and the host twin agree bit
+ * for bit.
+ * Create: the sampler's limits, and for every node the product of the smallest positive table entries of
+ *   the node and of each of its children must be at least DBL_MIN * 2^53 = 2^-969, else FBN_ERR_LIMIT naming
+ *   the node: a conditional is then zero only where a table entry is zero, never by underflow (the policy
+ *   of the exact engines' clique check).  64 V + 512 dmax bytes of LDS beyond 160 KiB: FBN_ERR_LIMIT.
+ * Run: chains < 1, sweeps < 1, burn_in < 0, a stream position ((case_offset + ncases) * chains + 64) * P at
+ *   or past 2^63: FBN_ERR_ARG; more than 2^31 - 1 (case, chunk) units: FBN_ERR_LIMIT.  Evidence codes are
+ *   checked first, as everywhere. */
+typedef struct fbn_gibbs fbn_gibbs;
+/* device < 0: a host-only handle running the host twin (bit-identical); its *_device entry returns FBN_ERR_NODEV. */
+int fbn_gibbs_create(const fbn_network *net, int device, fbn_gibbs **out);
+int fbn_gibbs_destroy(fbn_gibbs *s);
+/* evidence [ncases][V] int8 (-1 = unobserved) -> labels [ncases], marginals [ncases][sum_dom] (or NULL),
+ * states int8 [ncases][chains][V] (or NULL): the chains' assignments after the last sweep, `chains` draws
+ * per case from approximately P(x | e).  Host arrays, synchronous. */
+int fbn_gibbs_run(fbn_gibbs *s, const int8_t *evidence, int64_t ncases, int64_t chains, int64_t burn_in, int64_t sweeps,
+                  uint64_t seed, int64_t case_offset, int32_t *labels, double *marginals, int8_t *states);
+/* The same with device-resident buffers: asynchronous on hip_stream after the evidence check (one stream
+ * sync, as fbn_lw_run_device's). */
+int fbn_gibbs_run_device(fbn_gibbs *s, const int8_t *d_evidence, int64_t ncases, int64_t chains, int64_t burn_in,
+                         int64_t sweeps, uint64_t seed, int64_t case_offset, int32_t *d_labels, double *d_marginals,
+                         int8_t *d_states, void *hip_stream);
+/* Kernel tuning (an explicit API, not an environment variable).  A workgroup always holds the values (64 V
+ * bytes) and the conditional scratch (512 dmax) in LDS.  lds_bytes_max: while the total stays within it, the
+ * unit's accumulators (8 sum_dom) join them, then the cached parent configurations (256 V); accumulators
+ * that do not fit live in the unit's row of a global workspace.  0 = default (160 KiB, also the maximum),
+ * < 0 forces the global accumulators.  max_workgroups: cap of the persistent grid, 0 = default.  pc_cache:
+ * 0 recomputes a child's parent configuration on every update, 1 caches where it fits, -1 the default.
+ * Results depend on none of the three.  fbn_gibbs_info: the LDS bytes, the accumulators' home (0 LDS, 1
+ * global), the cache (0 / 1) and the grid a run of ncases cases of `chains` chains takes next. */
+int fbn_gibbs_set_tuning(fbn_gibbs *s, int64_t lds_bytes_max, int max_workgroups, int pc_cache);
+int fbn_gibbs_info(const fbn_gibbs *s, int64_t ncases, int64_t chains, int64_t *lds_bytes, int *path, int *pc_cache,
+                   int *grid);
+/* Device time (ms, hipEvent) of the handle's last run: the sampling launch and its finish. */
+int fbn_gibbs_last_kernel_ms(const fbn_gibbs *s, float *ms);
+/* Testing interface: states int8 [n][V], complete assignments (else FBN_ERR_ARG) -> out [n][sum_dom]: for
+ * every variable its normalised conditional given all the others, g[k] / tot as the estimator takes it,
+ * by the function the sweep calls.  n * sum_dom <= 2^22.  Host arrays. */
+int fbn_gibbs_debug_conditionals(fbn_gibbs *s, const int8_t *states, int64_t n, double *out);
+
 /* ------------------------------------------------------------------ score-based structure learning
  * Greedy hill climbing over arc additions, deletions and reversals under a decomposable score (-a 14).
  * The reference learns structure by constraint tests only, so there is no reference output to match: the
