@@ -35,6 +35,8 @@ reference's names and argument meaning:
 * ``HillClimbing(score, max_parents, allowed, start).learn(source)`` -- score-based structure learning: greedy
   hill climbing under BIC / AIC / log-likelihood, family scores batched on the device and bit-identical to
   a host twin (no reference counterpart); ``family_scores(ci, families, penalty)`` scores arbitrary families
+* ``ExactSearch(score, max_parents, allowed).learn(source)`` -- the globally best DAG under the same scores for
+  up to 26 variables, by dynamic programming over variable subsets on the device (no reference counterpart)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -59,6 +61,7 @@ from .api import (  # noqa: F401
     PosteriorSampler,
     GibbsSampling,
     HillClimbing,
+    ExactSearch,
     family_scores,
     hc_penalty,
     hc_table_bytes,
@@ -76,6 +79,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -194,6 +194,10 @@ _SIGS = {
     "fbn_hc_result_node_scores": [_vp, _vp, _vp],
     "fbn_hc_result_trace": [_vp, _vp, _vp],
     "fbn_hc_result_destroy": [_vp],
+    "fbn_exact_run": [_vp, _vp, _pp],
+    "fbn_exact_run_host": [C.c_int, _vp, _vp, _i64, _vp, _pp],
+    "fbn_exact_result_info": [_vp, _vp],
+    "fbn_exact_set_tuning": [_vp, _i32],
 }
 
 
@@ -1044,6 +1048,33 @@ class _HcInfo(C.Structure):
                 ("score_wall_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+def _take_hc_result(self, r):
+    """The fields of an fbn_hc_result onto `self` (HillClimbing, ExactSearch); destroys r."""
+    try:
+        info = _HcInfo()
+        lib.fbn_hc_result_info(r, C.byref(info))
+        n, it = info.nvars, info.iterations
+        off, par = np.zeros(n + 1, np.int32), np.zeros(max(info.narcs, 1), np.int32)
+        lib.fbn_hc_result_parents(r, _p(off), _p(par))
+        ns_, nl = np.zeros(n), np.zeros(n)
+        lib.fbn_hc_result_node_scores(r, _p(ns_), _p(nl))
+        ops, delta = np.zeros((max(it, 1), 3), np.int32), np.zeros(max(it, 1))
+        lib.fbn_hc_result_trace(r, _p(ops), _p(delta))
+        if isinstance(self, ExactSearch):
+            ex = _ExactInfo()
+            lib.fbn_exact_result_info(r, C.byref(ex))
+            self.exact_info = {k: getattr(ex, k) for k, _ in _ExactInfo._fields_}
+    finally:
+        lib.fbn_hc_result_destroy(r)
+    self.parents = [[int(q) for q in par[off[v]:off[v + 1]]] for v in range(n)]
+    self.score, self.loglik = info.score, info.loglik
+    self.node_scores, self.node_logliks = ns_, nl
+    self.trace = [(int(ops[k, 0]), int(ops[k, 1]), int(ops[k, 2]), float(delta[k])) for k in range(it)]
+    self.iterations, self.families_scored, self.kernel_ms = it, info.families_scored, info.kernel_ms
+    self.info = {k: getattr(info, k) for k, _ in _HcInfo._fields_ if k != "pad"}
+    return self
+
+
 class HillClimbing:
     """Score-based structure learning: greedy hill climbing over arc additions, deletions and reversals
     (fbn_hc_run; no reference counterpart).  score: "bic" | "aic" | "loglik" or an explicit non-negative
@@ -1092,25 +1123,7 @@ class HillClimbing:
             o, keep = self._options(len(ci.dims), ci.num_samples)
             lib.fbn_hc_run(ci._h, C.byref(o), C.byref(r))
         del keep
-        try:
-            info = _HcInfo()
-            lib.fbn_hc_result_info(r, C.byref(info))
-            n, it = info.nvars, info.iterations
-            off, par = np.zeros(n + 1, np.int32), np.zeros(max(info.narcs, 1), np.int32)
-            lib.fbn_hc_result_parents(r, _p(off), _p(par))
-            ns_, nl = np.zeros(n), np.zeros(n)
-            lib.fbn_hc_result_node_scores(r, _p(ns_), _p(nl))
-            ops, delta = np.zeros((max(it, 1), 3), np.int32), np.zeros(max(it, 1))
-            lib.fbn_hc_result_trace(r, _p(ops), _p(delta))
-        finally:
-            lib.fbn_hc_result_destroy(r)
-        self.parents = [[int(q) for q in par[off[v]:off[v + 1]]] for v in range(n)]
-        self.score, self.loglik = info.score, info.loglik
-        self.node_scores, self.node_logliks = ns_, nl
-        self.trace = [(int(ops[k, 0]), int(ops[k, 1]), int(ops[k, 2]), float(delta[k])) for k in range(it)]
-        self.iterations, self.families_scored, self.kernel_ms = it, info.families_scored, info.kernel_ms
-        self.info = {k: getattr(info, k) for k, _ in _HcInfo._fields_ if k != "pad"}
-        return self
+        return _take_hc_result(self, r)
 
     @property
     def oriented(self):
@@ -1121,6 +1134,66 @@ class HillClimbing:
     def set_tuning(ci, chunk_cells_max=0):
         """fbn_hc_set_tuning on a context: the most table cells per chunk of a batch; 0 = default."""
         lib.fbn_hc_set_tuning(ci._h, int(chunk_cells_max))
+
+
+class _ExactOptions(C.Structure):
+    _fields_ = [("penalty", C.c_double), ("max_parents", C.c_int32), ("pad", C.c_int32), ("max_family_cells", C.c_int64),
+                ("allowed", C.c_void_p), ("allowed_len", C.c_int64)]
+
+
+class _ExactInfo(C.Structure):
+    _fields_ = [("nvars", C.c_int32), ("tile_bits", C.c_int32), ("passes", C.c_int32), ("levels", C.c_int32),
+                ("families_scored", C.c_int64), ("batches", C.c_int64), ("lattice_bytes", C.c_int64),
+                ("score_kernel_ms", C.c_double), ("transform_kernel_ms", C.c_double), ("sink_kernel_ms", C.c_double),
+                ("score_wall_ms", C.c_double), ("upload_wall_ms", C.c_double), ("transform_wall_ms", C.c_double),
+                ("sink_wall_ms", C.c_double), ("trace_wall_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+class ExactSearch:
+    """Exact score-optimal structure learning for up to 26 variables: the globally best DAG under a
+    decomposable score by dynamic programming over variable subsets (fbn_exact_run; no reference counterpart).
+    score, max_parents, max_family_cells, allowed and learn(source, host) are HillClimbing's, and so are the
+    result fields (.parents, .score = the optimum R[V], .loglik, .node_scores, .node_logliks, .oriented;
+    .iterations is 0 and .trace empty); .exact_info holds the phase record (families scored, lattice bytes,
+    transform passes, kernel and wall ms per phase).  host=True runs the host twin (fbn_exact_run_host) on a
+    Dataset, bit-identical, without a device.  `.ci` is shared as HillClimbing.ci is."""
+
+    def __init__(self, score="bic", max_parents=None, max_family_cells=0, allowed=None, device=0):
+        self.score_name, self.device = score, device
+        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
+        self.ci = None
+
+    def _options(self, nsamples):
+        o = _ExactOptions()
+        o.penalty = hc_penalty(self.score_name, nsamples)
+        o.max_parents = -1 if self.max_parents is None else int(self.max_parents)
+        o.max_family_cells = int(self.max_family_cells)
+        a = None
+        if self.allowed is not None:
+            a = np.ascontiguousarray(np.asarray(self.allowed) != 0, np.uint8)
+            o.allowed, o.allowed_len = a.ctypes.data, a.size
+        return o, a
+
+    def learn(self, source, host=False):
+        r = C.c_void_p()
+        if host:
+            o, keep = self._options(source.num_instance)
+            lib.fbn_exact_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance, C.byref(o),
+                                   C.byref(r))
+        else:
+            ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
+            self.ci = ci
+            o, keep = self._options(ci.num_samples)
+            lib.fbn_exact_run(ci._h, C.byref(o), C.byref(r))
+        del keep
+        return _take_hc_result(self, r)
+
+    oriented = HillClimbing.oriented
+
+    @staticmethod
+    def set_tuning(ci, tile_bits=0):
+        """fbn_exact_set_tuning on a context: bits per pass of the subset-max transform; 0 = default."""
+        lib.fbn_exact_set_tuning(ci._h, int(tile_bits))
 
 
 def score_marginals(network, marginals, golden):

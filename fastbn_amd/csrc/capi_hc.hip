@@ -104,8 +104,9 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
     return FBN_OK;
 }
 
-// the device scorer: chunks of consecutive families whose tables fit the cap (a larger family alone)
-static int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms) {
+// the device scorer (hc_search.h: capi_exact.hip scores through it too): chunks of consecutive families
+// whose tables fit the cap (a larger family alone)
+int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms) {
     if (!B.nfam) return FBN_OK;
     FBN_HIP(hipSetDevice(c->device));
     if (int rc = HcTable(c)) return rc;

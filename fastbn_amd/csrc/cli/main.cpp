@@ -21,6 +21,9 @@
 // --max-parents K); prints the arc count, the score and the iterations, and with -f1 given the SHD against
 // that network through -a 0's comparison; --out FILE writes the DAG, one line per node: node, number of
 // parents, parents ascending.  --device -1 runs the host twin (same result, bit for bit).
+// -a 17, this build's own: exact score-optimal structure learning on -a 14's inputs, flags and output shape
+// (arcs, score, SHD against -f1, --out): the globally best DAG by dynamic programming over variable subsets;
+// a dataset of more than 26 variables is refused with the limit's message.
 // -a 15, this build's own: exact posterior sampling on -a 12's inputs: -q draws per case from P(x | e) under
 // --seed; prints the case count, the average log P(e) and the kernel time; --out FILE writes the drawn rows
 // as LIBSVM, the -q rows of a case one after the other (label = the value of variable 0).
@@ -65,7 +68,7 @@ int main(int argc, char **argv) {
         if (a == "--max-parents" && i + 1 < argc) { max_parents = atoi(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
                          "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik] [--max-parents K] [--out FILE] [--prefix DIR]"
@@ -454,10 +457,13 @@ int main(int argc, char **argv) {
         }
         fbn_em_destroy(em);
         fbn_network_destroy(net);
-    } else if (algorithm == 14) {
+    } else if (algorithm == 14 || algorithm == 17) {
         // score-based structure learning: no counterpart in the reference (its structure learner is PC-stable)
+        const bool exact = algorithm == 17;
         std::cout << "===============================" << std::endl
-                  << "Algorithm: hill climbing (HC) for score-based structure learning, #threads = " << num_threads << std::endl
+                  << (exact ? "Algorithm: exact search (subset-lattice DP) for score-optimal structure learning, #threads = "
+                            : "Algorithm: hill climbing (HC) for score-based structure learning, #threads = ")
+                  << num_threads << std::endl
                   << "score = " << score_name << ", max parents = " << max_parents << std::endl
                   << "\tsample set: " << train_set_file << std::endl;
         if (ref_given) std::cout << "\treference BN: " << ref_net_file << std::endl;
@@ -480,13 +486,18 @@ int main(int argc, char **argv) {
         if (fbn_hc_penalty(score_name.c_str(), ns, &opt.penalty)) return die();
         opt.max_parents = max_parents;
         opt.max_iter = -1;
+        fbn_exact_options xopt{};
+        xopt.penalty = opt.penalty;
+        xopt.max_parents = max_parents;
         fbn_hc_result *res = nullptr;
         fbn_ci_ctx *ctx = nullptr;
         if (device < 0) {
-            if (fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res)) return die();
+            if (exact ? fbn_exact_run_host(n, dims.data(), cols.data(), ns, &xopt, &res)
+                      : fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res))
+                return die();
         } else {
             if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
-            if (fbn_hc_run(ctx, &opt, &res)) return die();
+            if (exact ? fbn_exact_run(ctx, &xopt, &res) : fbn_hc_run(ctx, &opt, &res)) return die();
         }
         fbn_hc_info info;
         fbn_hc_result_info(res, &info);
@@ -495,9 +506,19 @@ int main(int argc, char **argv) {
         char buf[160];
         std::cout << "variables = " << n << ", samples = " << ns << std::endl << "arcs = " << info.narcs << std::endl;
         snprintf(buf, sizeof buf, "score = %.17g, log-likelihood = %.17g", info.score, info.loglik);
-        std::cout << buf << std::endl << "iterations = " << info.iterations << std::endl;
-        std::cout << "hc: " << info.families_scored << " families scored in " << info.batches << " batches, device kernel "
-                  << info.kernel_ms * 1e-3 << " s, search " << info.wall_ms * 1e-3 << " s" << std::endl;
+        std::cout << buf << std::endl;
+        if (exact) {
+            fbn_exact_info x;
+            fbn_exact_result_info(res, &x);
+            std::cout << "exact: " << x.families_scored << " families scored in " << x.batches << " batches, " << x.lattice_bytes
+                      << " lattice bytes, " << x.passes << " transform passes; device kernel: scores " << x.score_kernel_ms * 1e-3
+                      << " s, transform " << x.transform_kernel_ms * 1e-3 << " s, sinks " << x.sink_kernel_ms * 1e-3 << " s; search "
+                      << x.wall_ms * 1e-3 << " s" << std::endl;
+        } else {
+            std::cout << "iterations = " << info.iterations << std::endl;
+            std::cout << "hc: " << info.families_scored << " families scored in " << info.batches << " batches, device kernel "
+                      << info.kernel_ms * 1e-3 << " s, search " << info.wall_ms * 1e-3 << " s" << std::endl;
+        }
         if (ref_given) {
             std::vector<int32_t> tri;
             for (int v = 0; v < n; ++v)
@@ -622,7 +643,7 @@ int main(int argc, char **argv) {
         std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
                   << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15 and 16)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16 and 17)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

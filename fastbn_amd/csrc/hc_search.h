@@ -38,11 +38,14 @@ int HcCheckSamples(int64_t nsamples);
 
 // the host scorer over a host column store; L = the table of fbn_hc_fill_table(nsamples)
 HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const double *L);
+// the device scorer over a CI context's resident column store (capi_hc.hip)
+int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms);
 
 }  // namespace fbn
 
 struct fbn_hc_result {
     fbn_hc_info info{};
+    fbn_exact_info exact{};  // exact_host.cpp's phase record; nvars == 0 in a hill-climbing result
     std::vector<int32_t> parent_off, parents, ops;
     std::vector<double> node_score, node_loglik, delta;
 };

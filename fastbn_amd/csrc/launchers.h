@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, gibbs.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, gibbs.hip, exact_dp.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -139,5 +139,25 @@ struct HcScoreArgs {
     long long nfam;
 };
 extern "C" hipError_t fbn_hc_score_launch(const HcScoreArgs *a, hipStream_t stream);
+// The lattice kernels of the exact learner (exact_dp.hip; the pass geometry is exact_dp.h's ExactPass).
+// fbn_exact_pass_launch: one pass of the subset-max transform over all nvars lattices of 2^M entries
+// (val fp64, arg uint32, variable-major), in place; init_arg != 0: the args are not read but start as the
+// entries' own indices (the first pass).  fbn_exact_sink_launch: level `level` of the sink recursion over
+// the subsets of that popcount (level 0 writes R[0] = 0).
+struct ExactPassArgs {
+    double *val;
+    uint32_t *arg;
+    int nvars, M;
+    int gpos, hb, lo, s0, G;  // ExactPass
+    int init_arg;
+};
+extern "C" hipError_t fbn_exact_pass_launch(const ExactPassArgs *a, hipStream_t stream);
+struct ExactSinkArgs {
+    const double *bps;
+    double *R;
+    uint8_t *sink;
+    int nvars, level;
+};
+extern "C" hipError_t fbn_exact_sink_launch(const ExactSinkArgs *a, hipStream_t stream);
 
 #endif

@@ -1147,6 +1147,56 @@ int fbn_hc_result_node_scores(const fbn_hc_result *r, double *score, double *log
 int fbn_hc_result_trace(const fbn_hc_result *r, int32_t *ops, double *delta);
 int fbn_hc_result_destroy(fbn_hc_result *r);
 
+/* ------------------------------------------------------------------ exact score-optimal structure learning
+ * The globally best DAG under the same decomposable scores, by dynamic programming over variable subsets
+ * (Silander & Myllymaki 2006) (-a 17).  The reference has no score-based learner at all, so there is no
+ * reference output to match: the device path is held bit for bit to a host twin (fbn_exact_run_host).
+ *
+ * n variables, V the full set.  For a variable v and S within V \ {v}, c_v(S) is S with bit v squeezed out,
+ * an (n - 1)-bit index.  S is a candidate parent set of v when |S| <= max_parents, its family table has at
+ * most max_family_cells cells and allowed[x][v] holds for every x in S; the empty set always is one.
+ *   ls_v[S]  = fbn_score_families' score of (v, S) for candidates, -inf otherwise
+ *   bps_v[S] = max over T within S of ls_v[T], arg_v[S] = c_v of the maximising T
+ *   R[{}] = 0,  R[W] = max over v in W of R[W \ v] + bps_v[c_v(W \ v)],  sink[W] = that v;  R[V] is the optimum.
+ * Ties are part of the definition: the subset maximum is n - 1 sweeps, bit b = 0 .. n - 2 ascending, and in
+ * sweep b an index with bit b set takes its partner's value and arg only if the partner's is strictly greater;
+ * the sink maximum keeps the lowest v among equals.  The DAG is read off from sink[V] downwards.
+ *
+ * Limits: at most 26 variables; device state 12 n 2^(n-1) + 9 2^n bytes (about 11 GB at n = 26), checked
+ * against the free device memory before anything is allocated.  Past either: FBN_ERR_LIMIT, the message
+ * carrying the byte count.  One variable gives the empty DAG. */
+typedef struct fbn_exact_options {
+    double penalty;            /* >= 0 (fbn_hc_penalty); negative or NaN: FBN_ERR_ARG */
+    int32_t max_parents;       /* most parents of a node; < 0: no limit */
+    int32_t pad;
+    int64_t max_family_cells;  /* <= 0 or above FBN_PARAM_MAX_CELLS: FBN_PARAM_MAX_CELLS */
+    const uint8_t *allowed;    /* [nvars][nvars]: allowed[x * nvars + y] != 0 admits the arc x -> y; NULL: every arc */
+    int64_t allowed_len;       /* nvars * nvars when allowed != NULL, else FBN_ERR_ARG */
+} fbn_exact_options;
+
+typedef struct fbn_exact_info {
+    int32_t nvars, tile_bits;  /* tile_bits: bits swept per pass of the subset-max transform (0 on the host twin) */
+    int32_t passes, levels;    /* transform passes over all lattices; sink launches (n + 1: level 0 writes R[{}]) */
+    int64_t families_scored;   /* candidate families, plus the n chosen ones scored once more for the result */
+    int64_t batches;           /* scorer calls */
+    int64_t lattice_bytes;     /* 12 n 2^(n-1) + 9 2^n */
+    double score_kernel_ms, transform_kernel_ms, sink_kernel_ms; /* device time per phase (0 on the host twin) */
+    double score_wall_ms, upload_wall_ms, transform_wall_ms, sink_wall_ms, trace_wall_ms, wall_ms;
+} fbn_exact_info;
+
+/* The optimum over the context's resident column store.  The result is a hill-climbing result: parents
+ * ascending, node scores and log-likelihoods of the chosen families (scored in one last batch), score = R[V],
+ * loglik = the node log-likelihoods summed in variable order, iterations = 0 and an empty trace. */
+int fbn_exact_run(fbn_ci_ctx *c, const fbn_exact_options *options, fbn_hc_result **out);
+/* The same four phases in plain loops over the host scorer: the host twin.  No device. */
+int fbn_exact_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                       const fbn_exact_options *options, fbn_hc_result **out);
+/* The phase record of a result of the two entries above (FBN_ERR_ARG for a hill-climbing result). */
+int fbn_exact_result_info(const fbn_hc_result *r, fbn_exact_info *info);
+/* tile_bits = bits per transform pass, 1 .. 13; 0 = default.  Any value gives the same result bit for bit: a
+ * tuning/testing entry, so tests reach several passes and a ragged last pass at small sizes. */
+int fbn_exact_set_tuning(fbn_ci_ctx *c, int32_t tile_bits);
+
 #ifdef __cplusplus
 }
 #endif
