@@ -33,8 +33,9 @@ reference's names and argument meaning:
   Monte Carlo, for networks whose cliques no junction forest fits and evidence that starves the importance
   samplers; the chains' last states are approximate draws from P(x | e) (no reference counterpart)
 * ``HillClimbing(score, max_parents, allowed, start).learn(source)`` -- score-based structure learning: greedy
-  hill climbing under BIC / AIC / log-likelihood, family scores batched on the device and bit-identical to
-  a host twin (no reference counterpart); ``family_scores(ci, families, penalty)`` scores arbitrary families
+  hill climbing under BIC / AIC / log-likelihood or a Bayesian Dirichlet score ("bde", ("bde", iss), "k2"),
+  family scores batched on the device and bit-identical to a host twin (no reference counterpart);
+  ``family_scores(ci, families, penalty, score)`` scores arbitrary families
 * ``ExactSearch(score, max_parents, allowed).learn(source)`` -- the globally best DAG under the same scores for
   up to 26 variables, by dynamic programming over variable subsets on the device (no reference counterpart)
 

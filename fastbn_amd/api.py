@@ -198,6 +198,15 @@ _SIGS = {
     "fbn_exact_run_host": [C.c_int, _vp, _vp, _i64, _vp, _pp],
     "fbn_exact_result_info": [_vp, _vp],
     "fbn_exact_set_tuning": [_vp, _i32],
+    "fbn_score_families_bd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "fbn_score_families_bd_host": [C.c_int, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "fbn_hc_run_bd": [_vp, _vp, _vp, _pp],
+    "fbn_hc_run_bd_host": [C.c_int, _vp, _vp, _i64, _vp, _vp, _pp],
+    "fbn_exact_run_bd": [_vp, _vp, _vp, _pp],
+    "fbn_exact_run_bd_host": [C.c_int, _vp, _vp, _i64, _vp, _vp, _pp],
+    "fbn_bd_set_tuning": [_vp, _i32],
+    "fbn_bd_lgamma_diff": [_i64, _dbl, _vp, _vp],
+    "fbn_bd_score_table_host": [_vp, _i32, _i32, _vp, _vp, _vp],
 }
 
 
@@ -995,8 +1004,42 @@ class ParameterLearning:
         return self.ci.last_kernel_ms()
 
 
+class _BdScore(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("iss", C.c_double)]
+
+
+def _bd_score(score):
+    """The fbn_bd_score record of "bde" (iss = 1), "k2" or ("bde", iss); None for every other score."""
+    name, iss = score if isinstance(score, tuple) and len(score) == 2 else (score, 1.0)
+    if name not in ("bde", "k2"):
+        return None
+    if name == "k2" and isinstance(score, tuple):
+        raise FastBNError("k2 takes no equivalent sample size: score=\"k2\"")
+    return _BdScore(0 if name == "bde" else 1, 0, float(iss))
+
+
+def _bd_lgamma_diff(n, a):
+    """fbn_bd_lgamma_diff, a testing entry: (D(n, a) = lnGamma(a + n) - lnGamma(a) as the BD scores evaluate
+    it, the count from which it takes the Stirling form).  Host only."""
+    d, t = C.c_double(), C.c_int32()
+    lib.fbn_bd_lgamma_diff(int(n), float(a), C.byref(d), C.byref(t))
+    return d.value, t.value
+
+
+def _bd_score_table(table, score):
+    """fbn_bd_score_table_host, a testing entry: the twin's (loglik, score) of one r x q table of counts,
+    which unlike a dataset's may be all zeros.  Host only."""
+    tab = np.ascontiguousarray(table, np.uint32)
+    ll, sc = C.c_double(), C.c_double()
+    lib.fbn_bd_score_table_host(_p(tab), tab.shape[0], tab.shape[1], C.byref(_bd_score(score)), C.byref(ll), C.byref(sc))
+    return ll.value, sc.value
+
+
 def hc_penalty(score, nsamples):
-    """fbn_hc_penalty: the penalty of a named score ("bic", "aic", "loglik"), or a number as it is."""
+    """fbn_hc_penalty: the penalty of a named score ("bic", "aic", "loglik"), or a number as it is; 0 under
+    a Bayesian Dirichlet score ("bde", "k2", ("bde", iss)), which has no penalty term."""
+    if _bd_score(score) is not None:
+        return 0.0
     if isinstance(score, str):
         p = C.c_double()
         lib.fbn_hc_penalty(score.encode(), int(nsamples), C.byref(p))
@@ -1020,14 +1063,25 @@ def _csr_families(families):
     return off, cols
 
 
-def family_scores(source, families, penalty=0.0):
+def family_scores(source, families, penalty=0.0, score=None):
     """fbn_score_families: (loglik, score) float64 arrays of the families [(child, parent, ...), ...] from
     the column store resident in `source` (an IndependenceTest: on the device), or, for a Dataset,
-    fbn_score_families_host: the host twin, bit-identical, no device."""
+    fbn_score_families_host: the host twin, bit-identical, no device.  score = "bde" | "k2" | ("bde", iss):
+    the Bayesian Dirichlet score instead of loglik - penalty (fbn_score_families_bd and its twin)."""
     off, cols = _csr_families(families)
     n = len(families)
     ll, sc = np.zeros(max(n, 1)), np.zeros(max(n, 1))
-    if isinstance(source, IndependenceTest):
+    bd = None
+    if score is not None:
+        bd = _bd_score(score)
+        if bd is None:
+            raise FastBNError(f"unknown Bayesian Dirichlet score {score!r} (bde, k2, (bde, iss))")
+    if bd is not None and isinstance(source, IndependenceTest):
+        lib.fbn_score_families_bd(source._h, C.byref(bd), n, _p(off), _p(cols), _p(ll), _p(sc))
+    elif bd is not None:
+        lib.fbn_score_families_bd_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
+                                       C.byref(bd), n, _p(off), _p(cols), _p(ll), _p(sc))
+    elif isinstance(source, IndependenceTest):
         lib.fbn_score_families(source._h, float(penalty), n, _p(off), _p(cols), _p(ll), _p(sc))
     else:
         lib.fbn_score_families_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
@@ -1078,7 +1132,8 @@ def _take_hc_result(self, r):
 class HillClimbing:
     """Score-based structure learning: greedy hill climbing over arc additions, deletions and reversals
     (fbn_hc_run; no reference counterpart).  score: "bic" | "aic" | "loglik" or an explicit non-negative
-    penalty per free parameter.  allowed: [n][n] mask, allowed[x][y] lets the search add x -> y; start: a DAG
+    penalty per free parameter, or a Bayesian Dirichlet score "bde" (BDeu, iss = 1) | ("bde", iss) | "k2"
+    (fbn_hc_run_bd).  allowed: [n][n] mask, allowed[x][y] lets the search add x -> y; start: a DAG
     as parent lists.  learn(source): a Dataset (uploaded here), or an IndependenceTest, whose context is
     shared (`.ci`, as PCStable.ci: ParameterLearning(hc.ci) learns from the same upload); host=True runs
     the host twin (fbn_hc_run_host) on a Dataset, without a device.  Results: .parents (ascending parent
@@ -1113,15 +1168,23 @@ class HillClimbing:
 
     def learn(self, source, host=False):
         r = C.c_void_p()
+        bd = _bd_score(self.score_name)
         if host:
             o, keep = self._options(source.num_vars, source.num_instance)
-            lib.fbn_hc_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance, C.byref(o),
-                                C.byref(r))
+            if bd is not None:
+                lib.fbn_hc_run_bd_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
+                                       C.byref(o), C.byref(bd), C.byref(r))
+            else:
+                lib.fbn_hc_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
+                                    C.byref(o), C.byref(r))
         else:
             ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
             self.ci = ci
             o, keep = self._options(len(ci.dims), ci.num_samples)
-            lib.fbn_hc_run(ci._h, C.byref(o), C.byref(r))
+            if bd is not None:
+                lib.fbn_hc_run_bd(ci._h, C.byref(o), C.byref(bd), C.byref(r))
+            else:
+                lib.fbn_hc_run(ci._h, C.byref(o), C.byref(r))
         del keep
         return _take_hc_result(self, r)
 
@@ -1134,6 +1197,12 @@ class HillClimbing:
     def set_tuning(ci, chunk_cells_max=0):
         """fbn_hc_set_tuning on a context: the most table cells per chunk of a batch; 0 = default."""
         lib.fbn_hc_set_tuning(ci._h, int(chunk_cells_max))
+
+    @staticmethod
+    def set_bd_tuning(ci, pack=1):
+        """fbn_bd_set_tuning on a context: 1 = the BD reduction packs narrow families into one wave, 0 = one
+        wave per family; the same bits either way."""
+        lib.fbn_bd_set_tuning(ci._h, int(pack))
 
 
 class _ExactOptions(C.Structure):
@@ -1176,15 +1245,23 @@ class ExactSearch:
 
     def learn(self, source, host=False):
         r = C.c_void_p()
+        bd = _bd_score(self.score_name)
         if host:
             o, keep = self._options(source.num_instance)
-            lib.fbn_exact_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance, C.byref(o),
-                                   C.byref(r))
+            if bd is not None:
+                lib.fbn_exact_run_bd_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
+                                          C.byref(o), C.byref(bd), C.byref(r))
+            else:
+                lib.fbn_exact_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
+                                       C.byref(o), C.byref(r))
         else:
             ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
             self.ci = ci
             o, keep = self._options(ci.num_samples)
-            lib.fbn_exact_run(ci._h, C.byref(o), C.byref(r))
+            if bd is not None:
+                lib.fbn_exact_run_bd(ci._h, C.byref(o), C.byref(bd), C.byref(r))
+            else:
+                lib.fbn_exact_run(ci._h, C.byref(o), C.byref(r))
         del keep
         return _take_hc_result(self, r)
 

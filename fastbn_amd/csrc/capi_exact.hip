@@ -146,20 +146,34 @@ int fbn_exact_set_tuning(fbn_ci_ctx *c, int32_t tile_bits) {
     return FBN_OK;
 }
 
-int fbn_exact_run(fbn_ci_ctx *c, const fbn_exact_options *options, fbn_hc_result **out) {
+}  // extern "C"
+
+// fbn_exact_run (bd == nullptr; *bd outlives the run) and fbn_exact_run_bd
+static int ExactRun(fbn_ci_ctx *c, const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
     if (!c || !options || !out) return SetError(FBN_ERR_ARG, "null pointer");
     if (int rc = fbn::ExactCheck(c->nvars, c->dims.data(), *options)) return rc;
     if (int rc = fbn::HcCheckSamples(c->N)) return rc;
     FBN_HIP(hipSetDevice(c->device));
     auto r = std::unique_ptr<fbn_hc_result>(new (std::nothrow) fbn_hc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    fbn::HcScorer scorer = [c](const fbn::HcBatch &B, double *loglik, double *score, double *kernel_ms) {
-        return fbn::HcDeviceScore(c, B, loglik, score, kernel_ms);
+    fbn::HcScorer scorer = [c, bd](const fbn::HcBatch &B, double *loglik, double *score, double *kernel_ms) {
+        return fbn::HcDeviceScore(c, B, loglik, score, kernel_ms, bd);
     };
     if (int rc = fbn::ExactRunDevice(c, *options, scorer, r.get())) return rc;
     c->last_ms = (float)(r->exact.score_kernel_ms + r->exact.transform_kernel_ms + r->exact.sink_kernel_ms);
     *out = r.release();
     return FBN_OK;
+}
+
+extern "C" {
+
+int fbn_exact_run(fbn_ci_ctx *c, const fbn_exact_options *options, fbn_hc_result **out) {
+    return ExactRun(c, options, nullptr, out);
+}
+
+int fbn_exact_run_bd(fbn_ci_ctx *c, const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    return ExactRun(c, options, bd, out);
 }
 
 }  // extern "C"

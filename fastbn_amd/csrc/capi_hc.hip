@@ -6,6 +6,8 @@
 // arbitrary (child, parents) list) into the context's zeroed 32-bit tables and reduced by hc_score.hip to
 // two doubles per family; the tables never leave the device.  A batch whose tables exceed the chunk cap
 // (FBN_PARAM_MAX_CELLS, or fbn_hc_set_tuning's) is processed in chunks of consecutive families.
+// The _bd entries take the same route with hc_bd.hip as the reduction: the Bayesian Dirichlet scores
+// (hc_bd.h), the families' prior records in place of their penalty terms.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "capi_state.h"
+#include "hc_bd.h"
 #include "hc_score.h"
 #include "hc_search.h"
 #include "launchers.h"
@@ -36,9 +39,11 @@ static int HcTable(fbn_ci_ctx *c) {
     return FBN_OK;
 }
 
-// families [f0, f1) of B: descriptors up, tables zeroed, counted, reduced, 16 bytes per family back
+// families [f0, f1) of B: descriptors up, tables zeroed, counted, reduced, 16 bytes per family back.
+// bd == nullptr: hc_score.hip with the penalty terms; else hc_bd.hip with the families' prior records and
+// their index list by width class
 static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int64_t cells, double *loglik, double *score,
-                   double *kernel_ms) {
+                   double *kernel_ms, const fbn_bd_score *bd) {
     const int64_t nf = f1 - f0;
     int64_t slice = c->par_slice;
     if (slice <= 0) slice = fbn_param_default_slice(c->N, c->num_cu, nf);
@@ -49,6 +54,9 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
     const int64_t c0 = B.fam_off[f0], ncols = B.fam_off[f1] - c0;
     std::vector<FbnParamFamily> fam((size_t)nf);
     std::vector<int32_t> fstr((size_t)ncols);
+    std::vector<FbnBdPrior> prior;
+    std::vector<int32_t> qs, order;
+    if (bd) prior.resize((size_t)nf * 2), qs.resize((size_t)nf), order.resize((size_t)nf);
     size_t lds_ints = 1;
     int64_t tab_off = 0;
     for (int64_t f = f0; f < f1; ++f) {
@@ -62,14 +70,25 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
             str *= c->dims[fc[j]];
         }
         fstr[(size_t)o] = (int32_t)str;  // = cells / dims[child]: hc_score.hip reads it as q
+        if (bd) {
+            const int r = c->dims[fc[0]];
+            double a_cell, a_cfg;
+            fbn_bd_alphas(bd->kind, bd->iss, r, str, &a_cell, &a_cfg);
+            prior[(size_t)(2 * (f - f0))] = fbn_bd_prior(a_cell);
+            prior[(size_t)(2 * (f - f0) + 1)] = fbn_bd_prior(a_cfg);
+            qs[(size_t)(f - f0)] = (int32_t)str;
+        }
         tab_off += B.cells[f];
         if (B.cells[f] <= lds_max) lds_ints = std::max(lds_ints, fbn_param_lds_ints((int)B.cells[f]));
     }
     int rc;
     if ((rc = c->par_fam.ensure(fam.size() * sizeof(FbnParamFamily))) || (rc = c->par_col.ensure((size_t)ncols * 4)) ||
         (rc = c->par_str.ensure((size_t)ncols * 4)) || (rc = c->par_tab.ensure((size_t)cells * 4)) ||
-        (rc = c->hc_pen.ensure((size_t)nf * 8)) || (rc = c->hc_out.ensure((size_t)nf * 16)))
+        (rc = c->hc_pen.ensure((size_t)nf * (bd ? 2 * sizeof(FbnBdPrior) : 8))) || (rc = c->hc_out.ensure((size_t)nf * 16)) ||
+        (bd && (rc = c->hc_order.ensure((size_t)nf * 4))))
         return rc;
+    HcBdArgs ba{};
+    if (bd) fbn_hc_bd_bin(qs.data(), nf, c->bd_pack, order.data(), &ba);
     hipStream_t s = c->stream;
     CiSlot &S = c->slot[0];
     std::vector<double> out((size_t)nf * 2);
@@ -77,17 +96,30 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
     FBN_HIP(hipMemcpyAsync(c->par_fam.p, fam.data(), fam.size() * sizeof(FbnParamFamily), hipMemcpyHostToDevice, s));
     FBN_HIP(hipMemcpyAsync(c->par_col.p, B.fam_cols + c0, (size_t)ncols * 4, hipMemcpyHostToDevice, s));
     FBN_HIP(hipMemcpyAsync(c->par_str.p, fstr.data(), (size_t)ncols * 4, hipMemcpyHostToDevice, s));
-    FBN_HIP(hipMemcpyAsync(c->hc_pen.p, B.pen + f0, (size_t)nf * 8, hipMemcpyHostToDevice, s));
+    if (bd) {
+        FBN_HIP(hipMemcpyAsync(c->hc_pen.p, prior.data(), prior.size() * sizeof(FbnBdPrior), hipMemcpyHostToDevice, s));
+        FBN_HIP(hipMemcpyAsync(c->hc_order.p, order.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
+    } else {
+        FBN_HIP(hipMemcpyAsync(c->hc_pen.p, B.pen + f0, (size_t)nf * 8, hipMemcpyHostToDevice, s));
+    }
     if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
     FBN_HIP(hipMemsetAsync(c->par_tab.p, 0, (size_t)cells * 4, s));
     hipError_t e = fbn_param_launch(c->cols.as<uint8_t>(), c->N, c->par_fam.as<FbnParamFamily>(), nf, c->par_col.as<int32_t>(),
                                     c->par_str.as<int32_t>(), c->par_tab.as<uint32_t>(), slice, nslices, lds_max,
                                     lds_ints * 4, s);
     if (e != hipSuccess) return SetError(FBN_ERR_HIP, "family counts launch: %s", hipGetErrorString(e));
-    HcScoreArgs a{c->par_tab.as<uint32_t>(), c->par_fam.as<FbnParamFamily>(), c->par_str.as<int32_t>(),
-                  c->hc_pen.as<double>(), c->hc_L.as<double>(), c->hc_out.as<double>(), (long long)nf};
-    if ((e = fbn_hc_score_launch(&a, s)) != hipSuccess)
-        return SetError(FBN_ERR_HIP, "family score launch: %s", hipGetErrorString(e));
+    if (bd) {
+        ba.tab = c->par_tab.as<uint32_t>(), ba.fam = c->par_fam.as<FbnParamFamily>(), ba.fstr = c->par_str.as<int32_t>();
+        ba.prior = c->hc_pen.as<FbnBdPrior>(), ba.L = c->hc_L.as<double>(), ba.out = c->hc_out.as<double>();
+        ba.order = c->hc_order.as<int32_t>();
+        if ((e = fbn_hc_bd_launch(&ba, s)) != hipSuccess)
+            return SetError(FBN_ERR_HIP, "Bayesian Dirichlet score launch: %s", hipGetErrorString(e));
+    } else {
+        HcScoreArgs a{c->par_tab.as<uint32_t>(), c->par_fam.as<FbnParamFamily>(), c->par_str.as<int32_t>(),
+                      c->hc_pen.as<double>(), c->hc_L.as<double>(), c->hc_out.as<double>(), (long long)nf};
+        if ((e = fbn_hc_score_launch(&a, s)) != hipSuccess)
+            return SetError(FBN_ERR_HIP, "family score launch: %s", hipGetErrorString(e));
+    }
     if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
     FBN_HIP(hipMemcpyAsync(out.data(), c->hc_out.p, out.size() * 8, hipMemcpyDeviceToHost, s));
     FBN_HIP(hipStreamSynchronize(s));
@@ -106,7 +138,8 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
 
 // the device scorer (hc_search.h: capi_exact.hip scores through it too): chunks of consecutive families
 // whose tables fit the cap (a larger family alone)
-int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms) {
+int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms,
+                  const fbn_bd_score *bd) {
     if (!B.nfam) return FBN_OK;
     FBN_HIP(hipSetDevice(c->device));
     if (int rc = HcTable(c)) return rc;
@@ -114,7 +147,7 @@ int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score
     for (int64_t f0 = 0; f0 < B.nfam;) {
         int64_t f1 = f0 + 1, cells = B.cells[f0];
         while (f1 < B.nfam && cells + B.cells[f1] <= cap) cells += B.cells[f1++];
-        if (int rc = HcChunk(c, B, f0, f1, cells, loglik, score, kernel_ms)) return rc;
+        if (int rc = HcChunk(c, B, f0, f1, cells, loglik, score, kernel_ms, bd)) return rc;
         f0 = f1;
     }
     return FBN_OK;
@@ -131,30 +164,61 @@ int fbn_hc_set_tuning(fbn_ci_ctx *c, int64_t chunk_cells_max) {
     return FBN_OK;
 }
 
-int fbn_score_families(fbn_ci_ctx *c, double penalty, int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols,
-                       double *loglik, double *score) {
+}  // extern "C"
+
+// fbn_score_families (bd == nullptr) and fbn_score_families_bd
+static int ScoreFamilies(fbn_ci_ctx *c, double penalty, const fbn_bd_score *bd, int64_t nfam, const int64_t *fam_off,
+                         const int32_t *fam_cols, double *loglik, double *score) {
     if (!c) return SetError(FBN_ERR_ARG, "null pointer");
     // everything that can be refused is refused here, on the host, before any launch
     fbn::HcFamilies F;
     if (int rc = fbn::HcCheckFamilies(c->nvars, c->dims.data(), penalty, nfam, fam_off, fam_cols, &F)) return rc;
     if (int rc = fbn::HcCheckSamples(c->N)) return rc;
     double ms = 0.0;
-    const int rc = fbn::HcDeviceScore(c, F.batch(), loglik, score, &ms);
+    const int rc = fbn::HcDeviceScore(c, F.batch(), loglik, score, &ms, bd);
     c->last_ms = (float)ms;
     return rc;
 }
 
-int fbn_hc_run(fbn_ci_ctx *c, const fbn_hc_options *options, fbn_hc_result **out) {
+// fbn_hc_run (bd == nullptr; *bd outlives the search) and fbn_hc_run_bd
+static int HcRun(fbn_ci_ctx *c, const fbn_hc_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
     if (!c || !options || !out) return SetError(FBN_ERR_ARG, "null pointer");
     if (int rc = fbn::HcCheckSamples(c->N)) return rc;
     auto r = std::unique_ptr<fbn_hc_result>(new (std::nothrow) fbn_hc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    fbn::HcScorer scorer = [c](const fbn::HcBatch &B, double *loglik, double *score, double *kernel_ms) {
-        return fbn::HcDeviceScore(c, B, loglik, score, kernel_ms);
+    fbn::HcScorer scorer = [c, bd](const fbn::HcBatch &B, double *loglik, double *score, double *kernel_ms) {
+        return fbn::HcDeviceScore(c, B, loglik, score, kernel_ms, bd);
     };
     if (int rc = fbn::HcSearch(c->nvars, c->dims.data(), *options, scorer, r.get())) return rc;
     c->last_ms = (float)r->info.kernel_ms;
     *out = r.release();
+    return FBN_OK;
+}
+
+extern "C" {
+
+int fbn_score_families(fbn_ci_ctx *c, double penalty, int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols,
+                       double *loglik, double *score) {
+    return ScoreFamilies(c, penalty, nullptr, nfam, fam_off, fam_cols, loglik, score);
+}
+
+int fbn_score_families_bd(fbn_ci_ctx *c, const fbn_bd_score *bd, int64_t nfam, const int64_t *fam_off,
+                          const int32_t *fam_cols, double *loglik, double *score) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    return ScoreFamilies(c, 0.0, bd, nfam, fam_off, fam_cols, loglik, score);
+}
+
+int fbn_hc_run(fbn_ci_ctx *c, const fbn_hc_options *options, fbn_hc_result **out) { return HcRun(c, options, nullptr, out); }
+
+int fbn_hc_run_bd(fbn_ci_ctx *c, const fbn_hc_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    return HcRun(c, options, bd, out);
+}
+
+int fbn_bd_set_tuning(fbn_ci_ctx *c, int32_t pack) {
+    if (!c) return SetError(FBN_ERR_ARG, "null pointer");
+    if (pack != 0 && pack != 1) return SetError(FBN_ERR_ARG, "pack = %d is neither 0 nor 1", pack);
+    c->bd_pack = pack;
     return FBN_OK;
 }
 

@@ -191,7 +191,10 @@ struct fbn_ci_ctx {
     // score-based structure learning (capi_hc.hip, hc_score.hip): L[n] = n ln n for n <= N (built on the
     // host and uploaded by the first scoring call), the penalty terms and the two results per family of a
     // chunk, fbn_hc_set_tuning's chunk cap (0 = FBN_PARAM_MAX_CELLS)
-    DevBuf hc_L, hc_pen, hc_out;
+    // Bayesian Dirichlet scores (hc_bd.hip): hc_pen then holds the families' prior records, hc_order their
+    // index list by width class; bd_pack = fbn_bd_set_tuning's
+    DevBuf hc_L, hc_pen, hc_out, hc_order;
+    int bd_pack = 1;
     bool hc_table_ready = false;
     int64_t hc_chunk = 0;
     int exact_tile_bits = 0;  // fbn_exact_set_tuning (capi_exact.hip): bits per transform pass, 0 = default

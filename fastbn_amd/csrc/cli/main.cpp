@@ -17,8 +17,9 @@
 // --tol the relative stopping tolerance, pseudo-count 1; one line per iteration with the log-likelihood and
 // Q; --out FILE writes the learned CPTs as text, one line per node and parent configuration.
 // -a 14, this build's own too: score-based structure learning, greedy hill climbing over arc additions,
-// deletions and reversals from the empty graph on -f2's CSV (--score bic|aic|loglik, default bic;
-// --max-parents K); prints the arc count, the score and the iterations, and with -f1 given the SHD against
+// deletions and reversals from the empty graph on -f2's CSV (--score bic|aic|loglik|bde|k2, default bic;
+// --iss X: the equivalent sample size of bde, default 1, refused beside any other score; --max-parents K);
+// prints the arc count, the score and the iterations, and with -f1 given the SHD against
 // that network through -a 0's comparison; --out FILE writes the DAG, one line per node: node, number of
 // parents, parents ascending.  --device -1 runs the host twin (same result, bit for bit).
 // -a 17, this build's own: exact score-optimal structure learning on -a 14's inputs, flags and output shape
@@ -48,7 +49,8 @@ int main(int argc, char **argv) {
     unsigned long long seed = 0;
     std::string out_file, score_name = "bic";
     int max_parents = -1;
-    bool ref_given = false;
+    double iss = 1.0;
+    bool ref_given = false, iss_given = false;
     std::string net_file = "alarm/alarm.xml", ref_net_file = "alarm/alarm.bif",
                 train_set_file = "alarm/alarm_s5000.txt", test_set_file = "alarm/testing_alarm_1k_p20",
                 pt_file = "alarm/alarm_1k_pt", prefix = "../dataset/";
@@ -65,13 +67,14 @@ int main(int argc, char **argv) {
         if (a == "--eps" && i + 1 < argc) { eps = atof(argv[++i]); continue; }
         if (a == "--out" && i + 1 < argc) { out_file = argv[++i]; continue; }
         if (a == "--score" && i + 1 < argc) { score_name = argv[++i]; continue; }
+        if (a == "--iss" && i + 1 < argc) { iss = atof(argv[++i]); iss_given = true; continue; }
         if (a == "--max-parents" && i + 1 < argc) { max_parents = atoi(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
             std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
-                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik] [--max-parents K] [--out FILE] [--prefix DIR]"
+                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--out FILE] [--prefix DIR]"
                       << std::endl;
             return 0;
         case 'a': algorithm = atoi(argv[++i]); break;
@@ -483,7 +486,14 @@ int main(int argc, char **argv) {
         fbn_dataset_columns(ds, cols.data());
         fbn_dataset_destroy(ds);
         fbn_hc_options opt{};
-        if (fbn_hc_penalty(score_name.c_str(), ns, &opt.penalty)) return die();
+        // a Bayesian Dirichlet score (BDeu with --iss, K2) has no penalty term and goes through the _bd entries
+        const bool is_bd = score_name == "bde" || score_name == "k2";
+        if (iss_given && score_name != "bde") {
+            fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
+            return 1;
+        }
+        const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+        if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &opt.penalty)) return die();
         opt.max_parents = max_parents;
         opt.max_iter = -1;
         fbn_exact_options xopt{};
@@ -492,12 +502,16 @@ int main(int argc, char **argv) {
         fbn_hc_result *res = nullptr;
         fbn_ci_ctx *ctx = nullptr;
         if (device < 0) {
-            if (exact ? fbn_exact_run_host(n, dims.data(), cols.data(), ns, &xopt, &res)
-                      : fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res))
+            if (is_bd ? (exact ? fbn_exact_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, &bd, &res)
+                               : fbn_hc_run_bd_host(n, dims.data(), cols.data(), ns, &opt, &bd, &res))
+                      : (exact ? fbn_exact_run_host(n, dims.data(), cols.data(), ns, &xopt, &res)
+                               : fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res)))
                 return die();
         } else {
             if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
-            if (exact ? fbn_exact_run(ctx, &xopt, &res) : fbn_hc_run(ctx, &opt, &res)) return die();
+            if (is_bd ? (exact ? fbn_exact_run_bd(ctx, &xopt, &bd, &res) : fbn_hc_run_bd(ctx, &opt, &bd, &res))
+                      : (exact ? fbn_exact_run(ctx, &xopt, &res) : fbn_hc_run(ctx, &opt, &res)))
+                return die();
         }
         fbn_hc_info info;
         fbn_hc_result_info(res, &info);

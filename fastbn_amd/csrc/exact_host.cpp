@@ -227,8 +227,9 @@ using fbn::SetError;
 
 extern "C" {
 
-int fbn_exact_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
-                       const fbn_exact_options *options, fbn_hc_result **out) {
+// fbn_exact_run_host (bd == nullptr) and fbn_exact_run_bd_host
+static int ExactRunHostEntry(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                             const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
     if (!options || !out) return SetError(FBN_ERR_ARG, "null pointer");
     if (int rc = fbn::ExactCheck(nvars, dims, *options)) return rc;
     if (int rc = fbn::HcCheckSamples(nsamples)) return rc;
@@ -241,10 +242,21 @@ int fbn_exact_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int6
     fbn_hc_fill_table(L.data(), nsamples);
     auto r = std::unique_ptr<fbn_hc_result>(new (std::nothrow) fbn_hc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    if (int rc = fbn::ExactRunHost(nvars, dims, *options, fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data()), r.get()))
+    if (int rc = fbn::ExactRunHost(nvars, dims, *options, fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data(), bd), r.get()))
         return rc;
     *out = r.release();
     return FBN_OK;
+}
+
+int fbn_exact_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                       const fbn_exact_options *options, fbn_hc_result **out) {
+    return ExactRunHostEntry(nvars, dims, cols, nsamples, options, nullptr, out);
+}
+
+int fbn_exact_run_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                          const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    return ExactRunHostEntry(nvars, dims, cols, nsamples, options, bd, out);
 }
 
 int fbn_exact_result_info(const fbn_hc_result *r, fbn_exact_info *info) {

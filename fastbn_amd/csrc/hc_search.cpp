@@ -27,6 +27,7 @@
 #include <string>
 
 #include "fbn_internal.h"
+#include "hc_bd.h"
 #include "hc_score.h"
 
 namespace fbn {
@@ -94,6 +95,17 @@ int HcCheckFamilies(int nvars, const int32_t *dims, double penalty, int64_t nfam
     return FBN_OK;
 }
 
+int BdCheck(const fbn_bd_score *bd) {
+    if (!bd) return SetError(FBN_ERR_ARG, "null pointer");
+    if (bd->kind != FBN_SCORE_BDE && bd->kind != FBN_SCORE_K2)
+        return SetError(FBN_ERR_ARG, "score kind %d is neither FBN_SCORE_BDE nor FBN_SCORE_K2", bd->kind);
+    if (bd->kind == FBN_SCORE_K2) return FBN_OK;
+    if (!(bd->iss > 0.0) || std::isinf(bd->iss)) return SetError(FBN_ERR_ARG, "iss = %g is not a positive number", bd->iss);
+    if (bd->iss < kBdIssMin || bd->iss > kBdIssMax)
+        return SetError(FBN_ERR_LIMIT, "iss = %g outside %g .. %g", bd->iss, kBdIssMin, kBdIssMax);
+    return FBN_OK;
+}
+
 static int CheckColumns(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples) {
     if (!cols) return SetError(FBN_ERR_ARG, "null column store");
     for (int v = 0; v < nvars; ++v) {
@@ -105,8 +117,11 @@ static int CheckColumns(int nvars, const int32_t *dims, const uint8_t *cols, int
     return FBN_OK;
 }
 
-HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const double *L) {
+HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const double *L,
+                      const fbn_bd_score *bd) {
     (void)nvars;
+    const bool is_bd = bd != nullptr;
+    const fbn_bd_score S = is_bd ? *bd : fbn_bd_score{};
     return [=](const HcBatch &B, double *loglik, double *score, double *kernel_ms) -> int {
         (void)kernel_ms;
         std::vector<uint32_t> tab;
@@ -129,7 +144,13 @@ HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64
             }
             for (int64_t s = 0; s < nsamples; ++s) ++tab[(size_t)key[(size_t)s]];
             double ll, sc;
-            fbn_hc_family_host(tab.data(), r, q, L, B.pen[f], &ll, &sc);
+            if (is_bd) {
+                double a_cell, a_cfg;
+                fbn_bd_alphas(S.kind, S.iss, r, q, &a_cell, &a_cfg);
+                fbn_bd_family_host(tab.data(), r, q, L, a_cell, a_cfg, &ll, &sc);
+            } else {
+                fbn_hc_family_host(tab.data(), r, q, L, B.pen[f], &ll, &sc);
+            }
             if (loglik) loglik[f] = ll;
             if (score) score[f] = sc;
         }
@@ -385,9 +406,10 @@ int fbn_hc_penalty(const char *score, int64_t nsamples, double *penalty) {
     return FBN_OK;
 }
 
-int fbn_score_families_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, double penalty,
-                            int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols, double *loglik,
-                            double *score) {
+// fbn_score_families_host (bd == nullptr) and fbn_score_families_bd_host
+static int ScoreFamiliesHost(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, double penalty,
+                             const fbn_bd_score *bd, int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols,
+                             double *loglik, double *score) {
     fbn::HcFamilies F;
     if (int rc = fbn::HcCheckFamilies(nvars, dims, penalty, nfam, fam_off, fam_cols, &F)) return rc;
     if (int rc = fbn::HcCheckSamples(nsamples)) return rc;
@@ -396,11 +418,52 @@ int fbn_score_families_host(int nvars, const int32_t *dims, const uint8_t *cols,
     std::vector<double> L((size_t)nsamples + 1);
     fbn_hc_fill_table(L.data(), nsamples);
     double ms = 0.0;
-    return fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data())(F.batch(), loglik, score, &ms);
+    return fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data(), bd)(F.batch(), loglik, score, &ms);
 }
 
-int fbn_hc_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
-                    const fbn_hc_options *options, fbn_hc_result **out) {
+int fbn_score_families_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, double penalty,
+                            int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols, double *loglik,
+                            double *score) {
+    return ScoreFamiliesHost(nvars, dims, cols, nsamples, penalty, nullptr, nfam, fam_off, fam_cols, loglik, score);
+}
+
+int fbn_score_families_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                               const fbn_bd_score *bd, int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols,
+                               double *loglik, double *score) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    return ScoreFamiliesHost(nvars, dims, cols, nsamples, 0.0, bd, nfam, fam_off, fam_cols, loglik, score);
+}
+
+int fbn_bd_lgamma_diff(int64_t n, double a, double *d, int32_t *threshold) {
+    if (threshold) *threshold = kBdDirect;
+    if (!d) return FBN_OK;
+    if (n < 0 || n > 0xffffffffll || !(a >= kBdIssMin / 4294967296.0) || !(a <= kBdIssMax))
+        return SetError(FBN_ERR_ARG, "D(%lld, %g): arguments out of range", (long long)n, a);
+    *d = n ? fbn_bd_term((uint32_t)n, fbn_bd_prior(a)) : 0.0;
+    return FBN_OK;
+}
+
+int fbn_bd_score_table_host(const uint32_t *tab, int32_t r, int32_t q, const fbn_bd_score *bd, double *loglik,
+                            double *score) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    if (!tab || !loglik || !score) return SetError(FBN_ERR_ARG, "null pointer");
+    if (r < 1 || r > 256 || q < 1 || (int64_t)r * q > 0x7fffffffll)
+        return SetError(FBN_ERR_ARG, "table of %d x %d counters", r, q);
+    int64_t total = 0;
+    for (int64_t i = 0; i < (int64_t)r * q; ++i) total += tab[i];
+    if (total > kHcMaxSamples)
+        return SetError(FBN_ERR_LIMIT, "table: %lld samples (at most 2^24)", (long long)total);
+    std::vector<double> L((size_t)total + 1);
+    fbn_hc_fill_table(L.data(), total);
+    double a_cell, a_cfg;
+    fbn_bd_alphas(bd->kind, bd->iss, r, q, &a_cell, &a_cfg);
+    fbn_bd_family_host(tab, r, q, L.data(), a_cell, a_cfg, loglik, score);
+    return FBN_OK;
+}
+
+// fbn_hc_run_host (bd == nullptr) and fbn_hc_run_bd_host
+static int HcRunHost(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const fbn_hc_options *options,
+                     const fbn_bd_score *bd, fbn_hc_result **out) {
     if (!options || !out) return SetError(FBN_ERR_ARG, "null pointer");
     if (int rc = fbn::CheckDims(nvars, dims)) return rc;
     if (int rc = fbn::HcCheckSamples(nsamples)) return rc;
@@ -409,10 +472,21 @@ int fbn_hc_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t
     fbn_hc_fill_table(L.data(), nsamples);
     auto r = std::unique_ptr<fbn_hc_result>(new (std::nothrow) fbn_hc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    if (int rc = fbn::HcSearch(nvars, dims, *options, fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data()), r.get()))
+    if (int rc = fbn::HcSearch(nvars, dims, *options, fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data(), bd), r.get()))
         return rc;
     *out = r.release();
     return FBN_OK;
+}
+
+int fbn_hc_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                    const fbn_hc_options *options, fbn_hc_result **out) {
+    return HcRunHost(nvars, dims, cols, nsamples, options, nullptr, out);
+}
+
+int fbn_hc_run_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                       const fbn_hc_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
+    if (int rc = fbn::BdCheck(bd)) return rc;
+    return HcRunHost(nvars, dims, cols, nsamples, options, bd, out);
 }
 
 int fbn_hc_result_info(const fbn_hc_result *r, fbn_hc_info *info) {

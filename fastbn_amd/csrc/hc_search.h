@@ -36,10 +36,16 @@ int HcCheckFamilies(int nvars, const int32_t *dims, double penalty, int64_t nfam
                     const int32_t *fam_cols, HcFamilies *out);
 int HcCheckSamples(int64_t nsamples);
 
-// the host scorer over a host column store; L = the table of fbn_hc_fill_table(nsamples)
-HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const double *L);
-// the device scorer over a CI context's resident column store (capi_hc.hip)
-int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms);
+// a Bayesian Dirichlet score record: a known kind, iss within hc_bd.h's range (K2 ignores iss)
+int BdCheck(const fbn_bd_score *bd);
+
+// the host scorer over a host column store; L = the table of fbn_hc_fill_table(nsamples).  bd == nullptr:
+// score = loglik - pen[f] (hc_score.h); else the Bayesian Dirichlet score (hc_bd.h), pen[f] unread
+HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const double *L,
+                      const fbn_bd_score *bd = nullptr);
+// the device scorer over a CI context's resident column store (capi_hc.hip); bd as above
+int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms,
+                  const fbn_bd_score *bd = nullptr);
 
 }  // namespace fbn
 

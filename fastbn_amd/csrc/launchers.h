@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, gibbs.hip, exact_dp.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -139,6 +139,28 @@ struct HcScoreArgs {
     long long nfam;
 };
 extern "C" hipError_t fbn_hc_score_launch(const HcScoreArgs *a, hipStream_t stream);
+// The Bayesian Dirichlet reduction (hc_bd.hip) over the same tables: prior[2 f], prior[2 f + 1] = hc_bd.h's
+// records of family f's cell and configuration parameter -> out[2 f] = log-likelihood (hc_score.hip's
+// bits), out[2 f + 1] = the BD score.  Families are packed 64 / w to a wave by their width class (q <= w
+// = 1, 2, .., 32; class 6: one wave each): fbn_hc_bd_bin (host) fills order (to be uploaded by the caller)
+// and the class tables from the families' q; pack == 0 puts every family in class 6.
+struct FbnBdPrior;
+constexpr int kBdClasses = 7;
+struct HcBdArgs {
+    const uint32_t *tab;
+    const FbnParamFamily *fam;
+    const int32_t *fstr;
+    const FbnBdPrior *prior;
+    const double *L;
+    double *out;
+    const int32_t *order;                // [nfam] family indices, class by class
+    long long cls_count[kBdClasses + 1]; // families of class c
+    long long cls_first[kBdClasses + 1]; // its first entry of order
+    long long cls_block[kBdClasses + 1]; // its first workgroup; [kBdClasses] = the grid
+    long long nfam;
+};
+extern "C" void fbn_hc_bd_bin(const int32_t *q, long long nfam, int pack, int32_t *order, HcBdArgs *a);
+extern "C" hipError_t fbn_hc_bd_launch(const HcBdArgs *a, hipStream_t stream);
 // The lattice kernels of the exact learner (exact_dp.hip; the pass geometry is exact_dp.h's ExactPass).
 // fbn_exact_pass_launch: one pass of the subset-max transform over all nvars lattices of 2^M entries
 // (val fp64, arg uint32, variable-major), in place; init_arg != 0: the args are not read but start as the

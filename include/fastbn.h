@@ -1197,6 +1197,51 @@ int fbn_exact_result_info(const fbn_hc_result *r, fbn_exact_info *info);
  * tuning/testing entry, so tests reach several passes and a ragged last pass at small sizes. */
 int fbn_exact_set_tuning(fbn_ci_ctx *c, int32_t tile_bits);
 
+/* ------------------------------------------------------------------ Bayesian Dirichlet scores (BDeu, K2)
+ * The same learners under the Bayesian Dirichlet family score.  With D(n, a) = lnGamma(a + n) - lnGamma(a),
+ * a child of r states, q parent configurations (the full product of the parents' state counts):
+ *     score = sum_jk D(N_jk, a_cell) - sum_j D(N_j, a_cfg)
+ * FBN_SCORE_BDE (BDeu, equivalent sample size iss > 0):  a_cell = iss / (r q),  a_cfg = iss / q.
+ * FBN_SCORE_K2:                                          a_cell = 1,            a_cfg = r  (iss unread).
+ * D is evaluated by one header of this library (csrc/hc_bd.h) on the host and on the device: an own
+ * logarithm and + - * / only, one summation order, so as for the penalised scores the device path equals
+ * its host twin bit for bit and both searches walk one path.  loglik outputs keep their meaning and their
+ * bits.  The `penalty` of an options record is validated and otherwise unread by the _bd entries.
+ * iss <= 0, NaN or infinite: FBN_ERR_ARG; outside 1e-100 .. 1e100: FBN_ERR_LIMIT; an unknown kind: FBN_ERR_ARG. */
+#define FBN_SCORE_BDE 0
+#define FBN_SCORE_K2 1
+typedef struct fbn_bd_score {
+    int32_t kind;              /* FBN_SCORE_BDE or FBN_SCORE_K2 */
+    int32_t pad;
+    double iss;                /* BDeu's equivalent sample size */
+} fbn_bd_score;
+/* fbn_score_families / fbn_score_families_host under a Bayesian Dirichlet score */
+int fbn_score_families_bd(fbn_ci_ctx *c, const fbn_bd_score *bd, int64_t nfam, const int64_t *fam_off,
+                          const int32_t *fam_cols, double *loglik, double *score);
+int fbn_score_families_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                               const fbn_bd_score *bd, int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols,
+                               double *loglik, double *score);
+/* fbn_hc_run / fbn_hc_run_host under a Bayesian Dirichlet score */
+int fbn_hc_run_bd(fbn_ci_ctx *c, const fbn_hc_options *options, const fbn_bd_score *bd, fbn_hc_result **out);
+int fbn_hc_run_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                       const fbn_hc_options *options, const fbn_bd_score *bd, fbn_hc_result **out);
+/* fbn_exact_run / fbn_exact_run_host under a Bayesian Dirichlet score: ls_v[S] is the BD score of (v, S) */
+int fbn_exact_run_bd(fbn_ci_ctx *c, const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out);
+int fbn_exact_run_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                          const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out);
+/* pack = 1 (default): the device reduction packs 64 / w families with q <= w = 1, 2, .., 32 into one wave;
+ * pack = 0: one wave per family.  Either gives the same bits: a tuning/testing entry. */
+int fbn_bd_set_tuning(fbn_ci_ctx *c, int32_t pack);
+/* The two entries below are host-only testing entries: they reach the scores' arithmetic where no dataset can
+ * (one D, a table without a sample); the Python package binds them under private names.
+ * *d = D(n, a) as the scores evaluate it (0 <= n < 2^32; n = 0 gives 0), *threshold = the count from which
+ * D takes the Stirling form when a < 16.  Either pointer may be NULL. */
+int fbn_bd_lgamma_diff(int64_t n, double a, double *d, int32_t *threshold);
+/* The twin's log-likelihood and score of one counted table tab[k * q + j] of a child with r <= 256 states and
+ * q parent configurations; the counters sum to at most 2^24 and may all be zero (both outputs +0.0). */
+int fbn_bd_score_table_host(const uint32_t *tab, int32_t r, int32_t q, const fbn_bd_score *bd, double *loglik,
+                            double *score);
+
 #ifdef __cplusplus
 }
 #endif
