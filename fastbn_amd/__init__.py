@@ -38,6 +38,8 @@ reference's names and argument meaning:
   ``family_scores(ci, families, penalty, score)`` scores arbitrary families
 * ``ExactSearch(score, max_parents, allowed).learn(source)`` -- the globally best DAG under the same scores for
   up to 26 variables, by dynamic programming over variable subsets on the device (no reference counterpart)
+* ``ArcPosterior(score, max_parents, allowed, prior).learn(source)`` -- exact arc posteriors P(u -> v | data) by
+  Bayesian model averaging over all DAGs, the same lattices in the log-sum-exp semiring (no reference counterpart)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -63,6 +65,7 @@ from .api import (  # noqa: F401
     GibbsSampling,
     HillClimbing,
     ExactSearch,
+    ArcPosterior,
     family_scores,
     hc_penalty,
     hc_table_bytes,
@@ -80,6 +83,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "ArcPosterior", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -207,6 +207,16 @@ _SIGS = {
     "fbn_bd_set_tuning": [_vp, _i32],
     "fbn_bd_lgamma_diff": [_i64, _dbl, _vp, _vp],
     "fbn_bd_score_table_host": [_vp, _i32, _i32, _vp, _vp, _vp],
+    "fbn_bma_run": [_vp, _vp, _i32, _pp],
+    "fbn_bma_run_host": [C.c_int, _vp, _vp, _i64, _vp, _i32, _pp],
+    "fbn_bma_run_bd": [_vp, _vp, _i32, _vp, _pp],
+    "fbn_bma_run_bd_host": [C.c_int, _vp, _vp, _i64, _vp, _i32, _vp, _pp],
+    "fbn_bma_result_info": [_vp, _vp],
+    "fbn_bma_result_arcs": [_vp, _vp, _vp],
+    "fbn_bma_result_destroy": [_vp],
+    "fbn_bma_set_tuning": [_vp, _i32],
+    "fbn_bma_lse_exp": [_dbl, _vp],
+    "fbn_bma_lse": [_dbl, _dbl, _vp],
 }
 
 
@@ -1271,6 +1281,96 @@ class ExactSearch:
     def set_tuning(ci, tile_bits=0):
         """fbn_exact_set_tuning on a context: bits per pass of the subset-max transform; 0 = default."""
         lib.fbn_exact_set_tuning(ci._h, int(tile_bits))
+
+
+class _BmaInfo(C.Structure):
+    _fields_ = [("nvars", C.c_int32), ("tile_bits", C.c_int32), ("passes", C.c_int32), ("levels", C.c_int32),
+                ("prior", C.c_int32), ("pad", C.c_int32), ("families_scored", C.c_int64), ("batches", C.c_int64),
+                ("lattice_bytes", C.c_int64), ("log_z", C.c_double), ("b_full", C.c_double),
+                ("score_kernel_ms", C.c_double), ("alpha_kernel_ms", C.c_double), ("level_kernel_ms", C.c_double),
+                ("gamma_kernel_ms", C.c_double), ("q_kernel_ms", C.c_double), ("score_wall_ms", C.c_double),
+                ("upload_wall_ms", C.c_double), ("alpha_wall_ms", C.c_double), ("level_wall_ms", C.c_double),
+                ("gamma_wall_ms", C.c_double), ("q_wall_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def _lse_exp(x):
+    """fbn_bma_lse_exp, a testing entry: e^x for x <= 0 as the arc-posterior lattices evaluate it.  Host only."""
+    y = C.c_double()
+    lib.fbn_bma_lse_exp(float(x), C.byref(y))
+    return y.value
+
+
+def _lse(a, b):
+    """fbn_bma_lse, a testing entry: ln(e^a + e^b) as the arc-posterior lattices evaluate it.  Host only."""
+    y = C.c_double()
+    lib.fbn_bma_lse(float(a), float(b), C.byref(y))
+    return y.value
+
+
+class ArcPosterior:
+    """Exact arc posteriors for up to 26 variables: P(u -> v | data) for every arc by Bayesian model averaging
+    over all DAGs, the sum-product counterpart of ExactSearch's dynamic programme (fbn_bma_run; Koivisto & Sood
+    2004; no reference counterpart).  score, max_parents, max_family_cells, allowed and learn(source, host) are
+    ExactSearch's.  Under "bde" / ("bde", iss) / "k2" the local score is a log marginal likelihood and the
+    result a true posterior; under "bic" / "aic" it is the usual exp(score) approximation of one.
+
+    The structure prior is order-modular: uniform over the pairs (linear order, DAG consistent with it), so a
+    DAG weighs in proportion to its number of linear extensions -- the price of the exact algorithm and standard
+    for it.  prior: "uniform" (0) adds nothing per family, "indegree" (1) adds -ln C(n - 1, |parents|).
+
+    Results: .arc_prob [n][n] (arc_prob[u][v] = P(u -> v | data), zero diagonal), .skeleton_prob (arc_prob +
+    its transpose), .log_z (the log normaliser F[V]), .b_full (B[V], equal to it up to rounding), .q_empty [n]
+    (each 1 up to rounding), .info (the phase record: passes, kernel and wall ms per phase).  host=True runs the
+    host twin (fbn_bma_run_host) on a Dataset, bit-identical, without a device.  `.ci` is shared as
+    HillClimbing.ci is."""
+
+    PRIORS = {"uniform": 0, "indegree": 1}
+
+    def __init__(self, score="bde", max_parents=None, max_family_cells=0, allowed=None, prior=0, device=0):
+        self.score_name, self.device = score, device
+        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
+        self.prior = self.PRIORS.get(prior, prior)
+        self.ci = None
+
+    _options = ExactSearch._options
+
+    def learn(self, source, host=False):
+        r = C.c_void_p()
+        bd = _bd_score(self.score_name)
+        prior = int(self.prior)
+        if host:
+            o, keep = self._options(source.num_instance)
+            shape = (source.num_vars, _p(source.dims), _p(source.columns), source.num_instance)
+            if bd is not None:
+                lib.fbn_bma_run_bd_host(*shape, C.byref(o), prior, C.byref(bd), C.byref(r))
+            else:
+                lib.fbn_bma_run_host(*shape, C.byref(o), prior, C.byref(r))
+        else:
+            ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
+            self.ci = ci
+            o, keep = self._options(ci.num_samples)
+            if bd is not None:
+                lib.fbn_bma_run_bd(ci._h, C.byref(o), prior, C.byref(bd), C.byref(r))
+            else:
+                lib.fbn_bma_run(ci._h, C.byref(o), prior, C.byref(r))
+        del keep
+        try:
+            info = _BmaInfo()
+            lib.fbn_bma_result_info(r, C.byref(info))
+            n = info.nvars
+            self.arc_prob, self.q_empty = np.zeros((n, n)), np.zeros(n)
+            lib.fbn_bma_result_arcs(r, _p(self.arc_prob), _p(self.q_empty))
+        finally:
+            lib.fbn_bma_result_destroy(r)
+        self.log_z, self.b_full = info.log_z, info.b_full
+        self.skeleton_prob = self.arc_prob + self.arc_prob.T
+        self.info = {k: getattr(info, k) for k, _ in _BmaInfo._fields_ if k != "pad"}
+        return self
+
+    @staticmethod
+    def set_tuning(ci, tile_bits=0):
+        """fbn_bma_set_tuning on a context: bits per pass of the three transforms; 0 = default."""
+        lib.fbn_bma_set_tuning(ci._h, int(tile_bits))
 
 
 def score_marginals(network, marginals, golden):

@@ -198,6 +198,7 @@ struct fbn_ci_ctx {
     bool hc_table_ready = false;
     int64_t hc_chunk = 0;
     int exact_tile_bits = 0;  // fbn_exact_set_tuning (capi_exact.hip): bits per transform pass, 0 = default
+    int bma_tile_bits = 0;    // fbn_bma_set_tuning (capi_bma.hip): likewise for the arc-posterior transforms
     ~fbn_ci_ctx() {
         if (h_open) (void)hipHostFree(h_open);
         if (h_margin) (void)hipHostFree(h_margin);

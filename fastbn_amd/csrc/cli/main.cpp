@@ -25,6 +25,9 @@
 // -a 17, this build's own: exact score-optimal structure learning on -a 14's inputs, flags and output shape
 // (arcs, score, SHD against -f1, --out): the globally best DAG by dynamic programming over variable subsets;
 // a dataset of more than 26 variables is refused with the limit's message.
+// -a 18, this build's own: exact arc posteriors on -a 17's inputs and flags (--prior uniform|indegree, default
+// uniform): P(u -> v | data) for every arc by Bayesian model averaging on the same subset lattices; prints logZ
+// and the arcs with posterior >= 0.5, one per line; --out writes the full matrix, row u = the arcs out of u;
 // -a 15, this build's own: exact posterior sampling on -a 12's inputs: -q draws per case from P(x | e) under
 // --seed; prints the case count, the average log P(e) and the kernel time; --out FILE writes the drawn rows
 // as LIBSVM, the -q rows of a case one after the other (label = the value of variable 0).
@@ -47,7 +50,7 @@ int main(int argc, char **argv) {
     double tol = 0.0, damping = 0.0, eps = -1.0;
     long long num_samples = 10000, max_updating = 10, updating_interval = 2500;  // src/Parameter.cpp:14-15
     unsigned long long seed = 0;
-    std::string out_file, score_name = "bic";
+    std::string out_file, score_name = "bic", prior_name = "uniform";
     int max_parents = -1;
     double iss = 1.0;
     bool ref_given = false, iss_given = false;
@@ -69,12 +72,14 @@ int main(int argc, char **argv) {
         if (a == "--score" && i + 1 < argc) { score_name = argv[++i]; continue; }
         if (a == "--iss" && i + 1 < argc) { iss = atof(argv[++i]); iss_given = true; continue; }
         if (a == "--max-parents" && i + 1 < argc) { max_parents = atoi(argv[++i]); continue; }
+        if (a == "--prior" && i + 1 < argc) { prior_name = argv[++i]; continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17|18] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
-                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--out FILE] [--prefix DIR]"
+                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--prior uniform|indegree] "
+                         "[--out FILE] [--prefix DIR]"
                       << std::endl;
             return 0;
         case 'a': algorithm = atoi(argv[++i]); break;
@@ -557,6 +562,84 @@ int main(int argc, char **argv) {
         }
         fbn_hc_result_destroy(res);
         if (ctx) fbn_ci_ctx_destroy(ctx);
+    } else if (algorithm == 18) {
+        // exact arc posteriors: no counterpart in the reference
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: exact arc posteriors (Bayesian model averaging on the subset lattice), #threads = " << num_threads
+                  << std::endl
+                  << "score = " << score_name << ", max parents = " << max_parents << ", prior = " << prior_name << std::endl
+                  << "\tsample set: " << train_set_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        if (prior_name != "uniform" && prior_name != "indegree") {
+            fprintf(stderr, "Error: --prior is uniform or indegree, not %s\n", prior_name.c_str());
+            return 1;
+        }
+        const int32_t prior = prior_name == "indegree";
+        fbn_dataset *ds = nullptr;
+        if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
+        int n = 0;
+        int64_t ns = 0;
+        fbn_dataset_shape(ds, &n, &ns);
+        std::vector<int32_t> dims((size_t)n);
+        std::vector<uint8_t> cols((size_t)n * (size_t)ns);
+        fbn_dataset_dims(ds, dims.data());
+        fbn_dataset_columns(ds, cols.data());
+        fbn_dataset_destroy(ds);
+        const bool is_bd = score_name == "bde" || score_name == "k2";
+        if (iss_given && score_name != "bde") {
+            fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
+            return 1;
+        }
+        const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+        fbn_exact_options xopt{};
+        if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &xopt.penalty)) return die();
+        xopt.max_parents = max_parents;
+        fbn_bma_result *res = nullptr;
+        fbn_ci_ctx *ctx = nullptr;
+        if (device < 0) {
+            if (is_bd ? fbn_bma_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, prior, &bd, &res)
+                      : fbn_bma_run_host(n, dims.data(), cols.data(), ns, &xopt, prior, &res))
+                return die();
+        } else {
+            if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
+            if (is_bd ? fbn_bma_run_bd(ctx, &xopt, prior, &bd, &res) : fbn_bma_run(ctx, &xopt, prior, &res)) return die();
+        }
+        fbn_bma_info info;
+        fbn_bma_result_info(res, &info);
+        std::vector<double> P((size_t)n * (size_t)n);
+        fbn_bma_result_arcs(res, P.data(), nullptr);
+        char buf[160];
+        std::cout << "variables = " << n << ", samples = " << ns << std::endl;
+        snprintf(buf, sizeof buf, "logZ = %.17g, B[V] = %.17g", info.log_z, info.b_full);
+        std::cout << buf << std::endl << "arcs with posterior >= 0.5:" << std::endl;
+        for (int u = 0; u < n; ++u)
+            for (int v = 0; v < n; ++v)
+                if (P[(size_t)u * n + v] >= 0.5) {
+                    snprintf(buf, sizeof buf, "%d -> %d %.17g", u, v, P[(size_t)u * n + v]);
+                    std::cout << buf << std::endl;
+                }
+        std::cout << "bma: " << info.families_scored << " families scored in " << info.batches << " batches, " << info.lattice_bytes
+                  << " lattice bytes, " << info.passes << " passes per transform; device kernel: scores " << info.score_kernel_ms * 1e-3
+                  << " s, alpha " << info.alpha_kernel_ms * 1e-3 << " s, levels " << info.level_kernel_ms * 1e-3 << " s, Gamma "
+                  << info.gamma_kernel_ms * 1e-3 << " s, q " << info.q_kernel_ms * 1e-3 << " s; total " << info.wall_ms * 1e-3 << " s"
+                  << std::endl;
+        if (!out_file.empty()) {
+            FILE *f = fopen(out_file.c_str(), "w");
+            if (!f) {
+                fprintf(stderr, "Error: cannot write %s\n", out_file.c_str());
+                return 1;
+            }
+            for (int u = 0; u < n; ++u)
+                for (int v = 0; v < n; ++v) fprintf(f, "%.17g%c", P[(size_t)u * n + v], v + 1 < n ? ' ' : '\n');
+            fclose(f);
+            std::cout << "arc posteriors written to " << out_file << std::endl;
+        }
+        fbn_bma_result_destroy(res);
+        if (ctx) fbn_ci_ctx_destroy(ctx);
     } else if (algorithm == 15) {
         // exact posterior sampling: no counterpart in the reference (its samplers weigh; none draws from P(x | e))
         std::cout << "===============================" << std::endl
@@ -657,7 +740,7 @@ int main(int argc, char **argv) {
         std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
                   << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16 and 17)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16, 17 and 18)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

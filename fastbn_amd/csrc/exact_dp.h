@@ -42,8 +42,9 @@ struct ExactPass {
 // the passes of tile_bits (1 .. kExactTileBitsMax) bits each over M >= 1 bits, the last one ragged.  A
 // block fills the LDS tile (2^kExactLdsBits entries, or 2^tile_bits where that is more): the c run bits
 // are what the pass's G bits leave of it, at most the bits below the group.  Returns their number.
-inline int fbn_exact_passes(int M, int tile_bits, ExactPass *out) {
-    const int T = tile_bits, lds = T > kExactLdsBits ? T : kExactLdsBits;
+// lds_bits: the tile of the kernel that runs the passes (exact_bma.hip's entries are 8 bytes, not 12).
+inline int fbn_exact_passes(int M, int tile_bits, ExactPass *out, int lds_bits = kExactLdsBits) {
+    const int T = tile_bits, lds = T > lds_bits ? T : lds_bits;
     int np = 0;
     for (int g0 = 0; g0 < M; g0 += T, ++np) {
         const int G = M - g0 < T ? M - g0 : T, room = g0 == 0 ? M - G : g0;
@@ -72,9 +73,11 @@ inline double ExactStateBytes(int n) {
 // options, dims and the variable limit; FBN_ERR_LIMIT names the bytes the lattices would take
 int ExactCheck(int nvars, const int32_t *dims, const fbn_exact_options &opt);
 // phase 1 for variable v: ls[0 .. 2^(n-1)) = -inf, then the candidates' scores, enumerated by size and
-// lexicographically within a size, scored through `scorer` in batches
+// lexicographically within a size, scored through `scorer` in batches.  size_prior (the arc-posterior
+// learner's log structure prior, exact_bma.h): a candidate of k parents gets score + size_prior[k]; nullptr
+// (the exact search): the score as it is
 int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, int v, double *ls,
-                     fbn_exact_info *info);
+                     fbn_exact_info *info, const double *size_prior = nullptr);
 // phase 4: the DAG from sink [2^n] and arg_at(v, index) = arg_v[index], the chosen families scored once
 // more for the node values; RV = R[V]
 int ExactTrace(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, const uint8_t *sink,

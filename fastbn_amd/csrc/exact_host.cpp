@@ -64,7 +64,7 @@ int ExactCheck(int nvars, const int32_t *dims, const fbn_exact_options &opt) {
 }
 
 int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, int v, double *ls,
-                     fbn_exact_info *info) {
+                     fbn_exact_info *info, const double *size_prior) {
     const int64_t cap = CellCap(opt);
     std::fill(ls, ls + ((size_t)1 << (n - 1)), -std::numeric_limits<double>::infinity());
     std::vector<int32_t> others;
@@ -79,7 +79,8 @@ int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, c
         if (F.cells.empty()) return FBN_OK;
         sc.resize(F.cells.size());
         if (int rc = Score(scorer, F, nullptr, sc.data(), info)) return rc;
-        for (size_t f = 0; f < where.size(); ++f) ls[where[f]] = sc[f];
+        for (size_t f = 0; f < where.size(); ++f)  // squeezing keeps the size: popcount(where) parents
+            ls[where[f]] = size_prior ? sc[f] + size_prior[__builtin_popcount(where[f])] : sc[f];
         F.off.assign(1, 0);
         F.cols.clear(), F.cells.clear(), F.pen.clear(), where.clear();
         return FBN_OK;

@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -181,5 +181,35 @@ struct ExactSinkArgs {
     int nvars, level;
 };
 extern "C" hipError_t fbn_exact_sink_launch(const ExactSinkArgs *a, hipStream_t stream);
+// The lattice kernels of the arc-posterior learner (exact_bma.hip; include/fastbn.h states the quantities).
+// fbn_bma_pass_launch: one pass (ExactPass geometry over kBmaLdsBits) of a transform of all nvars value
+// lattices x [nvars][2^M], in place after the load.  dir: kBmaSubset (an index with the bit set combines with
+// its partner) or kBmaSuperset (with the bit clear); op: kBmaLse or kBmaAdd; load, what an entry starts as:
+// kBmaLoadX x itself; kBmaLoadLs ls (the first alpha pass); kBmaLoadGamma F[U] + B[V \ U \ v] (the first
+// Gamma pass); kBmaLoadP exp((ls + x) - F[V]) (the first q pass).  The valid triples are the six the
+// learner uses; any other is hipErrorInvalidValue.
+enum { kBmaSubset = 0, kBmaSuperset = 1 };
+enum { kBmaLse = 0, kBmaAdd = 1 };
+enum { kBmaLoadX = 0, kBmaLoadLs = 1, kBmaLoadGamma = 2, kBmaLoadP = 3 };
+struct BmaPassArgs {
+    double *x;
+    const double *ls, *F, *B;  // read by the loads that name them
+    int nvars, M;
+    int gpos, hb, lo, s0, G;  // ExactPass
+    int dir, op, load;
+};
+extern "C" hipError_t fbn_bma_pass_launch(const BmaPassArgs *a, hipStream_t stream);
+// level `level` of the forward and backward recursions: F[W] and B[W] of every W of that popcount from level
+// - 1 and the alpha lattices (level 0 writes F[0] = B[0] = 0)
+struct BmaLevelArgs {
+    const double *alpha;
+    double *F, *B;
+    int nvars, level;
+};
+extern "C" hipError_t fbn_bma_level_launch(const BmaLevelArgs *a, hipStream_t stream);
+// out[u * nvars + v] = q_v[{u}] (0 on the diagonal), out[nvars * nvars + v] = q_v[{}], then F[V] and B[V]:
+// nvars * nvars + nvars + 2 doubles
+extern "C" hipError_t fbn_bma_gather_launch(const double *q, const double *F, const double *B, int nvars, double *out,
+                                            hipStream_t stream);
 
 #endif

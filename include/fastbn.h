@@ -1242,6 +1242,71 @@ int fbn_bd_lgamma_diff(int64_t n, double a, double *d, int32_t *threshold);
 int fbn_bd_score_table_host(const uint32_t *tab, int32_t r, int32_t q, const fbn_bd_score *bd, double *loglik,
                             double *score);
 
+/* ------------------------------------------------------------------ exact arc posteriors (Bayesian model averaging)
+ * P(u -> v | data) for every arc, exactly, by the sum-product counterpart of the exact search's dynamic
+ * programme (Koivisto & Sood 2004; Koivisto 2006 for all arcs in one backward pass) (-a 18).  Same inputs,
+ * scores, constraints and options record as fbn_exact_run; the device path is held bit for bit to a host twin.
+ * Under FBN_SCORE_BDE / K2 the local score is a log marginal likelihood and the result a true posterior;
+ * under a penalised score (bic, aic) it is the usual exp(score) approximation of one.
+ *
+ * The structure prior is ORDER-MODULAR: uniform over the pairs (linear order, DAG consistent with it), so a
+ * DAG weighs in proportion to its number of linear extensions.  That is the price of the exact algorithm and
+ * standard for it.  Per family it is prior = 0: nothing; prior = 1: -ln C(n - 1, |S|), uniform over indegrees.
+ *
+ * All quantities are natural logarithms; (+) is log-sum-exp, evaluated by csrc/exact_lse.h on both sides.
+ * n variables, V the full set, c_v(S) and the candidates as above.
+ *   ls_v[S]    = the exact search's local score (-inf for non-candidates, the empty set always a candidate)
+ *                plus the prior term of |S|, one of n doubles computed once on the host
+ *   a_v[S]     = (+) over T within S of ls_v[T]: n - 1 sweeps, bit b ascending; in sweep b an index with bit b
+ *                set becomes lse(own, partner)
+ *   F[{}] = 0, F[W] = (+) over v in W, ascending, of F[W \ v] + a_v[c_v(W \ v)];   logZ = F[V]
+ *   B[{}] = 0, B[T] = (+) over v in T, ascending, of a_v[c_v(V \ T)] + B[T \ v]    (v first among T, after V \ T);
+ *                B[V] equals F[V] up to rounding; both are reported
+ *   (a (+) over v ascending is a left fold: the first term, then lse(accumulated, next term))
+ *   g_v[c_v(U)] = F[U] + B[V \ U \ v] for U within V \ v
+ *   G_v[T]     = (+) over U containing T of g_v[U]: the same sweep order; in sweep b an index with bit b clear
+ *                becomes lse(own, partner)
+ *   p_v[T]     = exp((ls_v[T] + G_v[T]) - logZ): the posterior that v's parent set is exactly T; 0 where ls is -inf
+ *   q_v[T]     = the plain sum over U containing T of p_v[U], same sweeps (own + partner);
+ *                q_v[{u}] = P(u -> v | data), q_v[{}] = 1 up to rounding
+ * Every lattice entry has one evaluation order whatever the tiling of the sweeps, so any tile_bits gives the
+ * same bits, the arc matrix included.
+ *
+ * Limits: at most 26 variables; device state 16 n 2^(n-1) + 16 2^n bytes (two value lattices, F and B),
+ * checked against the free device memory before anything is allocated: FBN_ERR_LIMIT, the message carrying the
+ * byte count.  One variable: the empty matrix, logZ = ls_0[{}]. */
+typedef struct fbn_bma_info {
+    int32_t nvars, tile_bits;  /* tile_bits: bits swept per transform pass (0 on the host twin) */
+    int32_t passes, levels;    /* passes of ONE transform (each of the three runs as many); level launches, n + 1 */
+    int32_t prior, pad;
+    int64_t families_scored, batches;
+    int64_t lattice_bytes;     /* 16 n 2^(n-1) + 16 2^n */
+    double log_z, b_full;      /* F[V], B[V] */
+    double score_kernel_ms, alpha_kernel_ms, level_kernel_ms, gamma_kernel_ms, q_kernel_ms; /* 0 on the host twin */
+    double score_wall_ms, upload_wall_ms, alpha_wall_ms, level_wall_ms, gamma_wall_ms, q_wall_ms, wall_ms;
+} fbn_bma_info;
+
+typedef struct fbn_bma_result fbn_bma_result;
+
+/* prior: 0 uniform, 1 indegree-uniform (above); anything else FBN_ERR_ARG.  options as fbn_exact_run's. */
+int fbn_bma_run(fbn_ci_ctx *c, const fbn_exact_options *options, int32_t prior, fbn_bma_result **out);
+int fbn_bma_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                     const fbn_exact_options *options, int32_t prior, fbn_bma_result **out);
+int fbn_bma_run_bd(fbn_ci_ctx *c, const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd,
+                   fbn_bma_result **out);
+int fbn_bma_run_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                        const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd, fbn_bma_result **out);
+int fbn_bma_result_info(const fbn_bma_result *r, fbn_bma_info *info);
+/* arc_prob [nvars][nvars]: arc_prob[u * nvars + v] = P(u -> v | data), zero diagonal; q_empty [nvars] = q_v[{}].
+ * Either may be NULL. */
+int fbn_bma_result_arcs(const fbn_bma_result *r, double *arc_prob, double *q_empty);
+int fbn_bma_result_destroy(fbn_bma_result *r);
+/* tile_bits = bits per transform pass, 1 .. 13; 0 = default.  Any value gives the same bits: a tuning/testing entry. */
+int fbn_bma_set_tuning(fbn_ci_ctx *c, int32_t tile_bits);
+/* Host-only testing entries into exact_lse.h: *y = fbn_lse_exp(x) (x <= 0), *y = fbn_lse(a, b). */
+int fbn_bma_lse_exp(double x, double *y);
+int fbn_bma_lse(double a, double b, double *y);
+
 #ifdef __cplusplus
 }
 #endif
