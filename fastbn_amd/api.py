@@ -217,6 +217,25 @@ _SIGS = {
     "fbn_bma_set_tuning": [_vp, _i32],
     "fbn_bma_lse_exp": [_dbl, _vp],
     "fbn_bma_lse": [_dbl, _dbl, _vp],
+    "fbn_cdataset_load_csv": [_cstr, _pp],
+    "fbn_cdataset_shape": [_vp, _vp, _vp],
+    "fbn_cdataset_columns": [_vp, _vp],
+    "fbn_cdataset_var_name": [_vp, C.c_int, C.c_char_p, C.c_int],
+    "fbn_cdataset_destroy": [_vp],
+    "fbn_gci_upload": [_vp, C.c_int, _i64, C.c_int, _pp],
+    "fbn_gci_from_device": [_vp, C.c_int, _i64, C.c_int, _pp],
+    "fbn_gci_corr": [_vp, _vp],
+    "fbn_gci_run": [_vp, _vp, _i64, C.c_int, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "fbn_gci_pc_stable": [_vp, _dbl, C.c_int, _pp],
+    "fbn_pc_degenerate": [_vp, _vp],
+    "fbn_gci_set_tuning": [_vp, _i32, _i32],
+    "fbn_gci_info": [_vp, _vp],
+    "fbn_gci_last_kernel_ms": [_vp, _vp],
+    "fbn_gci_corr_kernel_ms": [_vp, _vp],
+    "fbn_gci_ctx_destroy": [_vp],
+    "fbn_gci_host_run": [_vp, C.c_int, _i64, _vp, _i64, C.c_int, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "fbn_gci_host_pc_stable": [_vp, C.c_int, _i64, _dbl, C.c_int, _pp],
+    "fbn_gci_tau": [_dbl, _i64, C.c_int, _vp],
 }
 
 
@@ -278,7 +297,7 @@ _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
                 "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2, "MostProbableExplanation": 2,
                 "ExpectationMaximization": 2, "PosteriorSampler": 2, "GibbsSampling": 2,
-                "IndependenceTest": 3, "Dataset": 4, "Network": 5}
+                "IndependenceTest": 3, "GaussianIndependenceTest": 3, "Dataset": 4, "Network": 5}
 
 
 def _register(obj):
@@ -489,6 +508,39 @@ class Dataset:
             self.columns = np.ascontiguousarray(columns, dtype=np.uint8)
             self.dims = np.ascontiguousarray(dims, dtype=np.int32)
             self.names = [str(i) for i in range(self.columns.shape[0])]
+
+    @property
+    def num_vars(self):
+        return self.columns.shape[0]
+
+    @property
+    def num_instance(self):
+        return self.columns.shape[1]
+
+
+class ContinuousDataset:
+    """Real-valued training set: `columns` float64 [nvars][nsamples], from a CSV (a header line of names,
+    then rows of numbers: fbn_cdataset_load_csv) or from an array."""
+
+    def __init__(self, path=None, columns=None, names=None):
+        if path is not None:
+            h = C.c_void_p()
+            lib.fbn_cdataset_load_csv(os.fsencode(path), C.byref(h))
+            nv, ns = C.c_int(), C.c_int64()
+            lib.fbn_cdataset_shape(h, C.byref(nv), C.byref(ns))
+            self.columns = np.zeros((nv.value, ns.value), np.float64)
+            lib.fbn_cdataset_columns(h, _p(self.columns))
+            self.names = []
+            buf = C.create_string_buffer(256)
+            for v in range(nv.value):
+                lib.fbn_cdataset_var_name(h, v, buf, 256)
+                self.names.append(buf.value.decode())
+            lib.fbn_cdataset_destroy(h)
+        else:
+            self.columns = np.ascontiguousarray(columns, dtype=np.float64)
+            if self.columns.ndim != 2:
+                raise ValueError("columns: float64 [nvars][nsamples]")
+            self.names = list(names) if names is not None else [str(i) for i in range(self.columns.shape[0])]
 
     @property
     def num_vars(self):
@@ -794,6 +846,93 @@ class IndependenceTest(_Handle):
 
 
 
+def _gci_outputs(n):
+    return np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n, np.uint8)
+
+
+class GaussianIndependenceTest(_Handle):
+    """Fisher-z tests of the partial correlation on the device (fbn_gci_*): the float64 column store and
+    its correlation matrix stay resident."""
+
+    _destroy = "fbn_gci_ctx_destroy"
+
+    def __init__(self, dataset, alpha=0.05, device=0):
+        self.alpha = alpha
+        self.num_vars, self.num_samples = int(dataset.num_vars), int(dataset.num_instance)
+        h = C.c_void_p()
+        lib.fbn_gci_upload(_p(dataset.columns), self.num_vars, self.num_samples, device, C.byref(h))
+        self._h = h
+        _register(self)
+
+    def correlation(self):
+        """R float64 [nvars][nvars] as the tests read it: symmetric, unit diagonal."""
+        R = np.zeros((self.num_vars, self.num_vars))
+        lib.fbn_gci_corr(self._h, _p(R))
+        return R
+
+    def run(self, items, d):
+        """items [n][2 + d] = (x, y, z...) -> (r, z, p, indep); a degenerate test has r = NaN and is dependent."""
+        items = np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 2 + d)
+        n = items.shape[0]
+        r, z, p, ind = _gci_outputs(n)
+        deg = C.c_int64()
+        lib.fbn_gci_run(self._h, _p(items), n, d, self.alpha, _p(r), _p(z), _p(p), _p(ind), C.byref(deg))
+        self.degenerate = deg.value
+        return r, z, p, ind.astype(bool)
+
+    def IndependenceResult(self, x, y, z=()):
+        r, zz, p, ind = self.run(np.array([[x, y, *z]], np.int32), len(z))
+        return {"r": r[0], "z": zz[0], "p_value": p[0], "is_independent": bool(ind[0])}
+
+    def set_tuning(self, split_k=0, tile=0):
+        """Sample slices and tile edge (32 / 64) of the Gram kernel, 0 = automatic; R is recomputed."""
+        lib.fbn_gci_set_tuning(self._h, int(split_k), int(tile))
+
+    def info(self):
+        out = np.zeros(4, np.int64)
+        lib.fbn_gci_info(self._h, _p(out))
+        return {k: int(v) for k, v in zip(("tile", "split_k", "slab_bytes", "degenerate"), out)}
+
+    def corr_kernel_ms(self):
+        """(column means, Gram, reduce) of the last computation of R."""
+        ms = (C.c_float * 3)()
+        lib.fbn_gci_corr_kernel_ms(self._h, ms)
+        return tuple(ms)
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_gci_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+
+def gci_host_run(R, nsamples, items, d, alpha=0.05):
+    """The host twin of GaussianIndependenceTest.run on a correlation matrix R (fbn_gci_host_run) ->
+    (r, z, p, indep, degenerate count)."""
+    R = np.ascontiguousarray(R, np.float64)
+    items = np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 2 + d)
+    n = items.shape[0]
+    r, z, p, ind = _gci_outputs(n)
+    deg = C.c_int64()
+    lib.fbn_gci_host_run(_p(R), R.shape[0], int(nsamples), _p(items), n, d, alpha, _p(r), _p(z), _p(p), _p(ind),
+                         C.byref(deg))
+    return r, z, p, ind.astype(bool), deg.value
+
+
+def gci_host_pc_stable(R, nsamples, alpha=0.05, depth=1000):
+    """The host twin of PC-stable on continuous data over a correlation matrix R -> PCResult."""
+    R = np.ascontiguousarray(R, np.float64)
+    r = C.c_void_p()
+    lib.fbn_gci_host_pc_stable(_p(R), R.shape[0], int(nsamples), alpha, depth, C.byref(r))
+    return PCResult(r)
+
+
+def gci_tau(alpha, nsamples, d):
+    """tau_d: a Gaussian test is independent iff |r| <= tau_d."""
+    t = C.c_double()
+    lib.fbn_gci_tau(alpha, int(nsamples), d, C.byref(t))
+    return t.value
+
+
 class PCResult(_Handle):
     """A PC-stable result handle: skeleton, sepsets, orientation, SHD (fbn_pc_*)."""
 
@@ -825,6 +964,9 @@ class PCResult(_Handle):
         nb = C.c_int64()
         lib.fbn_pc_device_bytes(handle, C.byref(nb))
         self.device_bytes = nb.value
+        deg = C.c_int64()
+        lib.fbn_pc_degenerate(handle, C.byref(deg))
+        self.degenerate = deg.value  # Gaussian runs: tests with a singular conditioning block (dependent)
 
     @classmethod
     def with_levels(cls, handle):
@@ -909,12 +1051,24 @@ class PCStable:
 
     def StructLearnCompData(self, dataset, group_size=1, num_threads=1, print_struct=False, verbose=False):
         """`dataset`: a Dataset (uploaded for this call) or an IndependenceTest whose column store is
-        already resident on the device (reused across calls)."""
+        already resident on the device (reused across calls); or a ContinuousDataset / a
+        GaussianIndependenceTest: Fisher-z tests of the partial correlation (group_size must be 1)."""
+        if isinstance(dataset, (ContinuousDataset, GaussianIndependenceTest)):
+            if group_size != 1:
+                raise ValueError("continuous data: group_size must be 1")
+            ci = dataset if isinstance(dataset, GaussianIndependenceTest) else GaussianIndependenceTest(dataset, self.alpha, self.device)
+            self.ci = ci
+            r = C.c_void_p()
+            lib.fbn_gci_pc_stable(ci._h, self.alpha, self.depth, C.byref(r))
+            return self._take(PCResult(r))
         ci = dataset if isinstance(dataset, IndependenceTest) else IndependenceTest(dataset, self.alpha, self.device)
         self.ci = ci  # the context of the run: ParameterLearning(pc.ci) learns from the same upload
         r = C.c_void_p()
         lib.fbn_pc_stable(ci._h, self.alpha, self.depth, group_size, C.byref(r))
-        self.result = res = PCResult(r)
+        return self._take(PCResult(r))
+
+    def _take(self, res):
+        self.result = res
         self.tests_per_level, self.launched_per_level = res.tests_per_level, res.launched_per_level
         self.total_s, self.kernel_s, self.device_bytes = res.total_s, res.kernel_s, res.device_bytes
         self.num_ci_test = res.num_ci_test

@@ -28,6 +28,10 @@
 // -a 18, this build's own: exact arc posteriors on -a 17's inputs and flags (--prior uniform|indegree, default
 // uniform): P(u -> v | data) for every arc by Bayesian model averaging on the same subset lattices; prints logZ
 // and the arcs with posterior >= 0.5, one per line; --out writes the full matrix, row u = the arcs out of u;
+// -a 19, this build's own: PC-stable on continuous data: -f2 is a CSV of reals (a header line, then rows of numbers);
+// Fisher-z tests of the partial correlation at alpha 0.05, --depth as -a 0; prints -a 0's lines (tests per level,
+// remaining edges, SHD against -f1 when given); --out FILE writes the learned PDAG, one edge per line: from, to, 1
+// for an arc; min, max, 0 for an undirected edge.
 // -a 15, this build's own: exact posterior sampling on -a 12's inputs: -q draws per case from P(x | e) under
 // --seed; prints the case count, the average log P(e) and the kernel time; --out FILE writes the drawn rows
 // as LIBSVM, the -q rows of a case one after the other (label = the value of variable 0).
@@ -75,7 +79,7 @@ int main(int argc, char **argv) {
         if (a == "--prior" && i + 1 < argc) { prior_name = argv[++i]; continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17|18] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17|18|19] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
                          "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--prior uniform|indegree] "
@@ -640,6 +644,74 @@ int main(int argc, char **argv) {
         }
         fbn_bma_result_destroy(res);
         if (ctx) fbn_ci_ctx_destroy(ctx);
+    } else if (algorithm == 19) {
+        // PC-stable on continuous data: no counterpart in the reference (its ContinuousNode has no learner)
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: PC-stable on continuous data (Fisher-z partial correlation), #threads = " << num_threads << std::endl
+                  << "\tsample set: " << train_set_file << std::endl;
+        if (ref_given) std::cout << "\treference BN: " << ref_net_file << std::endl;
+        std::cout << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        fbn_cdataset *ds = nullptr;
+        if (fbn_cdataset_load_csv(train_set_file.c_str(), &ds)) return die();
+        int n = 0;
+        int64_t ns = 0;
+        fbn_cdataset_shape(ds, &n, &ns);
+        std::vector<double> cols((size_t)n * (size_t)ns);
+        fbn_cdataset_columns(ds, cols.data());
+        fbn_cdataset_destroy(ds);
+        std::cout << "==================================================" << '\n'
+                  << "Begin structural learning with PC-stable" << std::endl;
+        fbn_gci_ctx *ctx = nullptr;
+        fbn_pc_result *res = nullptr;
+        if (fbn_gci_upload(cols.data(), n, ns, device, &ctx) || fbn_gci_pc_stable(ctx, 0.05, depth, &res)) return die();
+        int nl = 0, ne = 0, no = 0;
+        fbn_pc_num_levels(res, &nl);
+        std::vector<int64_t> tests((size_t)nl);
+        fbn_pc_level_tests(res, tests.data());
+        int64_t total = 0;
+        for (int l = 0; l < nl; ++l) {
+            total += tests[l];
+            std::cout << "Level " << l << "... # of CI-tests is " << total << std::endl;
+        }
+        fbn_pc_num_edges(res, &ne);
+        double total_s = 0, kernel_s = 0, min_margin = 0;
+        int64_t near = 0, degenerate = 0;
+        float corr_ms[3] = {0.f, 0.f, 0.f};
+        fbn_pc_timing(res, &total_s, &kernel_s);
+        fbn_pc_decision_margin(res, &min_margin, &near);
+        fbn_pc_degenerate(res, &degenerate);
+        fbn_gci_corr_kernel_ms(ctx, corr_ms);
+        std::cout << "==================================================" << std::endl;
+        std::cout << "# of CI-tests is " << total << ", # of degenerate tests is " << degenerate << std::endl;
+        std::cout << "# remaining edges = " << ne << std::endl;
+        std::cout << "correlation: device kernels " << (corr_ms[0] + corr_ms[1] + corr_ms[2]) * 1e-3 << " s; pc-stable step 1: "
+                  << total_s << " s (device kernels " << kernel_s << " s)" << std::endl;
+        std::cout << "min | |r| - tau | = " << min_margin << " (" << near << " decisions within 1e-9)" << std::endl;
+        fbn_pc_num_oriented_edges(res, &no);
+        std::vector<int32_t> tri(3 * (size_t)no + 3);
+        fbn_pc_oriented_edges(res, tri.data());
+        if (ref_given) {
+            int shd = 0;
+            if (fbn_shd_bif(ref_net_file.c_str(), n, tri.data(), no, &shd)) return die();
+            std::cout << "SHD = " << shd << std::endl;
+        }
+        if (!out_file.empty()) {
+            // one line per edge of the learned PDAG: from, to, 1 for an arc; min, max, 0 for an undirected edge
+            FILE *f = fopen(out_file.c_str(), "w");
+            if (!f) {
+                fprintf(stderr, "Error: cannot write %s\n", out_file.c_str());
+                return 1;
+            }
+            for (int e = 0; e < no; ++e) fprintf(f, "%d %d %d\n", tri[3 * e], tri[3 * e + 1], tri[3 * e + 2]);
+            fclose(f);
+            std::cout << "PDAG written to " << out_file << std::endl;
+        }
+        fbn_pc_result_destroy(res);
+        fbn_gci_ctx_destroy(ctx);
     } else if (algorithm == 15) {
         // exact posterior sampling: no counterpart in the reference (its samplers weigh; none draws from P(x | e))
         std::cout << "===============================" << std::endl
@@ -740,7 +812,7 @@ int main(int argc, char **argv) {
         std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
                   << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16, 17 and 18)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16, 17, 18 and 19)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

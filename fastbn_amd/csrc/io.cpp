@@ -611,4 +611,47 @@ int LoadLibsvm(const std::string &path, int num_nodes, int8_t *ev, int32_t *labe
     return FBN_OK;
 }
 
+// A CSV of reals: a header line of names, then one row of nvars numbers per sample (strtod's formats; an
+// empty line is skipped) -> cols [var][sample].  A field that is not a number, or a row of another length,
+// is FBN_ERR_IO naming the row.
+int LoadRealCsv(const std::string &path, int *nvars, int64_t *nsamples, std::vector<std::string> &names,
+                std::vector<double> &cols) {
+    std::ifstream in(path);
+    if (!in) return SetError(FBN_ERR_IO, "cannot open %s", path.c_str());
+    std::string line;
+    if (!std::getline(in, line)) return SetError(FBN_ERR_IO, "%s: empty file", path.c_str());
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+    names.clear();
+    for (size_t p = 0;;) {
+        const size_t c = line.find(',', p);
+        names.push_back(line.substr(p, c == std::string::npos ? c : c - p));
+        if (c == std::string::npos) break;
+        p = c + 1;
+    }
+    const int V = (int)names.size();
+    std::vector<double> rows;  // row-major
+    int64_t n = 0;
+    while (std::getline(in, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+        if (line.empty()) continue;
+        const char *p = line.c_str();
+        for (int v = 0; v < V; ++v) {
+            char *end = nullptr;
+            const double x = strtod(p, &end);
+            if (end == p || (v + 1 < V ? *end != ',' : *end != '\0'))
+                return SetError(FBN_ERR_IO, "%s: row %lld: field %d is not a number or the row has not %d fields", path.c_str(),
+                                (long long)n, v, V);
+            rows.push_back(x);
+            p = end + 1;
+        }
+        ++n;
+    }
+    if (n == 0) return SetError(FBN_ERR_IO, "%s: no rows", path.c_str());
+    cols.resize((size_t)V * (size_t)n);
+    for (int64_t s = 0; s < n; ++s)
+        for (int v = 0; v < V; ++v) cols[(size_t)v * (size_t)n + (size_t)s] = rows[(size_t)s * V + v];
+    *nvars = V, *nsamples = n;
+    return FBN_OK;
+}
+
 }  // namespace fbn

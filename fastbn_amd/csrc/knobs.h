@@ -29,6 +29,8 @@ inline constexpr Knob kKnobs[] = {
     // CI tests: counting paths (capi_ci.hip, capi_pc.hip)
     {"FBN_CI_BITSN", "off: levels >= 2 count from byte columns", kSeam, kPerCall},
     {"FBN_CI_FORCE_BITS", "off: bit-sliced columns from 4096 samples", kSeam, kPerCall},
+    {"FBN_CI_GCI_SPLITK", "0: fbn_gci_set_tuning's split_k, else about sixteen workgroups per CU", kSeam, kPerCall},
+    {"FBN_CI_GCI_TILE", "0: fbn_gci_set_tuning's tile, else 64 from 2048 variables, 32 below", kSeam, kPerCall},
     {"FBN_CI_GRAM4_SPLITS", "CUs / tiles", kSeam, kPerCall},
     {"FBN_CI_GRAM_NO_MFMA", "off: FP4 MFMA Gram where it pays", kSeam, kPerCall},
     {"FBN_CI_NO_BAND", "off: the G^2 decision band is built", kSeam, kPerCall},

@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, gci_corr.hip, gci_test.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -211,5 +211,38 @@ extern "C" hipError_t fbn_bma_level_launch(const BmaLevelArgs *a, hipStream_t st
 // nvars * nvars + nvars + 2 doubles
 extern "C" hipError_t fbn_bma_gather_launch(const double *q, const double *F, const double *B, int nvars, double *out,
                                             hipStream_t stream);
+// The correlation kernels of the Gaussian CI test (gci_corr.hip) over X float64 [nvars][N].
+// fbn_gci_means_launch: mean[v] and bad[v] (the column holds a non-finite value).  fbn_gci_gram_launch: the
+// centred Gram's upper tiles of tile x tile variables (64 or 32) in split_k sample slices of whole stages
+// (fbn_gci_stage() samples; 1 <= split_k <= stages) into slab, split_k * nt * tile^2 doubles with nt = T (T + 1) / 2,
+// T = ceil(nvars / tile).  fbn_gci_reduce_launch: the slices summed in order -> R [nvars][nvars] (symmetric, unit
+// diagonal) and var[v] = S_vv.
+struct GciCorrArgs {
+    const double *X;
+    double *mean;
+    int *bad;
+    double *slab, *R, *var;
+    int nvars;
+    long long N;
+    int tile, split_k;
+};
+extern "C" int fbn_gci_stage(void);
+extern "C" hipError_t fbn_gci_means_launch(const double *X, int nvars, long long N, double *mean, int *bad, hipStream_t stream);
+extern "C" hipError_t fbn_gci_gram_launch(const GciCorrArgs *a, hipStream_t stream);
+extern "C" hipError_t fbn_gci_reduce_launch(const GciCorrArgs *a, hipStream_t stream);
+// The test kernel (gci_test.hip): n tests of d conditioning variables (0..8), one per lane; items [n][2 + d], or
+// null with d == 0: test t is pair t of the complete graph.  r is optional.  stats: {smallest | |r| - tau | as
+// IEEE bits, tests within 1e-9 of tau, degenerate tests}, updated with one atomic group per wave.
+struct GciTestArgs {
+    const double *R;
+    int nvars;
+    const int32_t *items;
+    long long n;
+    double tau;
+    double *r;
+    uint8_t *indep;
+    unsigned long long *stats;
+};
+extern "C" hipError_t fbn_gci_test_launch(const GciTestArgs *a, int d, hipStream_t stream);
 
 #endif

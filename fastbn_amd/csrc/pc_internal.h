@@ -276,6 +276,7 @@ struct PCResultHost {
     double min_margin = 0.0;
     int64_t near_alpha = 0;
     bool margin_done = false;  // min_margin / near_alpha already hold the run's log (device-resident run)
+    int64_t degenerate = 0;    // Gaussian runs (gci.h): tests with a singular conditioning block, taken as dependent
     // skeleton path: 0 host-driven levels, 1 device-resident search (pc_small), 2 device-resident
     // search refused at launch or timed out at a grid barrier -> host-driven levels (same answer)
     int path = 0;

@@ -1307,6 +1307,66 @@ int fbn_bma_set_tuning(fbn_ci_ctx *c, int32_t tile_bits);
 int fbn_bma_lse_exp(double x, double *y);
 int fbn_bma_lse(double a, double b, double *y);
 
+/* ------------------------------------------------------------------ PC-stable on continuous data (Gaussian CI test)
+ * Structure learning from real-valued columns with the Fisher-z test of the partial correlation (Kalisch &
+ * Buehlmann 2007) (-a 19).  The sufficient statistic is the correlation matrix R of the columns, computed once
+ * on the device in two passes (column means; then the centred Gram on the fp64 matrix cores, the mean
+ * subtracted on the way in, so a large offset of a column does not cancel).  A test (x, y | Z), |Z| = d <= 8,
+ * eliminates Z from the (d + 2) x (d + 2) block of R without square roots and takes
+ *   r = c / sqrt(a b) of the 2 x 2 Schur complement (a c; c b), clamped to [-1, 1];
+ *   independent iff |r| <= tau_d = tanh(Phi^-1(1 - alpha / 2) / sqrt(N - d - 3)),
+ * which is "p > alpha" of the two-sided test.  z = sqrt(N - d - 3) atanh(r) and p = erfc(|z| / sqrt 2) are
+ * formed on the host for reporting and never decided on.  A pivot <= 2^-40 (a singular or nearly singular
+ * conditioning block) makes the test DEGENERATE: r = z = p = NaN and the decision is dependent (the rule of a
+ * df == 0 result inside a group on the discrete path); degenerate tests are counted.
+ * The device's r equals the host twin's bit for bit on the same R (csrc/gci_elim.h is evaluated by both).
+ * Errors: a column with zero variance or a non-finite value is FBN_ERR_ARG at upload, naming the variable;
+ * N - d - 3 <= 0 and more than 32768 variables are FBN_ERR_LIMIT; alpha outside (0, 1) is FBN_ERR_ARG. */
+typedef struct fbn_cdataset fbn_cdataset;
+/* a CSV of reals: a header line of names, then one row of numbers per sample */
+int fbn_cdataset_load_csv(const char *path, fbn_cdataset **out);
+int fbn_cdataset_shape(const fbn_cdataset *ds, int *nvars, int64_t *nsamples);
+int fbn_cdataset_columns(const fbn_cdataset *ds, double *cols /* [nvars][nsamples] */);
+int fbn_cdataset_var_name(const fbn_cdataset *ds, int v, char *buf, int cap);
+int fbn_cdataset_destroy(fbn_cdataset *ds);
+
+typedef struct fbn_gci_ctx fbn_gci_ctx;
+/* cols: float64 [nvars][nsamples], variable-major like the discrete store; copied to `device`, where R is
+ * computed at once (and the columns checked).  fbn_gci_from_device: the columns are already in that device's memory. */
+int fbn_gci_upload(const double *cols, int nvars, int64_t nsamples, int device, fbn_gci_ctx **out);
+int fbn_gci_from_device(const double *d_cols, int nvars, int64_t nsamples, int device, fbn_gci_ctx **out);
+/* R [nvars][nvars] copied out: symmetric exactly, unit diagonal exactly */
+int fbn_gci_corr(fbn_gci_ctx *c, double *R);
+/* n tests, items [n][2 + d] = (x, y, z_0 .. z_{d-1}) as fbn_ci_run takes them.  r, z, p, indep [n] and
+ * degenerate (the count) may each be NULL. */
+int fbn_gci_run(fbn_gci_ctx *c, const int32_t *items, int64_t n, int d, double alpha, double *r, double *z, double *p,
+                uint8_t *indep, int64_t *degenerate);
+/* PC-stable with the reference's sequential semantics (group size 1) and orientation; the result is an
+ * ordinary fbn_pc_result: every fbn_pc_* accessor applies.  Its decision margin is the smallest | |r| - tau_d |
+ * over the non-degenerate tests and the number of them within 1e-9. */
+int fbn_gci_pc_stable(fbn_gci_ctx *c, double alpha, int depth, fbn_pc_result **out);
+/* degenerate tests of a Gaussian run (0 for a discrete one) */
+int fbn_pc_degenerate(const fbn_pc_result *r, int64_t *n);
+/* split_k = sample slices of the Gram (0 = automatic: about sixteen workgroups per CU; clipped to the number of
+ * 32-sample stages), tile = 32 or 64 variables per output tile edge (0 = automatic).  R is recomputed at once.
+ * For a given (tile, split_k) R is the same bits from run to run; different settings may differ in the last bits. */
+int fbn_gci_set_tuning(fbn_gci_ctx *c, int32_t split_k, int32_t tile);
+/* out = {tile, split_k of the resident R, slab bytes, degenerate tests of the last fbn_gci_run / fbn_gci_pc_stable} */
+int fbn_gci_info(const fbn_gci_ctx *c, int64_t out[4]);
+/* kernel time of the last launch group: the three correlation kernels, a test batch, or a PC run's batches */
+int fbn_gci_last_kernel_ms(const fbn_gci_ctx *c, float *ms);
+/* of the last computation of R: column means, Gram, reduce */
+int fbn_gci_corr_kernel_ms(const fbn_gci_ctx *c, float ms[3]);
+int fbn_gci_ctx_destroy(fbn_gci_ctx *c);
+/* Host twins: the same tests and the same driver on the CPU over a correlation matrix R [nvars][nvars] the
+ * caller hands in (every entry finite).  Given fbn_gci_corr's R they repeat the device's r, decisions, counts
+ * and sepsets bit for bit. */
+int fbn_gci_host_run(const double *R, int nvars, int64_t nsamples, const int32_t *items, int64_t n, int d, double alpha,
+                     double *r, double *z, double *p, uint8_t *indep, int64_t *degenerate);
+int fbn_gci_host_pc_stable(const double *R, int nvars, int64_t nsamples, double alpha, int depth, fbn_pc_result **out);
+/* tau_d of (alpha, nsamples, d) as both paths use it */
+int fbn_gci_tau(double alpha, int64_t nsamples, int d, double *tau);
+
 #ifdef __cplusplus
 }
 #endif
