@@ -40,6 +40,9 @@ reference's names and argument meaning:
   up to 26 variables, by dynamic programming over variable subsets on the device (no reference counterpart)
 * ``ArcPosterior(score, max_parents, allowed, prior).learn(source)`` -- exact arc posteriors P(u -> v | data) by
   Bayesian model averaging over all DAGs, the same lattices in the log-sum-exp semiring (no reference counterpart)
+* ``OrderMCMC(score, max_parents, allowed, prior, chains, burn_in, thin, samples, seed).learn(source)`` -- the same
+  arc posteriors for up to 64 variables by Metropolis-Hastings over node orders, one chain per wave on the device,
+  bit-identical to a host twin (no reference counterpart)
 * ``PCStable(alpha, depth).StructLearnCompData(ContinuousDataset(...))`` -- PC-stable on real-valued columns with the
   Fisher-z test of the partial correlation; ``GaussianIndependenceTest(dataset, alpha)`` holds the correlation matrix
   on the device (the reference's ContinuousNode has no learner)
@@ -69,6 +72,7 @@ from .api import (  # noqa: F401
     HillClimbing,
     ExactSearch,
     ArcPosterior,
+    OrderMCMC,
     ContinuousDataset,
     GaussianIndependenceTest,
     gci_host_run,
@@ -91,6 +95,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "ArcPosterior", "ContinuousDataset", "GaussianIndependenceTest", "gci_host_run", "gci_host_pc_stable", "gci_tau", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "ArcPosterior", "OrderMCMC", "ContinuousDataset", "GaussianIndependenceTest", "gci_host_run", "gci_host_pc_stable", "gci_tau", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

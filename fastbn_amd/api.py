@@ -217,6 +217,16 @@ _SIGS = {
     "fbn_bma_set_tuning": [_vp, _i32],
     "fbn_bma_lse_exp": [_dbl, _vp],
     "fbn_bma_lse": [_dbl, _dbl, _vp],
+    "fbn_omcmc_run": [_vp, _vp, _i32, _vp, _pp],
+    "fbn_omcmc_run_bd": [_vp, _vp, _i32, _vp, _vp, _pp],
+    "fbn_omcmc_run_host": [C.c_int, _vp, _vp, _i64, _vp, _i32, _vp, _pp],
+    "fbn_omcmc_run_bd_host": [C.c_int, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _pp],
+    "fbn_omcmc_result_info": [_vp, _vp],
+    "fbn_omcmc_result_arcs": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "fbn_omcmc_result_destroy": [_vp],
+    "fbn_omcmc_set_tuning": [_vp, _i32, _i64],
+    "fbn_omcmc_order_terms": [_vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp],
+    "fbn_omcmc_order_terms_host": [C.c_int, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp],
     "fbn_cdataset_load_csv": [_cstr, _pp],
     "fbn_cdataset_shape": [_vp, _vp, _vp],
     "fbn_cdataset_columns": [_vp, _vp],
@@ -1525,6 +1535,108 @@ class ArcPosterior:
     def set_tuning(ci, tile_bits=0):
         """fbn_bma_set_tuning on a context: bits per pass of the three transforms; 0 = default."""
         lib.fbn_bma_set_tuning(ci._h, int(tile_bits))
+
+
+class _OmcmcOptions(C.Structure):
+    _fields_ = [("chains", C.c_int32), ("samples", C.c_int32), ("burn_in", C.c_int64), ("thin", C.c_int64),
+                ("seed", C.c_uint64), ("chain_offset", C.c_int64), ("max_families", C.c_int64)]
+
+
+class _OmcmcInfo(C.Structure):
+    _fields_ = [("nvars", C.c_int32), ("prior", C.c_int32), ("chains", C.c_int32), ("samples", C.c_int32),
+                ("chains_per_group", C.c_int32), ("launches", C.c_int32), ("burn_in", C.c_int64), ("thin", C.c_int64),
+                ("steps", C.c_int64), ("steps_per_launch", C.c_int64), ("families", C.c_int64),
+                ("family_bytes", C.c_int64), ("families_scored", C.c_int64), ("batches", C.c_int64),
+                ("score_kernel_ms", C.c_double), ("chain_kernel_ms", C.c_double), ("score_wall_ms", C.c_double),
+                ("upload_wall_ms", C.c_double), ("chain_wall_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+class OrderMCMC:
+    """Arc posteriors for up to 64 variables by MCMC over node orders (fbn_omcmc_run; Friedman & Koller 2003; no
+    reference counterpart): Metropolis-Hastings chains whose stationary arc probabilities are ArcPosterior's
+    arc_prob, under the same scores, candidates (max_parents, max_family_cells, allowed) and order-modular prior
+    ("uniform" / "indegree").  One chain per wave on the device; `chains` independent chains start from seeded
+    random orders, discard burn_in steps and then take `samples` samples `thin` steps apart.  chain_offset numbers
+    the chains within the seed's stream, so two runs of 35 chains at offsets 0 and 35 are one run of 70;
+    max_families caps the family lists (0: 2^26 entries).
+
+    learn(source, host=False) is ArcPosterior's (`.ci` is shared the same way; host=True runs the host twin,
+    bit-identical, without a device).  Results: .arc_prob [n][n], .skeleton_prob, .chain_arc_prob [chains][n][n]
+    (the chains are independent: their spread gives .arc_se, the standard error of arc_prob), .orders [chains][n]
+    (the last orders), .log_score [chains][samples] (the order's log score L at every sample), .accept_rate
+    [chains], .info.  order_terms(orders, source, host) is a testing entry: the sampler's scan on given orders."""
+
+    PRIORS = ArcPosterior.PRIORS
+
+    def __init__(self, score="bde", max_parents=3, max_family_cells=0, allowed=None, prior=0, chains=64, burn_in=2000,
+                 thin=20, samples=200, seed=0, device=0, chain_offset=0, max_families=0):
+        self.score_name, self.device = score, device
+        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
+        self.prior = self.PRIORS.get(prior, prior)
+        self.chains, self.burn_in, self.thin, self.samples, self.seed = chains, burn_in, thin, samples, seed
+        self.chain_offset, self.max_families = chain_offset, max_families
+        self.ci = None
+
+    _options = ExactSearch._options
+
+    def _source(self, source, host):
+        """(leading arguments of the entry, number of samples): a Dataset's arrays for the twin, else the context"""
+        if host:
+            return (source.num_vars, _p(source.dims), _p(source.columns), source.num_instance), source.num_instance
+        source = self.ci if source is None else source
+        self.ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
+        return (self.ci._h,), self.ci.num_samples
+
+    def learn(self, source, host=False):
+        r = C.c_void_p()
+        bd = _bd_score(self.score_name)
+        m = _OmcmcOptions(int(self.chains), int(self.samples), int(self.burn_in), int(self.thin), int(self.seed),
+                          int(self.chain_offset), int(self.max_families))
+        lead, nsamples = self._source(source, host)
+        o, keep = self._options(nsamples)
+        name = "fbn_omcmc_run" + ("_bd" if bd is not None else "") + ("_host" if host else "")
+        args = (C.byref(o), int(self.prior)) + ((C.byref(bd),) if bd is not None else ()) + (C.byref(m), C.byref(r))
+        getattr(lib, name)(*lead, *args)
+        del keep
+        try:
+            info = _OmcmcInfo()
+            lib.fbn_omcmc_result_info(r, C.byref(info))
+            n, ch = info.nvars, info.chains
+            self.arc_prob, self.chain_arc_prob = np.zeros((n, n)), np.zeros((ch, n, n))
+            self.orders, self.log_score = np.zeros((ch, n), np.int32), np.zeros((ch, info.samples))
+            accepted = np.zeros(ch, np.int64)
+            lib.fbn_omcmc_result_arcs(r, _p(self.arc_prob), _p(self.chain_arc_prob), _p(self.orders), _p(self.log_score),
+                                      _p(accepted))
+        finally:
+            lib.fbn_omcmc_result_destroy(r)
+        self.accepted = accepted
+        self.accept_rate = accepted / float(info.steps)
+        self.skeleton_prob = self.arc_prob + self.arc_prob.T
+        self.arc_se = self.chain_arc_prob.std(axis=0, ddof=1) / np.sqrt(ch) if ch > 1 else np.full((n, n), np.inf)
+        self.info = {k: getattr(info, k) for k, _ in _OmcmcInfo._fields_}
+        return self
+
+    def order_terms(self, orders, source=None, host=False):
+        """fbn_omcmc_order_terms(_host): (term [k][n], arcs [k][n][n]) of the orders [k][n] -- term[i][v] the log-sum-exp
+        of v's candidate parent sets within its predecessors in order i, arcs[i][u][v] = P(u -> v | order i).  source
+        as learn's; None: the context of the last learn."""
+        od = np.ascontiguousarray(orders, np.int32)
+        k, n = od.shape
+        term, arcs = np.zeros((k, n)), np.zeros((k, n, n))
+        bd = _bd_score(self.score_name)
+        lead, nsamples = self._source(source, host)
+        o, keep = self._options(nsamples)
+        getattr(lib, "fbn_omcmc_order_terms" + ("_host" if host else ""))(
+            *lead, C.byref(o), int(self.prior), C.byref(bd) if bd is not None else None, int(self.max_families), _p(od), k,
+            _p(term), _p(arcs))
+        del keep
+        return term, arcs
+
+    @staticmethod
+    def set_tuning(ci, chains_per_group=0, steps_per_launch=0):
+        """fbn_omcmc_set_tuning on a context: chains (waves) per workgroup, 1 .. 16, and steps per kernel launch;
+        0 = default.  The same bits either way."""
+        lib.fbn_omcmc_set_tuning(ci._h, int(chains_per_group), int(steps_per_launch))
 
 
 def score_marginals(network, marginals, golden):

@@ -199,6 +199,8 @@ struct fbn_ci_ctx {
     int64_t hc_chunk = 0;
     int exact_tile_bits = 0;  // fbn_exact_set_tuning (capi_exact.hip): bits per transform pass, 0 = default
     int bma_tile_bits = 0;    // fbn_bma_set_tuning (capi_bma.hip): likewise for the arc-posterior transforms
+    int omcmc_group = 0;      // fbn_omcmc_set_tuning (capi_omcmc.hip): chains per workgroup, 0 = default
+    int64_t omcmc_steps_per_launch = 0;  // steps per chain-kernel launch, 0 = all in one
     ~fbn_ci_ctx() {
         if (h_open) (void)hipHostFree(h_open);
         if (h_margin) (void)hipHostFree(h_margin);

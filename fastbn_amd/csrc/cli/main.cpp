@@ -28,6 +28,10 @@
 // -a 18, this build's own: exact arc posteriors on -a 17's inputs and flags (--prior uniform|indegree, default
 // uniform): P(u -> v | data) for every arc by Bayesian model averaging on the same subset lattices; prints logZ
 // and the arcs with posterior >= 0.5, one per line; --out writes the full matrix, row u = the arcs out of u;
+// -a 20, this build's own: the same arc posteriors for up to 64 variables by MCMC over node orders, on -a 18's
+// inputs and flags (--max-parents defaults to 3 here) plus -q chains (default 64), -m burn-in steps (2000), -l samples
+// per chain (200), --thin steps between samples (20), --seed; prints the arcs with posterior >= 0.5, the mean
+// acceptance rate and the largest between-chain standard error of an arc; --out writes the full matrix as -a 18.
 // -a 19, this build's own: PC-stable on continuous data: -f2 is a CSV of reals (a header line, then rows of numbers);
 // Fisher-z tests of the partial correlation at alpha 0.05, --depth as -a 0; prints -a 0's lines (tests per level,
 // remaining edges, SHD against -f1 when given); --out FILE writes the learned PDAG, one edge per line: from, to, 1
@@ -37,6 +41,7 @@
 // as LIBSVM, the -q rows of a case one after the other (label = the value of variable 0).
 // -a 16, this build's own: Gibbs sampling on -a 10's inputs and flags: -q chains per case, -m burn-in sweeps,
 // -l counted sweeps (their defaults are -a 10's: 10000, 10, 2500), --seed; prints -a 10's result lines.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -57,7 +62,8 @@ int main(int argc, char **argv) {
     std::string out_file, score_name = "bic", prior_name = "uniform";
     int max_parents = -1;
     double iss = 1.0;
-    bool ref_given = false, iss_given = false;
+    bool ref_given = false, iss_given = false, q_given = false, m_given = false, l_given = false;
+    long long thin = 20;
     std::string net_file = "alarm/alarm.xml", ref_net_file = "alarm/alarm.bif",
                 train_set_file = "alarm/alarm_s5000.txt", test_set_file = "alarm/testing_alarm_1k_p20",
                 pt_file = "alarm/alarm_1k_pt", prefix = "../dataset/";
@@ -77,22 +83,23 @@ int main(int argc, char **argv) {
         if (a == "--iss" && i + 1 < argc) { iss = atof(argv[++i]); iss_given = true; continue; }
         if (a == "--max-parents" && i + 1 < argc) { max_parents = atoi(argv[++i]); continue; }
         if (a == "--prior" && i + 1 < argc) { prior_name = argv[++i]; continue; }
+        if (a == "--thin" && i + 1 < argc) { thin = atoll(argv[++i]); continue; }
         switch (argv[i][1]) {
         case 'h':
-            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17|18|19] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
+            std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17|18|19|20] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
-                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--prior uniform|indegree] "
+                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--prior uniform|indegree] [--thin T] "
                          "[--out FILE] [--prefix DIR]"
                       << std::endl;
             return 0;
         case 'a': algorithm = atoi(argv[++i]); break;
         case 't': num_threads = atoi(argv[++i]); break;
         case 'g': group_size = atoi(argv[++i]); break;
-        case 'q': num_samples = atoll(argv[++i]); break;
+        case 'q': num_samples = atoll(argv[++i]); q_given = true; break;
         case 'd': propagation_length = atoi(argv[++i]); break;  // src/Parameter.cpp:40
-        case 'm': max_updating = atoll(argv[++i]); break;       // src/Parameter.cpp:38
-        case 'l': updating_interval = atoll(argv[++i]); break;  // src/Parameter.cpp:39
+        case 'm': max_updating = atoll(argv[++i]); m_given = true; break;      // src/Parameter.cpp:38
+        case 'l': updating_interval = atoll(argv[++i]); l_given = true; break;  // src/Parameter.cpp:39
         case 'f':
             switch (argv[i][2]) {
             case '0': net_file = argv[++i]; break;
@@ -644,6 +651,102 @@ int main(int argc, char **argv) {
         }
         fbn_bma_result_destroy(res);
         if (ctx) fbn_ci_ctx_destroy(ctx);
+    } else if (algorithm == 20) {
+        // order MCMC: no counterpart in the reference
+        const long long chains = q_given ? num_samples : 64, burn_in = m_given ? max_updating : 2000,
+                        samples = l_given ? updating_interval : 200;
+        if (max_parents < 0) max_parents = 3;
+        std::cout << "===============================" << std::endl
+                  << "Algorithm: arc posteriors by MCMC over node orders, #threads = " << num_threads << std::endl
+                  << "score = " << score_name << ", max parents = " << max_parents << ", prior = " << prior_name << std::endl
+                  << "chains = " << chains << ", burn-in = " << burn_in << ", samples = " << samples << ", thin = " << thin
+                  << ", seed = " << seed << std::endl
+                  << "\tsample set: " << train_set_file << std::endl
+                  << "===============================" << std::endl;
+        auto die = [] {
+            fprintf(stderr, "Error: %s\n", fbn_last_error());
+            return 1;
+        };
+        if (prior_name != "uniform" && prior_name != "indegree") {
+            fprintf(stderr, "Error: --prior is uniform or indegree, not %s\n", prior_name.c_str());
+            return 1;
+        }
+        if (chains < 1 || chains > 0x7fffffffLL || samples < 1 || samples > 0x7fffffffLL) {
+            fprintf(stderr, "Error: -q chains and -l samples are 1 .. 2^31 - 1\n");
+            return 1;
+        }
+        const int32_t prior = prior_name == "indegree";
+        fbn_dataset *ds = nullptr;
+        if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
+        int n = 0;
+        int64_t ns = 0;
+        fbn_dataset_shape(ds, &n, &ns);
+        std::vector<int32_t> dims((size_t)n);
+        std::vector<uint8_t> cols((size_t)n * (size_t)ns);
+        fbn_dataset_dims(ds, dims.data());
+        fbn_dataset_columns(ds, cols.data());
+        fbn_dataset_destroy(ds);
+        const bool is_bd = score_name == "bde" || score_name == "k2";
+        if (iss_given && score_name != "bde") {
+            fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
+            return 1;
+        }
+        const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+        fbn_exact_options xopt{};
+        if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &xopt.penalty)) return die();
+        xopt.max_parents = max_parents;
+        const fbn_omcmc_options mopt{(int32_t)chains, (int32_t)samples, burn_in, thin, seed, 0, 0};
+        fbn_omcmc_result *res = nullptr;
+        fbn_ci_ctx *ctx = nullptr;
+        if (device < 0) {
+            if (is_bd ? fbn_omcmc_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, prior, &bd, &mopt, &res)
+                      : fbn_omcmc_run_host(n, dims.data(), cols.data(), ns, &xopt, prior, &mopt, &res))
+                return die();
+        } else {
+            if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
+            if (is_bd ? fbn_omcmc_run_bd(ctx, &xopt, prior, &bd, &mopt, &res) : fbn_omcmc_run(ctx, &xopt, prior, &mopt, &res)) return die();
+        }
+        fbn_omcmc_info info;
+        fbn_omcmc_result_info(res, &info);
+        const size_t nn = (size_t)n * (size_t)n;
+        std::vector<double> P(nn), PC((size_t)chains * nn);
+        std::vector<int64_t> accepted((size_t)chains);
+        fbn_omcmc_result_arcs(res, P.data(), PC.data(), nullptr, nullptr, accepted.data());
+        char buf[160];
+        std::cout << "variables = " << n << ", samples = " << ns << std::endl << "arcs with posterior >= 0.5:" << std::endl;
+        for (int u = 0; u < n; ++u)
+            for (int v = 0; v < n; ++v)
+                if (P[(size_t)u * n + v] >= 0.5) {
+                    snprintf(buf, sizeof buf, "%d -> %d %.17g", u, v, P[(size_t)u * n + v]);
+                    std::cout << buf << std::endl;
+                }
+        double acc_sum = 0.0, se_max = 0.0;
+        for (long long c = 0; c < chains; ++c) acc_sum += (double)accepted[(size_t)c];
+        for (size_t e = 0; chains > 1 && e < nn; ++e) {  // the chains are independent: sd / sqrt(chains)
+            double ss = 0.0;
+            for (long long c = 0; c < chains; ++c) ss += (PC[(size_t)c * nn + e] - P[e]) * (PC[(size_t)c * nn + e] - P[e]);
+            se_max = std::max(se_max, std::sqrt(ss / (double)(chains - 1) / (double)chains));
+        }
+        snprintf(buf, sizeof buf, "acceptance rate = %.6g, largest standard error of an arc = %.6g", acc_sum / ((double)chains * (double)info.steps),
+                 se_max);
+        std::cout << buf << std::endl;
+        std::cout << "omcmc: " << info.families << " families in the lists (" << info.family_bytes << " bytes), scored in " << info.batches
+                  << " batches; " << info.steps << " steps per chain in " << info.launches << " launches; device kernel: scores "
+                  << info.score_kernel_ms * 1e-3 << " s, chains " << info.chain_kernel_ms * 1e-3 << " s; total " << info.wall_ms * 1e-3 << " s"
+                  << std::endl;
+        if (!out_file.empty()) {
+            FILE *f = fopen(out_file.c_str(), "w");
+            if (!f) {
+                fprintf(stderr, "Error: cannot write %s\n", out_file.c_str());
+                return 1;
+            }
+            for (int u = 0; u < n; ++u)
+                for (int v = 0; v < n; ++v) fprintf(f, "%.17g%c", P[(size_t)u * n + v], v + 1 < n ? ' ' : '\n');
+            fclose(f);
+            std::cout << "arc posteriors written to " << out_file << std::endl;
+        }
+        fbn_omcmc_result_destroy(res);
+        if (ctx) fbn_ci_ctx_destroy(ctx);
     } else if (algorithm == 19) {
         // PC-stable on continuous data: no counterpart in the reference (its ContinuousNode has no learner)
         std::cout << "===============================" << std::endl
@@ -812,7 +915,7 @@ int main(int argc, char **argv) {
         std::cout << "SISv1 is not defined by the reference (no code, no paper): not built.  Use -a 8 (SIS) or -a 10 (AIS-BN)."
                   << std::endl;
     } else if (algorithm >= 0 && algorithm <= 11) {
-        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16, 17, 18 and 19)." << std::endl;
+        std::cout << "This algorithm is not on the accelerated path of this build (only -a 0, 2, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16, 17, 18, 19 and 20)." << std::endl;
     } else {
         std::cout << "\tError! Please give the right value of -a to specify the functionality/algorithm" << std::endl;
     }

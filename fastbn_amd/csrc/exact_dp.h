@@ -78,6 +78,12 @@ int ExactCheck(int nvars, const int32_t *dims, const fbn_exact_options &opt);
 // (the exact search): the score as it is
 int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, int v, double *ls,
                      fbn_exact_info *info, const double *size_prior = nullptr);
+// The enumeration phase 1 runs, shared with the sparse family lists of the order sampler (order_mcmc.h): the
+// candidates of v by size and lexicographically within a size, as 64-bit masks over the n <= 64 variables, scored
+// in batches; sink(mask, score + size_prior[|mask|]) per candidate in that order.  scorer == nullptr: nothing is
+// scored and the sink is not called.  count (optional) is advanced by the number of candidates.
+int ExactEnumerate(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer *scorer, int v, fbn_exact_info *info,
+                   const double *size_prior, const std::function<void(uint64_t, double)> &sink, int64_t *count);
 // phase 4: the DAG from sink [2^n] and arg_at(v, index) = arg_v[index], the chosen families scored once
 // more for the node values; RV = R[V]
 int ExactTrace(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, const uint8_t *sink,

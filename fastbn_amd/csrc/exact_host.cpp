@@ -63,24 +63,23 @@ int ExactCheck(int nvars, const int32_t *dims, const fbn_exact_options &opt) {
     return FBN_OK;
 }
 
-int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, int v, double *ls,
-                     fbn_exact_info *info, const double *size_prior) {
+int ExactEnumerate(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer *scorer, int v, fbn_exact_info *info,
+                   const double *size_prior, const std::function<void(uint64_t, double)> &sink, int64_t *count) {
     const int64_t cap = CellCap(opt);
-    std::fill(ls, ls + ((size_t)1 << (n - 1)), -std::numeric_limits<double>::infinity());
     std::vector<int32_t> others;
     for (int x = 0; x < n; ++x)
         if (x != v && (!opt.allowed || opt.allowed[(size_t)x * n + v])) others.push_back(x);
     const int m = (int)others.size(), kmax = opt.max_parents < 0 ? m : std::min<int>(opt.max_parents, m);
     HcFamilies F;
     F.off.assign(1, 0);
-    std::vector<uint32_t> where;
+    std::vector<uint64_t> where;
     std::vector<double> sc;
     auto flush = [&]() -> int {
         if (F.cells.empty()) return FBN_OK;
         sc.resize(F.cells.size());
-        if (int rc = Score(scorer, F, nullptr, sc.data(), info)) return rc;
-        for (size_t f = 0; f < where.size(); ++f)  // squeezing keeps the size: popcount(where) parents
-            ls[where[f]] = size_prior ? sc[f] + size_prior[__builtin_popcount(where[f])] : sc[f];
+        if (int rc = Score(*scorer, F, nullptr, sc.data(), info)) return rc;
+        for (size_t f = 0; f < where.size(); ++f)
+            sink(where[f], size_prior ? sc[f] + size_prior[__builtin_popcountll(where[f])] : sc[f]);
         F.off.assign(1, 0);
         F.cols.clear(), F.cells.clear(), F.pen.clear(), where.clear();
         return FBN_OK;
@@ -93,17 +92,20 @@ int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, c
         for (int i = 0; i < k; ++i) pos[(size_t)i] = i;
         for (;;) {  // the k-subsets of `others` in lexicographic order
             int64_t cells = dims[v];
-            uint32_t S = 0;
+            uint64_t S = 0;
             for (int i = 0; i < k; ++i) {
                 ps[(size_t)i] = others[(size_t)pos[(size_t)i]];
-                S |= 1u << ps[(size_t)i];
+                S |= (uint64_t)1 << ps[(size_t)i];
                 if (cells <= cap) cells *= dims[ps[(size_t)i]];  // <= cap * 256: no wrap
             }
             if (cells <= cap || k == 0) {  // the empty set is always a candidate
-                Push(F, dims, opt.penalty, v, ps.data(), k, cells);
-                where.push_back(fbn_exact_squeeze(S, v));
-                if ((int64_t)where.size() == kExactBatch)
-                    if (int rc = flush()) return rc;
+                if (count) ++*count;
+                if (scorer) {
+                    Push(F, dims, opt.penalty, v, ps.data(), k, cells);
+                    where.push_back(S);
+                    if ((int64_t)where.size() == kExactBatch)
+                        if (int rc = flush()) return rc;
+                }
             }
             int i = k - 1;
             while (i >= 0 && pos[(size_t)i] == m - k + i) --i;
@@ -112,7 +114,15 @@ int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, c
             for (int j = i + 1; j < k; ++j) pos[(size_t)j] = pos[(size_t)j - 1] + 1;
         }
     }
-    return flush();
+    return scorer ? flush() : FBN_OK;
+}
+
+int ExactLocalScores(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, int v, double *ls,
+                     fbn_exact_info *info, const double *size_prior) {
+    std::fill(ls, ls + ((size_t)1 << (n - 1)), -std::numeric_limits<double>::infinity());
+    // squeezing keeps the size: the prior's term was chosen by the parents' number
+    return ExactEnumerate(n, dims, opt, &scorer, v, info, size_prior,
+                          [&](uint64_t S, double score) { ls[fbn_exact_squeeze((uint32_t)S, v)] = score; }, nullptr);
 }
 
 int ExactTrace(int n, const int32_t *dims, const fbn_exact_options &opt, const HcScorer &scorer, const uint8_t *sink,

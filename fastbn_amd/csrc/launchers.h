@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, gci_corr.hip, gci_test.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, order_mcmc.hip, gci_corr.hip, gci_test.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -211,6 +211,16 @@ extern "C" hipError_t fbn_bma_level_launch(const BmaLevelArgs *a, hipStream_t st
 // nvars * nvars + nvars + 2 doubles
 extern "C" hipError_t fbn_bma_gather_launch(const double *q, const double *F, const double *B, int nvars, double *out,
                                             hipStream_t stream);
+// The order-MCMC kernels (order_mcmc.hip; order_mcmc.h's arguments): a->group chains (one wave each) per
+// workgroup, fbn_omcmc_wave_lds_bytes() of dynamic LDS per wave.  fbn_omcmc_chain_launch: the steps [a->t0, a->t1)
+// of every chain; fbn_omcmc_terms_launch: the terms and arc features of a->k given orders, one wave each.
+namespace fbn {
+struct OmcmcDeviceArgs;
+struct OmcmcTermsArgs;
+}
+extern "C" size_t fbn_omcmc_wave_lds_bytes(void);
+extern "C" hipError_t fbn_omcmc_chain_launch(const fbn::OmcmcDeviceArgs *a, hipStream_t stream);
+extern "C" hipError_t fbn_omcmc_terms_launch(const fbn::OmcmcTermsArgs *a, hipStream_t stream);
 // The correlation kernels of the Gaussian CI test (gci_corr.hip) over X float64 [nvars][N].
 // fbn_gci_means_launch: mean[v] and bad[v] (the column holds a non-finite value).  fbn_gci_gram_launch: the
 // centred Gram's upper tiles of tile x tile variables (64 or 32) in split_k sample slices of whole stages

@@ -1307,6 +1307,99 @@ int fbn_bma_set_tuning(fbn_ci_ctx *c, int32_t tile_bits);
 int fbn_bma_lse_exp(double x, double *y);
 int fbn_bma_lse(double a, double b, double *y);
 
+/* ------------------------------------------------------------------ order MCMC: arc posteriors for up to 64 variables
+ * The same posterior as fbn_bma_run, sampled instead of summed: Metropolis-Hastings over linear orders (Friedman &
+ * Koller 2003) (-a 20).  Under the order-modular prior above, P(order | data) is proportional to
+ * exp sum_v (+)_{P within pred(v)} s_v(P), with the same local scores, candidates, options record and priors, so
+ * the chains' stationary arc probabilities are fbn_bma_run's arc_prob -- for up to 26 variables the exact value
+ * the sampler converges to.  The device path is held bit for bit to a host twin.
+ *
+ * Variables and families.  n <= 64; a parent set is a 64-bit mask (bit x = variable x).  The FAMILY LIST of v holds
+ * every candidate parent set of v (fbn_exact_run's sense), enumerated by size and lexicographically within a size,
+ * as (mask, score): score = the scorer's value plus the prior's term of |P|.  The empty set is entry 0.  The lists
+ * are built once through the family scorer; their total is capped (max_families; 2^26 by default) and, on the
+ * device, sized against the free memory: past either is FBN_ERR_LIMIT, the message carrying the count.
+ *
+ * Order terms.  An order is a permutation, pred(v) the mask of the variables before v; an entry is CONSISTENT when
+ * (mask & ~pred(v)) == 0.  With m the largest consistent score and the consistent entries ranked r = 0, 1, .. in
+ * list order,
+ *   term_v = m + ln(S),  S = the sum of e^(s - m): slot l of 64 adds the entries of rank r = l (mod 64) ascending
+ *            from 0.0, then the slots are summed by the butterfly x[i] += x[i ^ off], off = 32, 16, .., 1;
+ *   L      = the sum of term_v, v ascending, from 0.0.
+ * e^x and ln are csrc/exact_lse.h's fbn_lse_exp and csrc/hc_bd.h's fbn_bd_ln on both sides.  The summation order
+ * is part of the definition and independent of any tuning.
+ *
+ * Chain c of a run is chain g = chain_offset + c of the seed.  It starts from a seeded random permutation and at
+ * step t proposes to swap the nodes at two distinct positions i < j drawn uniformly; only the terms of the nodes at
+ * positions i .. j are recomputed; with delta = L' - L the move is accepted iff delta >= 0 or u < e^delta, u a
+ * 53-bit uniform.  The generator is numpy's PCG64 of the seed; the start permutation reads positions
+ * (g << 40) + k, step t (0-based) positions (g << 40) + 64 + 3 t .. + 2 (i and j, then u), whether the move is
+ * accepted or not: a pure function of (seed, g, t), so splitting the chains over calls changes nothing.
+ *
+ * Samples are taken after step burn_in + thin, burn_in + 2 thin, .., `samples` per chain.  At a sample, for every v
+ * and u in pred(v),  P(u -> v | order) = the sum, in list order from 0.0, of e^(s - term_v) over the consistent
+ * entries holding u.  chain_arc_prob[c][u][v] is the sum of these over the chain's samples, in sample order, divided
+ * by `samples`; arc_prob the sum of chain_arc_prob over the chains, in chain order, divided by `chains`.  The
+ * chains are independent: the standard error of arc_prob is the chains' standard deviation / sqrt(chains).
+ *
+ * Limits: chain_offset + chains <= 2^23, burn_in + thin * samples < 2^38 - 64: FBN_ERR_LIMIT.  chains, samples or
+ * thin < 1, a negative burn_in, chain_offset or max_families, an unknown prior: FBN_ERR_ARG.  More than 64
+ * variables: FBN_ERR_LIMIT.  No result is left behind by a failing call. */
+typedef struct fbn_omcmc_options {
+    int32_t chains, samples;   /* >= 1 */
+    int64_t burn_in, thin;     /* >= 0, >= 1 */
+    uint64_t seed;
+    int64_t chain_offset;      /* >= 0 */
+    int64_t max_families;      /* cap on the list entries of all nodes; 0: 2^26 */
+} fbn_omcmc_options;
+
+typedef struct fbn_omcmc_info {
+    int32_t nvars, prior, chains, samples;
+    int32_t chains_per_group, launches;  /* waves per workgroup, chain-kernel launches (0 on the host twin) */
+    int64_t burn_in, thin, steps;        /* steps = burn_in + thin * samples, per chain */
+    int64_t steps_per_launch;            /* 0 on the host twin */
+    int64_t families, family_bytes;      /* list entries of all nodes; 16 bytes each */
+    int64_t families_scored, batches;    /* the scorer's counters */
+    double score_kernel_ms, chain_kernel_ms; /* device time (0 on the host twin) */
+    double score_wall_ms, upload_wall_ms, chain_wall_ms, wall_ms;
+} fbn_omcmc_info;
+
+typedef struct fbn_omcmc_result fbn_omcmc_result;
+
+/* options, prior and bd as fbn_bma_run's / fbn_bma_run_bd's; the context's resident column store */
+int fbn_omcmc_run(fbn_ci_ctx *c, const fbn_exact_options *options, int32_t prior, const fbn_omcmc_options *mcmc,
+                  fbn_omcmc_result **out);
+int fbn_omcmc_run_bd(fbn_ci_ctx *c, const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd,
+                     const fbn_omcmc_options *mcmc, fbn_omcmc_result **out);
+/* The host twin: the same definitions in plain loops over the host scorer.  No device. */
+int fbn_omcmc_run_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                       const fbn_exact_options *options, int32_t prior, const fbn_omcmc_options *mcmc,
+                       fbn_omcmc_result **out);
+int fbn_omcmc_run_bd_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                          const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd,
+                          const fbn_omcmc_options *mcmc, fbn_omcmc_result **out);
+int fbn_omcmc_result_info(const fbn_omcmc_result *r, fbn_omcmc_info *info);
+/* arc_prob [nvars][nvars] (arc_prob[u * nvars + v] = P(u -> v | data), zero diagonal); chain_arc_prob
+ * [chains][nvars][nvars]; orders int32 [chains][nvars], every chain's last order; log_score [chains][samples], L at
+ * every sample; accepted int64 [chains], the accepted steps.  Any may be NULL. */
+int fbn_omcmc_result_arcs(const fbn_omcmc_result *r, double *arc_prob, double *chain_arc_prob, int32_t *orders,
+                          double *log_score, int64_t *accepted);
+int fbn_omcmc_result_destroy(fbn_omcmc_result *r);
+/* chains_per_group: chains (waves) of one workgroup, 1 .. 16; steps_per_launch: steps of one kernel launch, the
+ * orders parked in device memory between launches; 0 = default (4; all steps in one launch).  Any values give the
+ * same bits: a tuning/testing entry. */
+int fbn_omcmc_set_tuning(fbn_ci_ctx *c, int32_t chains_per_group, int64_t steps_per_launch);
+/* Testing entries: the sampler's scan on given orders, no chain.  orders int32 [k][nvars] (permutations, else
+ * FBN_ERR_ARG) -> term [k][nvars] (term_v of order i at term[i * nvars + v]) and arcs [k][nvars][nvars]
+ * (P(u -> v | order i) at arcs[(i * nvars + u) * nvars + v], 0 outside pred(v)).  bd may be NULL (the penalised
+ * score of options->penalty); max_families as above, 0 = default.  The first runs the kernel's scan over the
+ * context's column store, the second the twin's. */
+int fbn_omcmc_order_terms(fbn_ci_ctx *c, const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd,
+                          int64_t max_families, const int32_t *orders, int64_t k, double *term, double *arcs);
+int fbn_omcmc_order_terms_host(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples,
+                               const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd,
+                               int64_t max_families, const int32_t *orders, int64_t k, double *term, double *arcs);
+
 /* ------------------------------------------------------------------ PC-stable on continuous data (Gaussian CI test)
  * Structure learning from real-valued columns with the Fisher-z test of the partial correlation (Kalisch &
  * Buehlmann 2007) (-a 19).  The sufficient statistic is the correlation matrix R of the columns, computed once
