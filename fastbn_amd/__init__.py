@@ -46,6 +46,11 @@ reference's names and argument meaning:
 * ``PCStable(alpha, depth).StructLearnCompData(ContinuousDataset(...))`` -- PC-stable on real-valued columns with the
   Fisher-z test of the partial correlation; ``GaussianIndependenceTest(dataset, alpha)`` holds the correlation matrix
   on the device (the reference's ContinuousNode has no learner)
+* ``GaussianParameterLearning(source).LearnParamsKnowStructCompData(parents)`` -- the maximum-likelihood
+  ``GaussianNetwork`` (linear-Gaussian: intercepts, coefficients, residual variances) of a learned structure, and
+  ``GaussianInference(network).infer(evidence)`` -- exact posterior means, variances and log densities of batches of
+  cases (NaN = unobserved), one workgroup per case on the device, bit-identical to a host twin (no reference
+  counterpart)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """
@@ -75,6 +80,10 @@ from .api import (  # noqa: F401
     OrderMCMC,
     ContinuousDataset,
     GaussianIndependenceTest,
+    GaussianNetwork,
+    GaussianParameterLearning,
+    GaussianInference,
+    gnet_learn_host,
     gci_host_run,
     gci_host_pc_stable,
     gci_tau,
@@ -95,6 +104,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["FastBNError", "Network", "Dataset", "JunctionTree", "JunctionForest", "IndependenceTest", "PCStable", "PCResult", "ParameterLearning",
-           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "ArcPosterior", "OrderMCMC", "ContinuousDataset", "GaussianIndependenceTest", "gci_host_run", "gci_host_pc_stable", "gci_tau", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
+           "Sampler", "LikelihoodWeighting", "LoopyBeliefPropagation", "EPISBN", "AISBN", "SelfImportanceSampling", "MostProbableExplanation", "ExpectationMaximization", "PosteriorSampler", "GibbsSampling", "HillClimbing", "ExactSearch", "ArcPosterior", "OrderMCMC", "ContinuousDataset", "GaussianIndependenceTest", "GaussianNetwork", "GaussianParameterLearning", "GaussianInference", "gnet_learn_host", "gci_host_run", "gci_host_pc_stable", "gci_tau", "family_scores", "hc_penalty", "hc_table_bytes", "score_marginals",
            "family_sizes", "pdag_to_dag", "orient_skeleton", "shd_bif",
            "lib", "load_libsvm", "write_csv", "write_libsvm", "device_count", "kernel_options"]

@@ -246,6 +246,19 @@ _SIGS = {
     "fbn_gci_host_run": [_vp, C.c_int, _i64, _vp, _i64, C.c_int, _dbl, _vp, _vp, _vp, _vp, _vp],
     "fbn_gci_host_pc_stable": [_vp, C.c_int, _i64, _dbl, C.c_int, _pp],
     "fbn_gci_tau": [_dbl, _i64, C.c_int, _vp],
+    "fbn_gnet_create": [C.c_int, _vp, _vp, _vp, _vp, _vp, _pp],
+    "fbn_gnet_learn": [_vp, _vp, _vp, _pp],
+    "fbn_gnet_learn_host": [C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _pp],
+    "fbn_gnet_params": [_vp, _vp, _vp, _vp],
+    "fbn_gnet_joint": [_vp, _vp, _vp],
+    "fbn_gnet_destroy": [_vp],
+    "fbn_ginf_create": [_vp, C.c_int, _pp],
+    "fbn_ginf_run": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "fbn_ginf_run_device": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "fbn_ginf_set_tuning": [_vp, _i32],
+    "fbn_ginf_info": [_vp, _vp],
+    "fbn_ginf_last_kernel_ms": [_vp, _vp],
+    "fbn_ginf_destroy": [_vp],
 }
 
 
@@ -306,8 +319,8 @@ lib = _Lib()
 _LIVE = weakref.WeakSet()
 _CLOSE_ORDER = {"PCResult": 0, "PCDistSession": 1, "JunctionTree": 2, "Sampler": 2, "LikelihoodWeighting": 2,
                 "LoopyBeliefPropagation": 2, "EPISBN": 2, "AISBN": 2, "SelfImportanceSampling": 2, "MostProbableExplanation": 2,
-                "ExpectationMaximization": 2, "PosteriorSampler": 2, "GibbsSampling": 2,
-                "IndependenceTest": 3, "GaussianIndependenceTest": 3, "Dataset": 4, "Network": 5}
+                "ExpectationMaximization": 2, "PosteriorSampler": 2, "GibbsSampling": 2, "GaussianInference": 2,
+                "IndependenceTest": 3, "GaussianIndependenceTest": 3, "Dataset": 4, "Network": 5, "GaussianNetwork": 5}
 
 
 def _register(obj):
@@ -1176,6 +1189,119 @@ class ParameterLearning:
 
     def last_kernel_ms(self):
         return self.ci.last_kernel_ms()
+
+
+class GaussianNetwork(_Handle):
+    """A linear-Gaussian network (fbn_gnet): X_v = intercept[v] + sum_k coef[v][k] X_parents[v][k] + N(0,
+    variance[v]).  `coef` is a list of lists aligned with `parents`, or flat in the same order."""
+
+    _destroy = "fbn_gnet_destroy"
+
+    def __init__(self, parents=None, intercept=None, coef=None, variance=None, names=None, _handle=None):
+        self.parents = [[int(q) for q in ps] for ps in parents]
+        self.num_nodes = len(self.parents)
+        self.names = list(names) if names is not None else [str(i) for i in range(self.num_nodes)]
+        self._off, self._par = _csr_parents(self.parents, self.num_nodes)
+        if _handle is None:
+            flat = [float(w) for ws in coef for w in (ws if np.ndim(ws) else [ws])]
+            if len(flat) != int(self._off[-1]):
+                raise FastBNError(f"{len(flat)} coefficients for {int(self._off[-1])} parents")
+            b = np.ascontiguousarray(intercept, np.float64)
+            s = np.ascontiguousarray(variance, np.float64)
+            if len(b) != self.num_nodes or len(s) != self.num_nodes:
+                raise FastBNError(f"intercept and variance: one value for each of the {self.num_nodes} nodes")
+            _handle = C.c_void_p()
+            lib.fbn_gnet_create(self.num_nodes, _p(self._off), _p(self._par), _p(b), _p(np.array(flat or [0.0])), _p(s),
+                                C.byref(_handle))
+        self._h = _handle
+        _register(self)
+
+    def params(self):
+        """(intercept [n], coef as a list of arrays aligned with parents, variance [n])."""
+        b, s = np.zeros(self.num_nodes), np.zeros(self.num_nodes)
+        w = np.zeros(max(int(self._off[-1]), 1))
+        lib.fbn_gnet_params(self._h, _p(b), _p(w), _p(s))
+        return b, [w[self._off[v]:self._off[v + 1]].copy() for v in range(self.num_nodes)], s
+
+    def joint(self):
+        """(mu [n], Sigma [n][n]) of the joint normal distribution."""
+        mu, cov = np.zeros(self.num_nodes), np.zeros((self.num_nodes, self.num_nodes))
+        lib.fbn_gnet_joint(self._h, _p(mu), _p(cov))
+        return mu, cov
+
+
+def gnet_learn_host(mean, ss, R, nsamples, parents, names=None):
+    """The host solve of GaussianParameterLearning from moments handed in (fbn_gnet_learn_host): mean [n], the
+    centred sums of squares ss [n] and the correlation matrix R [n][n] of nsamples samples -> GaussianNetwork."""
+    mean, ss, R = (np.ascontiguousarray(a, np.float64) for a in (mean, ss, R))
+    off, par = _csr_parents(parents, len(mean))
+    h = C.c_void_p()
+    lib.fbn_gnet_learn_host(len(mean), int(nsamples), _p(mean), _p(ss), _p(R), _p(off), _p(par), C.byref(h))
+    return GaussianNetwork(parents, names=names, _handle=h)
+
+
+class GaussianParameterLearning:
+    """Maximum-likelihood parameters of a known structure from complete real-valued data.  `source`: a
+    ContinuousDataset (uploaded here) or a GaussianIndependenceTest, whose context -- the column store and its
+    moments -- is shared, so PC-stable and learning use one upload (PCStable.ci after a run)."""
+
+    def __init__(self, source, device=0):
+        self.ci = source if isinstance(source, GaussianIndependenceTest) else GaussianIndependenceTest(source, device=device)
+
+    def LearnParamsKnowStructCompData(self, parents, names=None):
+        """The learned GaussianNetwork (fbn_gnet_learn): parents[v] in the node's own order."""
+        off, par = _csr_parents(parents, self.ci.num_vars)
+        h = C.c_void_p()
+        lib.fbn_gnet_learn(self.ci._h, _p(off), _p(par), C.byref(h))
+        return GaussianNetwork(parents, names=names, _handle=h)
+
+
+class GaussianInference(_Handle):
+    """Exact inference in a GaussianNetwork (fbn_ginf): batches of evidence cases conditioned on the resident
+    joint, one workgroup per case.  device < 0: the host twin (bit-identical results)."""
+
+    _destroy = "fbn_ginf_destroy"
+
+    def __init__(self, network, device=0):
+        self.network = network
+        self.degenerate = 0
+        h = C.c_void_p()
+        lib.fbn_ginf_create(network._h, int(device), C.byref(h))
+        self._h = h
+        _register(self)
+
+    def infer(self, evidence, mean=True, var=True):
+        """evidence float64 [ncases][num_nodes], NaN = unobserved -> (mean, var, logp); a degenerate case is NaN
+        throughout and counted in self.degenerate."""
+        ev = np.ascontiguousarray(evidence, np.float64).reshape(-1, self.network.num_nodes)
+        n = ev.shape[0]
+        m = np.zeros(ev.shape) if mean else None
+        v = np.zeros(ev.shape) if var else None
+        lp = np.zeros(n)
+        deg = C.c_int64()
+        lib.fbn_ginf_run(self._h, _p(ev), n, _p(m), _p(v), _p(lp), C.byref(deg))
+        self.degenerate = deg.value
+        return m, v, lp
+
+    def run_device(self, d_evidence_ptr, ncases, d_mean_ptr=None, d_var_ptr=None, d_logp_ptr=None, stream_ptr=None):
+        """Device-resident run (asynchronous on the stream after the evidence check)."""
+        opt = lambda q: C.c_void_p(q) if q else None
+        lib.fbn_ginf_run_device(self._h, C.c_void_p(d_evidence_ptr), int(ncases), opt(d_mean_ptr), opt(d_var_ptr),
+                                opt(d_logp_ptr), stream_ptr)
+
+    def set_tuning(self, max_workgroups=0):
+        """fbn_ginf_set_tuning: a cap on the persistent grid, 0 = automatic.  Results do not change."""
+        lib.fbn_ginf_set_tuning(self._h, int(max_workgroups))
+
+    def info(self):
+        out = np.zeros(6, np.int64)
+        lib.fbn_ginf_info(self._h, _p(out))
+        return {k: int(v) for k, v in zip(("nvars", "m_max", "lds_bytes", "workgroups", "tile", "degenerate"), out)}
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        lib.fbn_ginf_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
 
 
 class _BdScore(C.Structure):

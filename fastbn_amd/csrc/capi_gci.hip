@@ -203,6 +203,21 @@ struct DeviceTester : GciTester {
 };
 
 }  // namespace
+
+int GciMoments(fbn_gci_ctx *c, int *nvars, int64_t *N, std::vector<double> &mean, std::vector<double> &ss,
+               std::vector<double> &R) {
+    if (!c) return SetError(FBN_ERR_ARG, "null pointer");
+    const size_t n = (size_t)c->nvars;
+    mean.resize(n), ss.resize(n), R.resize(n * n);
+    FBN_HIP(hipSetDevice(c->device));
+    FBN_HIP(hipStreamSynchronize(c->stream));
+    FBN_HIP(hipMemcpy(mean.data(), c->mean.p, n * 8, hipMemcpyDeviceToHost));
+    FBN_HIP(hipMemcpy(ss.data(), c->var.p, n * 8, hipMemcpyDeviceToHost));
+    FBN_HIP(hipMemcpy(R.data(), c->R.p, n * n * 8, hipMemcpyDeviceToHost));
+    *nvars = c->nvars, *N = c->N;
+    return FBN_OK;
+}
+
 }  // namespace fbn
 
 extern "C" {

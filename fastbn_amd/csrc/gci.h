@@ -51,6 +51,11 @@ class GciTester {
 // ContinueAfter after each level, OrientPC at the end.
 int RunPCGauss(GciTester &T, int nvars, int64_t N, double alpha, int depth, PCResultHost &res);
 
+// the moments a device context holds, downloaded: mean [n], the centred sums of squares S_vv [n], R [n][n]
+// (defined beside the context, capi_gci.hip)
+int GciMoments(fbn_gci_ctx *c, int *nvars, int64_t *N, std::vector<double> &mean, std::vector<double> &ss,
+               std::vector<double> &R);
+
 int LoadRealCsv(const std::string &path, int *nvars, int64_t *nsamples, std::vector<std::string> &names,
                 std::vector<double> &cols);
 

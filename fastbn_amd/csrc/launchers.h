@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, order_mcmc.hip, gci_corr.hip, gci_test.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, order_mcmc.hip, gci_corr.hip, gci_test.hip, ginf.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -254,5 +254,22 @@ struct GciTestArgs {
     unsigned long long *stats;
 };
 extern "C" hipError_t fbn_gci_test_launch(const GciTestArgs *a, int d, hipStream_t stream);
+// Exact inference in a linear-Gaussian network (ginf.hip): ncases evidence rows ev [ncases][n] (NaN = unobserved)
+// conditioned on the joint mu [n], Sigma [n][n]; one workgroup of 256 threads per case, a persistent grid of
+// `grid` workgroups with lds_bytes = fbn_ginf_lds_bytes(n, m_max) (ginf_model.h) of dynamic LDS each, m_max the
+// batch's largest observed count (<= kGinfMaxObs: a case past it, which the caller refuses beforehand, gets
+// NaN).  mean, var [ncases][n] and logp [ncases] may each be null.  fbn_ginf_check_launch: word[0] = the
+// smallest flat index of an infinite value, word[1] = ~0 - the largest observed count (both start as ~0).
+struct GinfArgs {
+    const double *mu, *Sigma;
+    int n;
+    const double *ev;
+    long long ncases;
+    double *mean, *var, *logp;
+    int lds_bytes;
+};
+extern "C" hipError_t fbn_ginf_launch(const GinfArgs *a, int grid, hipStream_t stream);
+extern "C" hipError_t fbn_ginf_check_launch(const double *ev, long long ncases, int n, unsigned long long *word, int grid,
+                                            hipStream_t stream);
 
 #endif

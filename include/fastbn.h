@@ -1460,6 +1460,73 @@ int fbn_gci_host_pc_stable(const double *R, int nvars, int64_t nsamples, double 
 /* tau_d of (alpha, nsamples, d) as both paths use it */
 int fbn_gci_tau(double alpha, int64_t nsamples, int d, double *tau);
 
+/* ------------------------------------------------------------------ Gaussian Bayesian networks
+ * The continuous counterpart of network -> parameter learning -> exact inference.  The reference's ContinuousNode
+ * has no learner and no engine.
+ *
+ * MODEL.  A linear-Gaussian network over n variables:
+ *   X_v = b_v + sum_{p in Pa(v)} w_vp X_p + eps_v,   eps_v ~ N(0, s_v) independent, s_v > 0.
+ * JOINT.  mu [n], Sigma [n][n], built on the host in one fixed topological order: Kahn's algorithm, the lowest
+ * index first among the ready nodes; the parents of a node are added in ascending index order:
+ *   mu_v = b_v + sum_p w_vp mu_p;   for u earlier than v: Sigma_vu = Sigma_uv = sum_p w_vp Sigma_pu;
+ *   Sigma_vv = s_v + sum_p w_vp Sigma_pv.
+ * PARAMETERS of a known structure are maximum likelihood with divisor N, from the moments a Gaussian CI context
+ * holds (means, centred sums of squares, R), downloaded once.  Per node the normal equations are solved on the
+ * correlation scale by the square-root-free elimination of the Gaussian CI test (csrc/gci_elim.h; host code, any
+ * number of parents, pivots in ascending parent order), then rescaled:
+ *   w_vp = beta_p sd_v / sd_p,   b_v = mean_v - sum_p w_vp mean_p,   s_v = var_v * (Schur complement of v).
+ * A pivot or a Schur complement <= 2^-40 (collinear parents; a child that is a linear function of its parents)
+ * is FBN_ERR_ARG naming the node.
+ * A CASE is a float64 row [n]: NaN = unobserved, a finite value = observed, an infinity is FBN_ERR_ARG naming the
+ * case and the variable.  E = the observed indices ascending, m = |E|, U the rest, delta = x_E - mu_E.
+ *   Sigma_EE = L L^T, left-looking: L_ij = (Sigma[e_i][e_j] - sum_{k<j} L_ik L_jk) / L_jj, L_jj = sqrt(d_j),
+ *     d_j = Sigma[e_j][e_j] - sum_{k<j} L_jk^2;   L a = delta;
+ *   log p(e) = -(m ln 2 pi + sum_j ln d_j + a . a) / 2   (the logarithm is the library's own, csrc/hc_bd.h);
+ *   u in U: L y = Sigma_Eu, mean_u = mu_u + y . a, var_u = Sigma_uu - y . y clamped at 0;
+ *   u in E: mean_u = x_u, var_u = +0.0.
+ * Every sum runs from +0.0 in ascending index order and is then subtracted; csrc/ginf_model.h holds the
+ * recurrences once, and the kernel and the host twin both evaluate it: their results are equal bit for bit,
+ * whatever the grid.  A case is DEGENERATE when some d_j <= 2^-40 Sigma[e_j][e_j]: all its outputs are NaN, it is
+ * counted, and it is never an error (the Gaussian CI test's convention).  m = 0 returns the prior (mu, diag
+ * Sigma, log p = 0); m = n returns only a log density beside the observed values.
+ * LIMITS.  m <= 128 observed variables per case, n <= 8192 at fbn_ginf_create: FBN_ERR_LIMIT with the number,
+ * before any launch. */
+typedef struct fbn_gnet fbn_gnet;
+typedef struct fbn_ginf fbn_ginf;
+/* parent_off [nvars + 1], parents and coef [parent_off[nvars]] (coef aligned with the CSR parent list), intercept
+ * and variance [nvars].  A cycle, a parent out of range, listed twice or the node itself, a value that is not
+ * finite and a variance that is not positive are FBN_ERR_ARG. */
+int fbn_gnet_create(int nvars, const int32_t *parent_off, const int32_t *parents, const double *intercept, const double *coef,
+                    const double *variance, fbn_gnet **out);
+/* the maximum-likelihood network of a structure from a Gaussian CI context's resident moments */
+int fbn_gnet_learn(fbn_gci_ctx *c, const int32_t *parent_off, const int32_t *parents, fbn_gnet **out);
+/* the same solve from moments the caller hands in: mean [nvars], ss [nvars] = the centred sums of squares,
+ * R [nvars][nvars].  Given a context's moments it returns fbn_gnet_learn's bits.  No device. */
+int fbn_gnet_learn_host(int nvars, int64_t nsamples, const double *mean, const double *ss, const double *R,
+                        const int32_t *parent_off, const int32_t *parents, fbn_gnet **out);
+/* the parameters in fbn_gnet_create's layout; each pointer may be NULL */
+int fbn_gnet_params(const fbn_gnet *net, double *intercept, double *coef, double *variance);
+int fbn_gnet_joint(const fbn_gnet *net, double *mean /* [nvars] */, double *cov /* [nvars][nvars] */);
+int fbn_gnet_destroy(fbn_gnet *net);
+/* An inference handle: the joint is formed once and stays on `device`.  device < 0: a host-only handle, whose
+ * fbn_ginf_run is the host twin and whose fbn_ginf_run_device is FBN_ERR_NODEV. */
+int fbn_ginf_create(const fbn_gnet *net, int device, fbn_ginf **out);
+/* evidence [ncases][nvars] -> mean, var [ncases][nvars], logp [ncases], the number of degenerate cases; host
+ * arrays, synchronous, every output may be NULL */
+int fbn_ginf_run(fbn_ginf *h, const double *evidence, int64_t ncases, double *mean, double *var, double *logp,
+                 int64_t *degenerate);
+/* the same on device buffers, queued on hip_stream; asynchronous after the evidence check (one stream sync).
+ * d_mean, d_var, d_logp may each be NULL.  A degenerate case is the one whose log density is NaN. */
+int fbn_ginf_run_device(fbn_ginf *h, const double *d_evidence, int64_t ncases, double *d_mean, double *d_var, double *d_logp,
+                        void *hip_stream);
+/* max_workgroups caps the persistent grid (0 = automatic).  Results do not depend on it. */
+int fbn_ginf_set_tuning(fbn_ginf *h, int32_t max_workgroups);
+/* out = {nvars; of the last launch: the batch's largest m, LDS bytes per workgroup, workgroups, the tile T of
+ * unobserved variables at that m; degenerate cases of the last fbn_ginf_run} */
+int fbn_ginf_info(const fbn_ginf *h, int64_t out[6]);
+int fbn_ginf_last_kernel_ms(const fbn_ginf *h, float *ms);
+int fbn_ginf_destroy(fbn_ginf *h);
+
 #ifdef __cplusplus
 }
 #endif
