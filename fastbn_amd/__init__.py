@@ -51,6 +51,10 @@ reference's names and argument meaning:
   ``GaussianInference(network).infer(evidence)`` -- exact posterior means, variances and log densities of batches of
   cases (NaN = unobserved), one workgroup per case on the device, bit-identical to a host twin (no reference
   counterpart)
+* ``HillClimbing(score).learn(ContinuousDataset(...) | GaussianIndependenceTest)`` and ``family_scores`` on them --
+  score-based learning on real-valued columns: the Gaussian log-likelihood score ("bic", "aic", "loglik", a number)
+  and BGe ("bge", ("bge", alpha_mu[, alpha_w])) of families of up to 8 parents, one family per lane on the device
+  from the resident correlation matrix, bit-identical to a host twin (no reference counterpart)
 
 There is no CPU fallback: if the HIP library is missing, importing works but every call raises.
 """

@@ -246,6 +246,12 @@ _SIGS = {
     "fbn_gci_host_run": [_vp, C.c_int, _i64, _vp, _i64, C.c_int, _dbl, _vp, _vp, _vp, _vp, _vp],
     "fbn_gci_host_pc_stable": [_vp, C.c_int, _i64, _dbl, C.c_int, _pp],
     "fbn_gci_tau": [_dbl, _i64, C.c_int, _vp],
+    "fbn_gci_moments": [_vp, _vp, _vp, _vp],
+    "fbn_gscore_families": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "fbn_gscore_families_host": [C.c_int, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "fbn_hc_run_gauss": [_vp, _vp, _vp, _pp],
+    "fbn_hc_run_gauss_host": [C.c_int, _i64, _vp, _vp, _vp, _vp, _pp],
+    "fbn_gscore_info": [_vp, _vp],
     "fbn_gnet_create": [C.c_int, _vp, _vp, _vp, _vp, _vp, _pp],
     "fbn_gnet_learn": [_vp, _vp, _vp, _pp],
     "fbn_gnet_learn_host": [C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _pp],
@@ -916,6 +922,19 @@ class GaussianIndependenceTest(_Handle):
         lib.fbn_gci_info(self._h, _p(out))
         return {k: int(v) for k, v in zip(("tile", "split_k", "slab_bytes", "degenerate"), out)}
 
+    def moments(self):
+        """(mean [n], the centred sums of squares ss [n], R [n][n]) as the context holds them (fbn_gci_moments)."""
+        n = self.num_vars
+        mean, ss, R = np.zeros(n), np.zeros(n), np.zeros((n, n))
+        lib.fbn_gci_moments(self._h, _p(mean), _p(ss), _p(R))
+        return mean, ss, R
+
+    def score_info(self):
+        """fbn_gscore_info: the last family-score batch."""
+        out = np.zeros(3, np.int64)
+        lib.fbn_gscore_info(self._h, _p(out))
+        return {k: int(v) for k, v in zip(("families", "launches", "degenerate"), out)}
+
     def corr_kernel_ms(self):
         """(column means, Gram, reduce) of the last computation of R."""
         ms = (C.c_float * 3)()
@@ -1335,6 +1354,44 @@ def _bd_score_table(table, score):
     return ll.value, sc.value
 
 
+class _GaussScore(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("alpha_mu", C.c_double), ("alpha_w", C.c_double),
+                ("penalty", C.c_double)]
+
+
+def _is_gauss(source):
+    return isinstance(source, (ContinuousDataset, GaussianIndependenceTest))
+
+
+def _gauss_score(score, nsamples):
+    """The fbn_gauss_score record of a score on continuous data: "bic" | "aic" | "loglik" | a number (the
+    Gaussian log-likelihood score with that penalty per parameter), "bge" | ("bge", alpha_mu) |
+    ("bge", alpha_mu, alpha_w)."""
+    name, par = (score[0], tuple(score[1:])) if isinstance(score, tuple) else (score, ())
+    if name == "bge":
+        if len(par) > 2:
+            raise FastBNError("bge takes at most (alpha_mu, alpha_w)")
+        return _GaussScore(1, 0, float(par[0]) if par else 1.0, float(par[1]) if len(par) == 2 else 0.0, 0.0)
+    if name in ("bde", "k2"):
+        raise FastBNError(f"score {score!r} is for discrete data; continuous data takes bic, aic, loglik, a number or bge")
+    return _GaussScore(0, 0, 1.0, 0.0, hc_penalty(score, nsamples))
+
+
+def _host_moments(dataset):
+    """(mean, ss, R) that host=True hands the twins: of a ContinuousDataset by numpy; of a GaussianIndependenceTest
+    the context's own, downloaded, so the twin repeats the device's bits."""
+    if isinstance(dataset, GaussianIndependenceTest):
+        return dataset.moments()
+    x = dataset.columns
+    mean = x.mean(axis=1)
+    xc = x - mean[:, None]
+    S = xc @ xc.T
+    ss = np.ascontiguousarray(np.diag(S))
+    R = S / np.sqrt(np.outer(ss, ss))
+    R = np.triu(R, 1) + np.triu(R, 1).T + np.eye(len(ss))
+    return mean, ss, np.ascontiguousarray(R)
+
+
 def hc_penalty(score, nsamples):
     """fbn_hc_penalty: the penalty of a named score ("bic", "aic", "loglik"), or a number as it is; 0 under
     a Bayesian Dirichlet score ("bde", "k2", ("bde", iss)), which has no penalty term."""
@@ -1363,14 +1420,32 @@ def _csr_families(families):
     return off, cols
 
 
-def family_scores(source, families, penalty=0.0, score=None):
+def family_scores(source, families, penalty=0.0, score=None, host=False):
     """fbn_score_families: (loglik, score) float64 arrays of the families [(child, parent, ...), ...] from
     the column store resident in `source` (an IndependenceTest: on the device), or, for a Dataset,
     fbn_score_families_host: the host twin, bit-identical, no device.  score = "bde" | "k2" | ("bde", iss):
-    the Bayesian Dirichlet score instead of loglik - penalty (fbn_score_families_bd and its twin)."""
+    the Bayesian Dirichlet score instead of loglik - penalty (fbn_score_families_bd and its twin).
+    On continuous data (a GaussianIndependenceTest, or a ContinuousDataset, uploaded here; host=True: the twin
+    fbn_gscore_families_host over numpy's moments, no device) the Gaussian scores (fbn_gscore_families): score =
+    "bic" | "aic" | "loglik" | a number, or `penalty` when score is None, or "bge" | ("bge", alpha_mu[, alpha_w]).
+    A degenerate family is -inf twice; their count is left in source.degenerate."""
     off, cols = _csr_families(families)
     n = len(families)
     ll, sc = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    if _is_gauss(source):
+        ns = source.num_samples if isinstance(source, GaussianIndependenceTest) else source.num_instance
+        g = _gauss_score(float(penalty) if score is None else score, ns)
+        if host:
+            _, ss, R = _host_moments(source)
+            deg = C.c_int64()
+            lib.fbn_gscore_families_host(source.num_vars, ns, _p(ss), _p(R), C.byref(g), n, _p(off),
+                                         _p(cols), _p(ll), _p(sc), C.byref(deg))
+            source.degenerate = deg.value
+        else:
+            ci = source if isinstance(source, GaussianIndependenceTest) else GaussianIndependenceTest(source)
+            lib.fbn_gscore_families(ci._h, C.byref(g), n, _p(off), _p(cols), _p(ll), _p(sc))
+            source.degenerate = ci.score_info()["degenerate"]
+        return ll[:n], sc[:n]
     bd = None
     if score is not None:
         bd = _bd_score(score)
@@ -1436,7 +1511,11 @@ class HillClimbing:
     (fbn_hc_run_bd).  allowed: [n][n] mask, allowed[x][y] lets the search add x -> y; start: a DAG
     as parent lists.  learn(source): a Dataset (uploaded here), or an IndependenceTest, whose context is
     shared (`.ci`, as PCStable.ci: ParameterLearning(hc.ci) learns from the same upload); host=True runs
-    the host twin (fbn_hc_run_host) on a Dataset, without a device.  Results: .parents (ascending parent
+    the host twin (fbn_hc_run_host) on a Dataset, without a device.  On continuous data -- a ContinuousDataset
+    or a GaussianIndependenceTest, shared as .ci so GaussianParameterLearning(hc.ci) learns from the same upload --
+    "bic" | "aic" | "loglik" | a number mean the Gaussian log-likelihood score and "bge" | ("bge", alpha_mu[,
+    alpha_w]) the BGe score (fbn_hc_run_gauss; at most 8 parents); "bde" / "k2" there, and "bge" on discrete
+    data, raise FastBNError.  Results: .parents (ascending parent
     lists), .score, .loglik, .node_scores, .trace [(type, from, to, delta)] (type 0 add, 1 delete,
     2 reverse), .iterations, .families_scored, .kernel_ms, .info."""
 
@@ -1449,9 +1528,9 @@ class HillClimbing:
         self.allowed, self.start = allowed, start
         self.ci = None
 
-    def _options(self, nvars, nsamples):
+    def _options(self, nvars, nsamples, gauss=False):
         o = _HcOptions()
-        o.penalty = hc_penalty(self.score_name, nsamples)
+        o.penalty = 0.0 if gauss else hc_penalty(self.score_name, nsamples)
         o.max_parents = -1 if self.max_parents is None else int(self.max_parents)
         o.max_iter = -1 if self.max_iter is None else int(self.max_iter)
         o.max_family_cells = int(self.max_family_cells)
@@ -1468,6 +1547,10 @@ class HillClimbing:
 
     def learn(self, source, host=False):
         r = C.c_void_p()
+        if _is_gauss(source):
+            return self._learn_gauss(source, host)
+        if self.score_name == "bge" or (isinstance(self.score_name, tuple) and self.score_name[0] == "bge"):
+            raise FastBNError("score bge is for continuous data (a ContinuousDataset or GaussianIndependenceTest)")
         bd = _bd_score(self.score_name)
         if host:
             o, keep = self._options(source.num_vars, source.num_instance)
@@ -1485,6 +1568,26 @@ class HillClimbing:
                 lib.fbn_hc_run_bd(ci._h, C.byref(o), C.byref(bd), C.byref(r))
             else:
                 lib.fbn_hc_run(ci._h, C.byref(o), C.byref(r))
+        del keep
+        return _take_hc_result(self, r)
+
+    def _learn_gauss(self, source, host):
+        """learn() on continuous data: fbn_hc_run_gauss on a GaussianIndependenceTest (a ContinuousDataset is
+        uploaded into one; either way shared as .ci), or with host=True fbn_hc_run_gauss_host over numpy's moments (of a
+        GaussianIndependenceTest: over the context's own, downloaded)."""
+        r = C.c_void_p()
+        if host:
+            ns = source.num_samples if isinstance(source, GaussianIndependenceTest) else source.num_instance
+            g = _gauss_score(self.score_name, ns)
+            o, keep = self._options(source.num_vars, ns, gauss=True)
+            _, ss, R = _host_moments(source)
+            lib.fbn_hc_run_gauss_host(source.num_vars, ns, _p(ss), _p(R), C.byref(o), C.byref(g), C.byref(r))
+        else:
+            ci = source if isinstance(source, GaussianIndependenceTest) else GaussianIndependenceTest(source, device=self.device)
+            self.ci = ci
+            g = _gauss_score(self.score_name, ci.num_samples)
+            o, keep = self._options(ci.num_vars, ci.num_samples, gauss=True)
+            lib.fbn_hc_run_gauss(ci._h, C.byref(o), C.byref(g), C.byref(r))
         del keep
         return _take_hc_result(self, r)
 

@@ -13,46 +13,10 @@
 
 #include "fbn_device.h"
 #include "gci.h"
+#include "gci_ctx.h"
 #include "launchers.h"
 
-using fbn::DevBuf;
 using fbn::SetError;
-
-struct fbn_gci_ctx {
-    int device = 0, num_cu = 0, nvars = 0;
-    int64_t N = 0;
-    DevBuf X, mean, bad, slab, R, var, stats;
-    int want_split = 0, want_tile = 0;  // fbn_gci_set_tuning, 0 = automatic
-    int split_k = 0, tile = 0;          // what the resident R was computed with
-    hipStream_t stream = nullptr;
-    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};  // around means, Gram, reduce
-    float corr_ms[3] = {0.f, 0.f, 0.f};
-    float last_ms = 0.f;
-    bool timed = false;
-    struct Slot {
-        DevBuf items, indep, r;
-        void *h_items = nullptr, *h_res = nullptr;
-        size_t h_items_bytes = 0, h_res_bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;  // kernel start / end, results in pinned memory
-        int64_t n = 0;
-        bool want_r = false;
-        ~Slot() {
-            if (h_items) (void)hipHostFree(h_items);
-            if (h_res) (void)hipHostFree(h_res);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            if (done) (void)hipEventDestroy(done);
-        }
-    } slot[2];
-    unsigned long long *h_stats = nullptr;  // pinned: [0..2] the reset value, [3..5] the read-back
-    int64_t last_degenerate = 0;
-    ~fbn_gci_ctx() {
-        if (h_stats) (void)hipHostFree(h_stats);
-        for (auto &e : cev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
 
 namespace fbn {
 
@@ -99,6 +63,7 @@ int GciCompute(fbn_gci_ctx *c) {
         if (bad[(size_t)v]) return SetError(FBN_ERR_ARG, "column store: variable %d holds a value that is not finite", v);
     for (int v = 0; v < n; ++v)
         if (!(var[(size_t)v] > 0.0)) return SetError(FBN_ERR_ARG, "column store: variable %d has zero variance", v);
+    c->h_ss = std::move(var);  // the family scorer's tables are formed from it (capi_gscore.hip)
     return FBN_OK;
 }
 

@@ -17,7 +17,7 @@
 // --tol the relative stopping tolerance, pseudo-count 1; one line per iteration with the log-likelihood and
 // Q; --out FILE writes the learned CPTs as text, one line per node and parent configuration.
 // -a 14, this build's own too: score-based structure learning, greedy hill climbing over arc additions,
-// deletions and reversals from the empty graph on -f2's CSV (--score bic|aic|loglik|bde|k2, default bic;
+// deletions and reversals from the empty graph on -f2's CSV (--score bic|aic|loglik|bde|k2, default bic; bic-g|aic-g|loglik-g|bge: -f2 is a CSV of reals, the Gaussian scores, -a 14 only;
 // --iss X: the equivalent sample size of bde, default 1, refused beside any other score; --max-parents K);
 // prints the arc count, the score and the iterations, and with -f1 given the SHD against
 // that network through -a 0's comparison; --out FILE writes the DAG, one line per node: node, number of
@@ -89,7 +89,7 @@ int main(int argc, char **argv) {
             std::cout << "Usage: ./BayesianNetwork [-a 0|2|4|5|6|7|8|10|12|13|14|15|16|17|18|19|20] [-t threads] [-g group] [-q samples] [-d length] [-m updates] "
                          "[-l interval] [-f0 net] "
                          "[-f1 refnet] [-f2 train] [-f3 test] [-f4 pt] [--device N] [--gpus G] [--depth D] [--seed N] "
-                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2] [--iss X] [--max-parents K] [--prior uniform|indegree] [--thin T] "
+                         "[--tol T] [--damping L] [--eps E] [--score bic|aic|loglik|bde|k2|bic-g|aic-g|loglik-g|bge] [--iss X] [--max-parents K] [--prior uniform|indegree] [--thin T] "
                          "[--out FILE] [--prefix DIR]"
                       << std::endl;
             return 0;
@@ -491,43 +491,95 @@ int main(int argc, char **argv) {
             fprintf(stderr, "Error: %s\n", fbn_last_error());
             return 1;
         };
-        fbn_dataset *ds = nullptr;
-        if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
-        int n = 0;
-        int64_t ns = 0;
-        fbn_dataset_shape(ds, &n, &ns);
-        std::vector<int32_t> dims((size_t)n);
-        std::vector<uint8_t> cols((size_t)n * (size_t)ns);
-        fbn_dataset_dims(ds, dims.data());
-        fbn_dataset_columns(ds, cols.data());
-        fbn_dataset_destroy(ds);
-        fbn_hc_options opt{};
-        // a Bayesian Dirichlet score (BDeu with --iss, K2) has no penalty term and goes through the _bd entries
-        const bool is_bd = score_name == "bde" || score_name == "k2";
-        if (iss_given && score_name != "bde") {
-            fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
+        // the scores of continuous data (bic-g, aic-g, loglik-g: the Gaussian log-likelihood score; bge, with --iss as
+        // alpha_mu) read -f2 as a CSV of reals, as -a 19 does, and go through the _gauss entries
+        const bool gauss = score_name == "bic-g" || score_name == "aic-g" || score_name == "loglik-g" || score_name == "bge";
+        if (gauss && exact) {
+            fprintf(stderr, "Error: --score %s scores continuous data, which -a 17 does not learn from (hill climbing, -a 14, does)\n",
+                    score_name.c_str());
             return 1;
         }
-        const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
-        if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &opt.penalty)) return die();
-        opt.max_parents = max_parents;
-        opt.max_iter = -1;
-        fbn_exact_options xopt{};
-        xopt.penalty = opt.penalty;
-        xopt.max_parents = max_parents;
+        int n = 0;
+        int64_t ns = 0;
+        fbn_hc_options opt{};
         fbn_hc_result *res = nullptr;
         fbn_ci_ctx *ctx = nullptr;
-        if (device < 0) {
-            if (is_bd ? (exact ? fbn_exact_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, &bd, &res)
-                               : fbn_hc_run_bd_host(n, dims.data(), cols.data(), ns, &opt, &bd, &res))
-                      : (exact ? fbn_exact_run_host(n, dims.data(), cols.data(), ns, &xopt, &res)
-                               : fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res)))
+        fbn_gci_ctx *gctx = nullptr;
+        if (gauss) {
+            fbn_cdataset *cds = nullptr;
+            if (fbn_cdataset_load_csv(train_set_file.c_str(), &cds)) return die();
+            fbn_cdataset_shape(cds, &n, &ns);
+            std::vector<double> x((size_t)n * (size_t)ns);
+            fbn_cdataset_columns(cds, x.data());
+            fbn_cdataset_destroy(cds);
+            fbn_gauss_score g{score_name == "bge" ? FBN_GSCORE_BGE : FBN_GSCORE_LL, 0, iss_given ? iss : 1.0, 0.0, 0.0};
+            if (score_name != "bge") {
+                if (iss_given) {
+                    fprintf(stderr, "Error: --iss is alpha_mu of --score bge (or the equivalent sample size of bde); the score is %s\n",
+                            score_name.c_str());
+                    return 1;
+                }
+                if (fbn_hc_penalty(score_name.substr(0, score_name.size() - 2).c_str(), ns, &g.penalty)) return die();
+            }
+            opt.max_parents = max_parents;
+            opt.max_iter = -1;
+            if (device < 0) {
+                // the host twin over moments formed here: centred sums of squares and the correlation matrix
+                std::vector<double> ss((size_t)n), R((size_t)n * n);
+                for (int v = 0; v < n; ++v) {
+                    double *c = x.data() + (size_t)v * ns, m = 0.0;
+                    for (int64_t i = 0; i < ns; ++i) m += c[i];
+                    m /= (double)ns;
+                    for (int64_t i = 0; i < ns; ++i) c[i] -= m;
+                }
+                for (int u = 0; u < n; ++u)
+                    for (int v = u; v < n; ++v) {
+                        const double *a = x.data() + (size_t)u * ns, *b = x.data() + (size_t)v * ns;
+                        double d = 0.0;
+                        for (int64_t i = 0; i < ns; ++i) d += a[i] * b[i];
+                        R[(size_t)u * n + v] = R[(size_t)v * n + u] = d;
+                    }
+                for (int v = 0; v < n; ++v) ss[(size_t)v] = R[(size_t)v * n + v];
+                for (int u = 0; u < n; ++u)
+                    for (int v = 0; v < n; ++v) R[(size_t)u * n + v] = u == v ? 1.0 : R[(size_t)u * n + v] / sqrt(ss[(size_t)u] * ss[(size_t)v]);
+                if (fbn_hc_run_gauss_host(n, ns, ss.data(), R.data(), &opt, &g, &res)) return die();
+            } else if (fbn_gci_upload(x.data(), n, ns, device, &gctx) || fbn_hc_run_gauss(gctx, &opt, &g, &res)) {
                 return die();
+            }
         } else {
-            if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
-            if (is_bd ? (exact ? fbn_exact_run_bd(ctx, &xopt, &bd, &res) : fbn_hc_run_bd(ctx, &opt, &bd, &res))
-                      : (exact ? fbn_exact_run(ctx, &xopt, &res) : fbn_hc_run(ctx, &opt, &res)))
-                return die();
+            fbn_dataset *ds = nullptr;
+            if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
+            fbn_dataset_shape(ds, &n, &ns);
+            std::vector<int32_t> dims((size_t)n);
+            std::vector<uint8_t> cols((size_t)n * (size_t)ns);
+            fbn_dataset_dims(ds, dims.data());
+            fbn_dataset_columns(ds, cols.data());
+            fbn_dataset_destroy(ds);
+            // a Bayesian Dirichlet score (BDeu with --iss, K2) has no penalty term and goes through the _bd entries
+            const bool is_bd = score_name == "bde" || score_name == "k2";
+            if (iss_given && score_name != "bde") {
+                fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
+                return 1;
+            }
+            const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+            if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &opt.penalty)) return die();
+            opt.max_parents = max_parents;
+            opt.max_iter = -1;
+            fbn_exact_options xopt{};
+            xopt.penalty = opt.penalty;
+            xopt.max_parents = max_parents;
+            if (device < 0) {
+                if (is_bd ? (exact ? fbn_exact_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, &bd, &res)
+                                   : fbn_hc_run_bd_host(n, dims.data(), cols.data(), ns, &opt, &bd, &res))
+                          : (exact ? fbn_exact_run_host(n, dims.data(), cols.data(), ns, &xopt, &res)
+                                   : fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res)))
+                    return die();
+            } else {
+                if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
+                if (is_bd ? (exact ? fbn_exact_run_bd(ctx, &xopt, &bd, &res) : fbn_hc_run_bd(ctx, &opt, &bd, &res))
+                          : (exact ? fbn_exact_run(ctx, &xopt, &res) : fbn_hc_run(ctx, &opt, &res)))
+                    return die();
+            }
         }
         fbn_hc_info info;
         fbn_hc_result_info(res, &info);
@@ -573,6 +625,7 @@ int main(int argc, char **argv) {
         }
         fbn_hc_result_destroy(res);
         if (ctx) fbn_ci_ctx_destroy(ctx);
+        if (gctx) fbn_gci_ctx_destroy(gctx);
     } else if (algorithm == 18) {
         // exact arc posteriors: no counterpart in the reference
         std::cout << "===============================" << std::endl
@@ -581,6 +634,11 @@ int main(int argc, char **argv) {
                   << "score = " << score_name << ", max parents = " << max_parents << ", prior = " << prior_name << std::endl
                   << "\tsample set: " << train_set_file << std::endl
                   << "===============================" << std::endl;
+        if (score_name == "bic-g" || score_name == "aic-g" || score_name == "loglik-g" || score_name == "bge") {
+            fprintf(stderr, "Error: --score %s scores continuous data, which -a %d does not learn from (hill climbing, -a 14, does)\n",
+                    score_name.c_str(), algorithm);
+            return 1;
+        }
         auto die = [] {
             fprintf(stderr, "Error: %s\n", fbn_last_error());
             return 1;
@@ -663,6 +721,11 @@ int main(int argc, char **argv) {
                   << ", seed = " << seed << std::endl
                   << "\tsample set: " << train_set_file << std::endl
                   << "===============================" << std::endl;
+        if (score_name == "bic-g" || score_name == "aic-g" || score_name == "loglik-g" || score_name == "bge") {
+            fprintf(stderr, "Error: --score %s scores continuous data, which -a %d does not learn from (hill climbing, -a 14, does)\n",
+                    score_name.c_str(), algorithm);
+            return 1;
+        }
         auto die = [] {
             fprintf(stderr, "Error: %s\n", fbn_last_error());
             return 1;

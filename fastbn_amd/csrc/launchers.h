@@ -1,6 +1,6 @@
 // launchers.h -- the extern "C" kernel launchers of libfastbn, declared once: included by the file that
 // defines each one (jt_kernels.hip, jt_virt.hip, jt_tile.hip, ci_kernels.hip, ci_bits_*.hip, ci_l1.hip,
-// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, order_mcmc.hip, gci_corr.hip, gci_test.hip, ginf.hip) and by every caller (capi_*.hip), so a
+// ci_gram_mfma.hip, lbp.hip, sample.hip, epis.hip, ais.hip, jt_mpe.hip, jt_em.hip, jt_psample.hip, hc_score.hip, hc_bd.hip, gibbs.hip, exact_dp.hip, exact_bma.hip, order_mcmc.hip, gci_corr.hip, gci_test.hip, gscore.hip, ginf.hip) and by every caller (capi_*.hip), so a
 // definition that disagrees with its declaration does not compile.  A launcher with many arguments
 // takes one record that its caller fills by name: ci_args.h (CiArgs, CiBitsArgs, CiG2Args, CiL1Args),
 // jt_program.h (JtArgs, JtLdsArgs), and the newer subsystems' own *_model.h / sample_device.h.
@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "ci_args.h"
+#include "gscore.h"
 #include "jt_program.h"
 #include "lbp_model.h"
 
@@ -254,6 +255,20 @@ struct GciTestArgs {
     unsigned long long *stats;
 };
 extern "C" hipError_t fbn_gci_test_launch(const GciTestArgs *a, int d, hipStream_t stream);
+// The Gaussian family scorer (gscore.hip; gscore.h's scores): n families of p parents (0..8), one per lane, as
+// records rec [n][2 + p] = (out_index, child, parents ascending); each lane writes loglik[out_index] and
+// score[out_index] and the waves add their degenerate families to *degenerate.  lss, tq [nvars] and C are
+// gscore.h's tables.
+struct GscoreArgs {
+    const double *R, *lss, *tq;
+    int nvars;
+    const int32_t *rec;
+    long long n;
+    double *loglik, *score;
+    unsigned long long *degenerate;
+    FbnGsConsts C;
+};
+extern "C" hipError_t fbn_gscore_launch(const GscoreArgs *a, int p, int bge, hipStream_t stream);
 // Exact inference in a linear-Gaussian network (ginf.hip): ncases evidence rows ev [ncases][n] (NaN = unobserved)
 // conditioned on the joint mu [n], Sigma [n][n]; one workgroup of 256 threads per case, a persistent grid of
 // `grid` workgroups with lds_bytes = fbn_ginf_lds_bytes(n, m_max) (ginf_model.h) of dynamic LDS each, m_max the

@@ -1459,6 +1459,55 @@ int fbn_gci_host_run(const double *R, int nvars, int64_t nsamples, const int32_t
 int fbn_gci_host_pc_stable(const double *R, int nvars, int64_t nsamples, double alpha, int depth, fbn_pc_result **out);
 /* tau_d of (alpha, nsamples, d) as both paths use it */
 int fbn_gci_tau(double alpha, int64_t nsamples, int d, double *tau);
+/* The moments a context holds: mean [nvars], the centred sums of squares ss [nvars], R [nvars][nvars]; each
+ * may be NULL. */
+int fbn_gci_moments(fbn_gci_ctx *c, double *mean, double *ss, double *R);
+
+/* ------------------------------------------------------------------ Gaussian family scores
+ * Score-based structure learning on continuous data: the decomposable scores of a linear-Gaussian family (a child
+ * v regressed on its parents P, p = |P| <= 8) from a Gaussian context's resident moments, and hill climbing
+ * (the search of fbn_hc_run, unchanged) over them.  The device path is held bit for bit to the host twins below.
+ *
+ * From the pivots d_0 .. d_p of the square-root-free elimination of R over (P ascending, v):
+ *   FBN_GSCORE_LL   sigma^2 = ss_v d_p / N,  loglik = -(N/2)(ln 2 pi + 1 + ln sigma^2),
+ *                   score = loglik - penalty (p + 2)   (coefficients, intercept, variance; penalty as
+ *                   fbn_hc_penalty gives it for "bic", "aic", "loglik", or any non-negative number)
+ *   FBN_GSCORE_BGE  the Bayesian Gaussian equivalent score in the corrected form of Kuipers, Moffa & Heckerman
+ *                   (2014), the prior mean at the sample mean: with t = alpha_mu (alpha_w - n - 1) / (alpha_mu + 1),
+ *                   M = t I + S, c = N + alpha_w - n, c0 = alpha_w - n,
+ *                   score = -(N/2) ln pi + ln(alpha_mu / (N + alpha_mu)) / 2 + lnGamma((c + p + 1) / 2)
+ *                           - lnGamma((c0 + p + 1) / 2) + ((c0 + 2p + 1) / 2) ln t + ((c + p) / 2) ln det M_PP
+ *                           - ((c + p + 1) / 2) ln det M_{P u v};   loglik as under FBN_GSCORE_LL.
+ *                   alpha_w == 0 means n + alpha_mu + 1; alpha_w <= n - 1, a t that is not positive and
+ *                   alpha_mu <= 0 are FBN_ERR_ARG.
+ * A family with a pivot <= 2^-40 (a parent or the child is a linear function of the others within rounding) is
+ * degenerate: loglik = score = -inf, and it is counted.  Hill climbing never moves onto one; a starting graph
+ * that holds one is FBN_ERR_ARG.  More than 8 parents, or N <= p + 2, is FBN_ERR_LIMIT. */
+#define FBN_GSCORE_LL 0
+#define FBN_GSCORE_BGE 1
+typedef struct fbn_gauss_score {
+    int32_t kind;              /* FBN_GSCORE_LL or FBN_GSCORE_BGE */
+    int32_t pad;
+    double alpha_mu;           /* BGe: > 0 */
+    double alpha_w;            /* BGe: 0 = n + alpha_mu + 1 */
+    double penalty;            /* LL: per parameter, >= 0 */
+} fbn_gauss_score;
+/* loglik / score [nfam] of the families (child first; fbn_score_families' layout and argument checks); either may
+ * be NULL.  Families of every size may be mixed: they are bucketed by size on the host and each lane writes its
+ * family's place in the caller's order. */
+int fbn_gscore_families(fbn_gci_ctx *c, const fbn_gauss_score *g, int64_t nfam, const int64_t *fam_off,
+                        const int32_t *fam_cols, double *loglik, double *score);
+/* The host twin over moments handed in (fbn_gci_moments'); *degenerate (optional) = the degenerate families. */
+int fbn_gscore_families_host(int nvars, int64_t nsamples, const double *ss, const double *R, const fbn_gauss_score *g,
+                             int64_t nfam, const int64_t *fam_off, const int32_t *fam_cols, double *loglik, double *score,
+                             int64_t *degenerate);
+/* fbn_hc_run on a Gaussian context.  options->penalty and max_family_cells are ignored; max_parents < 0 means 8. */
+int fbn_hc_run_gauss(fbn_gci_ctx *c, const fbn_hc_options *options, const fbn_gauss_score *g, fbn_hc_result **out);
+int fbn_hc_run_gauss_host(int nvars, int64_t nsamples, const double *ss, const double *R, const fbn_hc_options *options,
+                          const fbn_gauss_score *g, fbn_hc_result **out);
+/* out = of the last batch (after fbn_hc_run_gauss: of its last batch, the degenerate count over the whole search):
+ * {families, kernel launches (one per parent count present), degenerate families} */
+int fbn_gscore_info(const fbn_gci_ctx *c, int64_t out[3]);
 
 /* ------------------------------------------------------------------ Gaussian Bayesian networks
  * The continuous counterpart of network -> parameter learning -> exact inference.  The reference's ContinuousNode
