@@ -1504,7 +1504,60 @@ def _take_hc_result(self, r):
     return self
 
 
-class HillClimbing:
+class _ExactOptions(C.Structure):
+    _fields_ = [("penalty", C.c_double), ("max_parents", C.c_int32), ("pad", C.c_int32), ("max_family_cells", C.c_int64),
+                ("allowed", C.c_void_p), ("allowed_len", C.c_int64)]
+
+
+class _ScoredLearner:
+    """What HillClimbing, ExactSearch, ArcPosterior and OrderMCMC share: the candidate options, the data source of a
+    run (a Dataset's arrays for the host twin, else a shared IndependenceTest, `.ci`) and the call of the entry
+    fbn_<stem>_run[_bd][_host] that the score and `host` select."""
+
+    _Options = _ExactOptions  # the entry's options record
+    _BD = object()   # in _call's middle arguments: where the entry takes its fbn_bd_score, if the score is one
+
+    def __init__(self, score, max_parents, max_family_cells, allowed, device):
+        self.score_name, self.device = score, device
+        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
+        self.ci = None
+
+    def _source(self, source, host):
+        """(leading arguments of the entry, variables, samples): a Dataset's arrays for the twin, else the context"""
+        if host:
+            return ((source.num_vars, _p(source.dims), _p(source.columns), source.num_instance), source.num_vars,
+                    source.num_instance)
+        source = self.ci if source is None else source
+        self.ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
+        return (self.ci._h,), len(self.ci.dims), self.ci.num_samples
+
+    def _options(self, nvars, nsamples, penalty=None):
+        """(the options record, the arrays it points into); penalty: None = the score's"""
+        o = self._Options()
+        o.penalty = hc_penalty(self.score_name, nsamples) if penalty is None else penalty
+        o.max_parents = -1 if self.max_parents is None else int(self.max_parents)
+        o.max_family_cells = int(self.max_family_cells)
+        keep = []
+        if self.allowed is not None:
+            a = np.ascontiguousarray(np.asarray(self.allowed) != 0, np.uint8)
+            keep.append(a)
+            o.allowed, o.allowed_len = a.ctypes.data, a.size
+        return o, keep
+
+    def _call(self, stem, source, host, *middle):
+        """fbn_<stem>_run[_bd][_host](source, options, *middle, result): the result handle"""
+        r = C.c_void_p()
+        bd = _bd_score(self.score_name)
+        lead, nvars, nsamples = self._source(source, host)
+        o, keep = self._options(nvars, nsamples)
+        name = f"fbn_{stem}_run" + ("_bd" if bd is not None else "") + ("_host" if host else "")
+        middle = tuple(C.byref(bd) if a is self._BD else a for a in middle if a is not self._BD or bd is not None)
+        getattr(lib, name)(*lead, C.byref(o), *middle, C.byref(r))
+        del keep
+        return r
+
+
+class HillClimbing(_ScoredLearner):
     """Score-based structure learning: greedy hill climbing over arc additions, deletions and reversals
     (fbn_hc_run; no reference counterpart).  score: "bic" | "aic" | "loglik" or an explicit non-negative
     penalty per free parameter, or a Bayesian Dirichlet score "bde" (BDeu, iss = 1) | ("bde", iss) | "k2"
@@ -1523,22 +1576,14 @@ class HillClimbing:
 
     def __init__(self, score="bic", max_parents=None, max_family_cells=0, max_iter=None, allowed=None, start=None,
                  device=0):
-        self.score_name, self.device = score, device
-        self.max_parents, self.max_family_cells, self.max_iter = max_parents, max_family_cells, max_iter
-        self.allowed, self.start = allowed, start
-        self.ci = None
+        super().__init__(score, max_parents, max_family_cells, allowed, device)
+        self.max_iter, self.start = max_iter, start
 
-    def _options(self, nvars, nsamples, gauss=False):
-        o = _HcOptions()
-        o.penalty = 0.0 if gauss else hc_penalty(self.score_name, nsamples)
-        o.max_parents = -1 if self.max_parents is None else int(self.max_parents)
+    _Options = _HcOptions
+
+    def _options(self, nvars, nsamples, penalty=None):
+        o, keep = super()._options(nvars, nsamples, penalty)
         o.max_iter = -1 if self.max_iter is None else int(self.max_iter)
-        o.max_family_cells = int(self.max_family_cells)
-        keep = []
-        if self.allowed is not None:
-            a = np.ascontiguousarray(np.asarray(self.allowed) != 0, np.uint8)
-            keep.append(a)
-            o.allowed, o.allowed_len = a.ctypes.data, a.size
         if self.start is not None:
             off, par = _csr_parents(self.start, nvars)
             keep += [off, par]
@@ -1546,30 +1591,11 @@ class HillClimbing:
         return o, keep
 
     def learn(self, source, host=False):
-        r = C.c_void_p()
         if _is_gauss(source):
             return self._learn_gauss(source, host)
         if self.score_name == "bge" or (isinstance(self.score_name, tuple) and self.score_name[0] == "bge"):
             raise FastBNError("score bge is for continuous data (a ContinuousDataset or GaussianIndependenceTest)")
-        bd = _bd_score(self.score_name)
-        if host:
-            o, keep = self._options(source.num_vars, source.num_instance)
-            if bd is not None:
-                lib.fbn_hc_run_bd_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
-                                       C.byref(o), C.byref(bd), C.byref(r))
-            else:
-                lib.fbn_hc_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
-                                    C.byref(o), C.byref(r))
-        else:
-            ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
-            self.ci = ci
-            o, keep = self._options(len(ci.dims), ci.num_samples)
-            if bd is not None:
-                lib.fbn_hc_run_bd(ci._h, C.byref(o), C.byref(bd), C.byref(r))
-            else:
-                lib.fbn_hc_run(ci._h, C.byref(o), C.byref(r))
-        del keep
-        return _take_hc_result(self, r)
+        return _take_hc_result(self, self._call("hc", source, host, self._BD))
 
     def _learn_gauss(self, source, host):
         """learn() on continuous data: fbn_hc_run_gauss on a GaussianIndependenceTest (a ContinuousDataset is
@@ -1579,14 +1605,14 @@ class HillClimbing:
         if host:
             ns = source.num_samples if isinstance(source, GaussianIndependenceTest) else source.num_instance
             g = _gauss_score(self.score_name, ns)
-            o, keep = self._options(source.num_vars, ns, gauss=True)
+            o, keep = self._options(source.num_vars, ns, penalty=0.0)
             _, ss, R = _host_moments(source)
             lib.fbn_hc_run_gauss_host(source.num_vars, ns, _p(ss), _p(R), C.byref(o), C.byref(g), C.byref(r))
         else:
             ci = source if isinstance(source, GaussianIndependenceTest) else GaussianIndependenceTest(source, device=self.device)
             self.ci = ci
             g = _gauss_score(self.score_name, ci.num_samples)
-            o, keep = self._options(ci.num_vars, ci.num_samples, gauss=True)
+            o, keep = self._options(ci.num_vars, ci.num_samples, penalty=0.0)
             lib.fbn_hc_run_gauss(ci._h, C.byref(o), C.byref(g), C.byref(r))
         del keep
         return _take_hc_result(self, r)
@@ -1608,11 +1634,6 @@ class HillClimbing:
         lib.fbn_bd_set_tuning(ci._h, int(pack))
 
 
-class _ExactOptions(C.Structure):
-    _fields_ = [("penalty", C.c_double), ("max_parents", C.c_int32), ("pad", C.c_int32), ("max_family_cells", C.c_int64),
-                ("allowed", C.c_void_p), ("allowed_len", C.c_int64)]
-
-
 class _ExactInfo(C.Structure):
     _fields_ = [("nvars", C.c_int32), ("tile_bits", C.c_int32), ("passes", C.c_int32), ("levels", C.c_int32),
                 ("families_scored", C.c_int64), ("batches", C.c_int64), ("lattice_bytes", C.c_int64),
@@ -1621,7 +1642,7 @@ class _ExactInfo(C.Structure):
                 ("sink_wall_ms", C.c_double), ("trace_wall_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
-class ExactSearch:
+class ExactSearch(_ScoredLearner):
     """Exact score-optimal structure learning for up to 26 variables: the globally best DAG under a
     decomposable score by dynamic programming over variable subsets (fbn_exact_run; no reference counterpart).
     score, max_parents, max_family_cells, allowed and learn(source, host) are HillClimbing's, and so are the
@@ -1631,42 +1652,10 @@ class ExactSearch:
     Dataset, bit-identical, without a device.  `.ci` is shared as HillClimbing.ci is."""
 
     def __init__(self, score="bic", max_parents=None, max_family_cells=0, allowed=None, device=0):
-        self.score_name, self.device = score, device
-        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
-        self.ci = None
-
-    def _options(self, nsamples):
-        o = _ExactOptions()
-        o.penalty = hc_penalty(self.score_name, nsamples)
-        o.max_parents = -1 if self.max_parents is None else int(self.max_parents)
-        o.max_family_cells = int(self.max_family_cells)
-        a = None
-        if self.allowed is not None:
-            a = np.ascontiguousarray(np.asarray(self.allowed) != 0, np.uint8)
-            o.allowed, o.allowed_len = a.ctypes.data, a.size
-        return o, a
+        super().__init__(score, max_parents, max_family_cells, allowed, device)
 
     def learn(self, source, host=False):
-        r = C.c_void_p()
-        bd = _bd_score(self.score_name)
-        if host:
-            o, keep = self._options(source.num_instance)
-            if bd is not None:
-                lib.fbn_exact_run_bd_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
-                                          C.byref(o), C.byref(bd), C.byref(r))
-            else:
-                lib.fbn_exact_run_host(source.num_vars, _p(source.dims), _p(source.columns), source.num_instance,
-                                       C.byref(o), C.byref(r))
-        else:
-            ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
-            self.ci = ci
-            o, keep = self._options(ci.num_samples)
-            if bd is not None:
-                lib.fbn_exact_run_bd(ci._h, C.byref(o), C.byref(bd), C.byref(r))
-            else:
-                lib.fbn_exact_run(ci._h, C.byref(o), C.byref(r))
-        del keep
-        return _take_hc_result(self, r)
+        return _take_hc_result(self, self._call("exact", source, host, self._BD))
 
     oriented = HillClimbing.oriented
 
@@ -1700,7 +1689,7 @@ def _lse(a, b):
     return y.value
 
 
-class ArcPosterior:
+class ArcPosterior(_ScoredLearner):
     """Exact arc posteriors for up to 26 variables: P(u -> v | data) for every arc by Bayesian model averaging
     over all DAGs, the sum-product counterpart of ExactSearch's dynamic programme (fbn_bma_run; Koivisto & Sood
     2004; no reference counterpart).  score, max_parents, max_family_cells, allowed and learn(source, host) are
@@ -1720,33 +1709,11 @@ class ArcPosterior:
     PRIORS = {"uniform": 0, "indegree": 1}
 
     def __init__(self, score="bde", max_parents=None, max_family_cells=0, allowed=None, prior=0, device=0):
-        self.score_name, self.device = score, device
-        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
+        super().__init__(score, max_parents, max_family_cells, allowed, device)
         self.prior = self.PRIORS.get(prior, prior)
-        self.ci = None
-
-    _options = ExactSearch._options
 
     def learn(self, source, host=False):
-        r = C.c_void_p()
-        bd = _bd_score(self.score_name)
-        prior = int(self.prior)
-        if host:
-            o, keep = self._options(source.num_instance)
-            shape = (source.num_vars, _p(source.dims), _p(source.columns), source.num_instance)
-            if bd is not None:
-                lib.fbn_bma_run_bd_host(*shape, C.byref(o), prior, C.byref(bd), C.byref(r))
-            else:
-                lib.fbn_bma_run_host(*shape, C.byref(o), prior, C.byref(r))
-        else:
-            ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
-            self.ci = ci
-            o, keep = self._options(ci.num_samples)
-            if bd is not None:
-                lib.fbn_bma_run_bd(ci._h, C.byref(o), prior, C.byref(bd), C.byref(r))
-            else:
-                lib.fbn_bma_run(ci._h, C.byref(o), prior, C.byref(r))
-        del keep
+        r = self._call("bma", source, host, int(self.prior), self._BD)
         try:
             info = _BmaInfo()
             lib.fbn_bma_result_info(r, C.byref(info))
@@ -1780,7 +1747,7 @@ class _OmcmcInfo(C.Structure):
                 ("upload_wall_ms", C.c_double), ("chain_wall_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
-class OrderMCMC:
+class OrderMCMC(_ScoredLearner):
     """Arc posteriors for up to 64 variables by MCMC over node orders (fbn_omcmc_run; Friedman & Koller 2003; no
     reference counterpart): Metropolis-Hastings chains whose stationary arc probabilities are ArcPosterior's
     arc_prob, under the same scores, candidates (max_parents, max_family_cells, allowed) and order-modular prior
@@ -1799,34 +1766,15 @@ class OrderMCMC:
 
     def __init__(self, score="bde", max_parents=3, max_family_cells=0, allowed=None, prior=0, chains=64, burn_in=2000,
                  thin=20, samples=200, seed=0, device=0, chain_offset=0, max_families=0):
-        self.score_name, self.device = score, device
-        self.max_parents, self.max_family_cells, self.allowed = max_parents, max_family_cells, allowed
+        super().__init__(score, max_parents, max_family_cells, allowed, device)
         self.prior = self.PRIORS.get(prior, prior)
         self.chains, self.burn_in, self.thin, self.samples, self.seed = chains, burn_in, thin, samples, seed
         self.chain_offset, self.max_families = chain_offset, max_families
-        self.ci = None
-
-    _options = ExactSearch._options
-
-    def _source(self, source, host):
-        """(leading arguments of the entry, number of samples): a Dataset's arrays for the twin, else the context"""
-        if host:
-            return (source.num_vars, _p(source.dims), _p(source.columns), source.num_instance), source.num_instance
-        source = self.ci if source is None else source
-        self.ci = source if isinstance(source, IndependenceTest) else IndependenceTest(source, device=self.device)
-        return (self.ci._h,), self.ci.num_samples
 
     def learn(self, source, host=False):
-        r = C.c_void_p()
-        bd = _bd_score(self.score_name)
         m = _OmcmcOptions(int(self.chains), int(self.samples), int(self.burn_in), int(self.thin), int(self.seed),
                           int(self.chain_offset), int(self.max_families))
-        lead, nsamples = self._source(source, host)
-        o, keep = self._options(nsamples)
-        name = "fbn_omcmc_run" + ("_bd" if bd is not None else "") + ("_host" if host else "")
-        args = (C.byref(o), int(self.prior)) + ((C.byref(bd),) if bd is not None else ()) + (C.byref(m), C.byref(r))
-        getattr(lib, name)(*lead, *args)
-        del keep
+        r = self._call("omcmc", source, host, int(self.prior), self._BD, C.byref(m))
         try:
             info = _OmcmcInfo()
             lib.fbn_omcmc_result_info(r, C.byref(info))
@@ -1853,8 +1801,8 @@ class OrderMCMC:
         k, n = od.shape
         term, arcs = np.zeros((k, n)), np.zeros((k, n, n))
         bd = _bd_score(self.score_name)
-        lead, nsamples = self._source(source, host)
-        o, keep = self._options(nsamples)
+        lead, nvars, nsamples = self._source(source, host)
+        o, keep = self._options(nvars, nsamples)
         getattr(lib, "fbn_omcmc_order_terms" + ("_host" if host else ""))(
             *lead, C.byref(o), int(self.prior), C.byref(bd) if bd is not None else None, int(self.max_families), _p(od), k,
             _p(term), _p(arcs))

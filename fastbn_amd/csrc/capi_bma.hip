@@ -7,7 +7,6 @@
 // the free device memory before anything is allocated and freed on return.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
 #include <memory>
 #include <new>
@@ -15,42 +14,14 @@
 
 #include "capi_state.h"
 #include "exact_bma.h"
-#include "hc_search.h"
 #include "launchers.h"
+#include "learner_device.h"
 
 using fbn::SetError;
 
 namespace fbn {
 
 namespace {
-
-using Clock = std::chrono::steady_clock;
-double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
-struct Pinned {
-    void *p = nullptr;
-    ~Pinned() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-
-// one phase's launches between the context's two events: kernel ms (0 with timing off) and wall ms
-template <class Launches>
-int Phase(fbn_ci_ctx *c, double *kernel_ms, double *wall_ms, Launches launches) {
-    CiSlot &S = c->slot[0];
-    const auto t0 = Clock::now();
-    if (c->timing) FBN_HIP(hipEventRecord(S.ev0, c->stream));
-    if (int rc = launches()) return rc;
-    if (c->timing) FBN_HIP(hipEventRecord(S.ev1, c->stream));
-    FBN_HIP(hipStreamSynchronize(c->stream));
-    if (c->timing) {
-        float f = 0.f;
-        FBN_HIP(hipEventElapsedTime(&f, S.ev0, S.ev1));
-        *kernel_ms = f;
-    }
-    *wall_ms = MsSince(t0);
-    return FBN_OK;
-}
 
 int BmaRunDevice(fbn_ci_ctx *c, const fbn_exact_options &opt, int prior, const HcScorer &scorer, fbn_bma_result *res) {
     const auto t_start = Clock::now();
@@ -67,21 +38,12 @@ int BmaRunDevice(fbn_ci_ctx *c, const fbn_exact_options &opt, int prior, const H
         return FBN_OK;
     }
     const size_t L = (size_t)1 << M, NW = (size_t)1 << n, nout = (size_t)n * n + n + 2;
-    size_t free_b = 0, total_b = 0;
-    FBN_HIP(hipMemGetInfo(&free_b, &total_b));
-    if ((size_t)info.lattice_bytes > free_b)
-        return SetError(FBN_ERR_LIMIT, "%d variables: the posterior lattices take %lld bytes, %zu are free on the device", n,
-                        (long long)info.lattice_bytes, free_b);
-    const int T = c->bma_tile_bits > 0 ? c->bma_tile_bits : fbn_bma_default_tile_bits(M);
-    ExactPass pass[kExactMaxVars];
-    info.tile_bits = T;
-    info.passes = fbn_exact_passes(M, T, pass, kBmaLdsBits);
-    for (int p = 0; p < info.passes; ++p)
-        if (((uint64_t)n << (M - pass[p].lo - pass[p].hb)) > kExactGridMax)
-            return SetError(FBN_ERR_LIMIT, "tile_bits = %d: pass %d of %d variables needs more than %llu workgroups", T, p, n,
-                            (unsigned long long)kExactGridMax);
-    DevBuf ls, X, Fw, Bw, out;
     int rc;
+    if ((rc = LatticeFits(n, info.lattice_bytes, "posterior"))) return rc;
+    ExactPass pass[kExactMaxVars];
+    info.tile_bits = c->bma_tile_bits > 0 ? c->bma_tile_bits : fbn_bma_default_tile_bits(M);
+    if ((rc = LatticePasses(n, info.tile_bits, kBmaLdsBits, pass, &info.passes))) return rc;
+    DevBuf ls, X, Fw, Bw, out;
     if ((rc = ls.ensure(L * n * 8)) || (rc = X.ensure(L * n * 8)) || (rc = Fw.ensure(NW * 8)) || (rc = Bw.ensure(NW * 8)) ||
         (rc = out.ensure(nout * 8)))
         return rc;
@@ -90,15 +52,8 @@ int BmaRunDevice(fbn_ci_ctx *c, const fbn_exact_options &opt, int prior, const H
     // the local scores of one variable at a time into pinned memory, then up
     const std::vector<double> lp = BmaSizePrior(n, prior);
     Pinned stage;
-    hipError_t e = hipHostMalloc(&stage.p, L * 8, hipHostMallocDefault);
-    if (e != hipSuccess) return SetError(FBN_ERR_NOMEM, "hipHostMalloc(%zu): %s", L * 8, hipGetErrorString(e));
-    for (int v = 0; v < n; ++v) {
-        if ((rc = ExactLocalScores(n, dims, opt, scorer, v, static_cast<double *>(stage.p), &xi, lp.empty() ? nullptr : lp.data())))
-            return rc;
-        const auto t0 = Clock::now();
-        FBN_HIP(hipMemcpy(ls.as<double>() + L * v, stage.p, L * 8, hipMemcpyHostToDevice));
-        info.upload_wall_ms += MsSince(t0);
-    }
+    if ((rc = LatticeLocalScores(c, opt, scorer, lp.empty() ? nullptr : lp.data(), stage, ls.as<double>(), &xi, &info.upload_wall_ms)))
+        return rc;
     BmaTakeScoring(xi, &info);
 
     // a transform: its first pass loads what `first_load` names, the later ones the lattice itself
@@ -126,8 +81,8 @@ int BmaRunDevice(fbn_ci_ctx *c, const fbn_exact_options &opt, int prior, const H
     if ((rc = Phase(c, &info.gamma_kernel_ms, &info.gamma_wall_ms, transform(kBmaSuperset, kBmaLse, kBmaLoadGamma, "Gamma")))) return rc;
     if ((rc = Phase(c, &info.q_kernel_ms, &info.q_wall_ms, transform(kBmaSuperset, kBmaAdd, kBmaLoadP, "q")))) return rc;
 
-    if ((e = fbn_bma_gather_launch(X.as<double>(), Fw.as<double>(), Bw.as<double>(), n, out.as<double>(), s)) != hipSuccess)
-        return SetError(FBN_ERR_HIP, "gather launch: %s", hipGetErrorString(e));
+    const hipError_t e = fbn_bma_gather_launch(X.as<double>(), Fw.as<double>(), Bw.as<double>(), n, out.as<double>(), s);
+    if (e != hipSuccess) return SetError(FBN_ERR_HIP, "gather launch: %s", hipGetErrorString(e));
     std::vector<double> h(nout);
     FBN_HIP(hipMemcpyAsync(h.data(), out.p, nout * 8, hipMemcpyDeviceToHost, s));
     FBN_HIP(hipStreamSynchronize(s));
@@ -149,10 +104,7 @@ static int BmaRun(fbn_ci_ctx *c, const fbn_exact_options *options, int32_t prior
     FBN_HIP(hipSetDevice(c->device));
     auto r = std::unique_ptr<fbn_bma_result>(new (std::nothrow) fbn_bma_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    fbn::HcScorer scorer = [c, bd](const fbn::HcBatch &B, double *loglik, double *score, double *kernel_ms) {
-        return fbn::HcDeviceScore(c, B, loglik, score, kernel_ms, bd);
-    };
-    if (int rc = fbn::BmaRunDevice(c, *options, prior, scorer, r.get())) return rc;
+    if (int rc = fbn::BmaRunDevice(c, *options, prior, fbn::HcDeviceScorer(c, bd), r.get())) return rc;
     const fbn_bma_info &i = r->info;
     c->last_ms = (float)(i.score_kernel_ms + i.alpha_kernel_ms + i.level_kernel_ms + i.gamma_kernel_ms + i.q_kernel_ms);
     *out = r.release();

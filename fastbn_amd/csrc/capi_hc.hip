@@ -21,6 +21,7 @@
 #include "hc_score.h"
 #include "hc_search.h"
 #include "launchers.h"
+#include "learner_device.h"
 #include "param_counts.h"
 
 using fbn::SetError;
@@ -90,7 +91,6 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
     HcBdArgs ba{};
     if (bd) fbn_hc_bd_bin(qs.data(), nf, c->bd_pack, order.data(), &ba);
     hipStream_t s = c->stream;
-    CiSlot &S = c->slot[0];
     std::vector<double> out((size_t)nf * 2);
     fbn::StreamDrain drain(s);  // after fam, fstr and out: an early return waits for the copies that use them
     FBN_HIP(hipMemcpyAsync(c->par_fam.p, fam.data(), fam.size() * sizeof(FbnParamFamily), hipMemcpyHostToDevice, s));
@@ -102,33 +102,36 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
     } else {
         FBN_HIP(hipMemcpyAsync(c->hc_pen.p, B.pen + f0, (size_t)nf * 8, hipMemcpyHostToDevice, s));
     }
-    if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
-    FBN_HIP(hipMemsetAsync(c->par_tab.p, 0, (size_t)cells * 4, s));
-    hipError_t e = fbn_param_launch(c->cols.as<uint8_t>(), c->N, c->par_fam.as<FbnParamFamily>(), nf, c->par_col.as<int32_t>(),
-                                    c->par_str.as<int32_t>(), c->par_tab.as<uint32_t>(), slice, nslices, lds_max,
-                                    lds_ints * 4, s);
-    if (e != hipSuccess) return SetError(FBN_ERR_HIP, "family counts launch: %s", hipGetErrorString(e));
-    if (bd) {
-        ba.tab = c->par_tab.as<uint32_t>(), ba.fam = c->par_fam.as<FbnParamFamily>(), ba.fstr = c->par_str.as<int32_t>();
-        ba.prior = c->hc_pen.as<FbnBdPrior>(), ba.L = c->hc_L.as<double>(), ba.out = c->hc_out.as<double>();
-        ba.order = c->hc_order.as<int32_t>();
-        if ((e = fbn_hc_bd_launch(&ba, s)) != hipSuccess)
-            return SetError(FBN_ERR_HIP, "Bayesian Dirichlet score launch: %s", hipGetErrorString(e));
-    } else {
-        HcScoreArgs a{c->par_tab.as<uint32_t>(), c->par_fam.as<FbnParamFamily>(), c->par_str.as<int32_t>(),
-                      c->hc_pen.as<double>(), c->hc_L.as<double>(), c->hc_out.as<double>(), (long long)nf};
-        if ((e = fbn_hc_score_launch(&a, s)) != hipSuccess)
-            return SetError(FBN_ERR_HIP, "family score launch: %s", hipGetErrorString(e));
-    }
-    if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
-    FBN_HIP(hipMemcpyAsync(out.data(), c->hc_out.p, out.size() * 8, hipMemcpyDeviceToHost, s));
-    FBN_HIP(hipStreamSynchronize(s));
+    double ms = 0.0, wall_ms = 0.0;
+    rc = Phase(
+        c, &ms, &wall_ms,
+        [&]() -> int {
+            FBN_HIP(hipMemsetAsync(c->par_tab.p, 0, (size_t)cells * 4, s));
+            hipError_t e = fbn_param_launch(c->cols.as<uint8_t>(), c->N, c->par_fam.as<FbnParamFamily>(), nf, c->par_col.as<int32_t>(),
+                                            c->par_str.as<int32_t>(), c->par_tab.as<uint32_t>(), slice, nslices, lds_max,
+                                            lds_ints * 4, s);
+            if (e != hipSuccess) return SetError(FBN_ERR_HIP, "family counts launch: %s", hipGetErrorString(e));
+            if (bd) {
+                ba.tab = c->par_tab.as<uint32_t>(), ba.fam = c->par_fam.as<FbnParamFamily>(), ba.fstr = c->par_str.as<int32_t>();
+                ba.prior = c->hc_pen.as<FbnBdPrior>(), ba.L = c->hc_L.as<double>(), ba.out = c->hc_out.as<double>();
+                ba.order = c->hc_order.as<int32_t>();
+                if ((e = fbn_hc_bd_launch(&ba, s)) != hipSuccess)
+                    return SetError(FBN_ERR_HIP, "Bayesian Dirichlet score launch: %s", hipGetErrorString(e));
+            } else {
+                HcScoreArgs a{c->par_tab.as<uint32_t>(), c->par_fam.as<FbnParamFamily>(), c->par_str.as<int32_t>(),
+                              c->hc_pen.as<double>(), c->hc_L.as<double>(), c->hc_out.as<double>(), (long long)nf};
+                if ((e = fbn_hc_score_launch(&a, s)) != hipSuccess)
+                    return SetError(FBN_ERR_HIP, "family score launch: %s", hipGetErrorString(e));
+            }
+            return FBN_OK;
+        },
+        [&]() -> int {
+            FBN_HIP(hipMemcpyAsync(out.data(), c->hc_out.p, out.size() * 8, hipMemcpyDeviceToHost, s));
+            return FBN_OK;
+        });
+    if (rc) return rc;
     drain.done();
-    if (c->timing) {
-        float ms = 0.f;
-        FBN_HIP(hipEventElapsedTime(&ms, S.ev0, S.ev1));
-        *kernel_ms += ms;
-    }
+    *kernel_ms += ms;
     for (int64_t f = 0; f < nf; ++f) {
         if (loglik) loglik[f0 + f] = out[(size_t)(2 * f)];
         if (score) score[f0 + f] = out[(size_t)(2 * f + 1)];
@@ -136,7 +139,7 @@ static int HcChunk(fbn_ci_ctx *c, const HcBatch &B, int64_t f0, int64_t f1, int6
     return FBN_OK;
 }
 
-// the device scorer (hc_search.h: capi_exact.hip scores through it too): chunks of consecutive families
+// the device scorer (hc_search.h: every learner scores through it, as HcDeviceScorer): chunks of consecutive families
 // whose tables fit the cap (a larger family alone)
 int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms,
                   const fbn_bd_score *bd) {
@@ -151,6 +154,12 @@ int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score
         f0 = f1;
     }
     return FBN_OK;
+}
+
+HcScorer HcDeviceScorer(fbn_ci_ctx *c, const fbn_bd_score *bd) {
+    return [c, bd](const HcBatch &B, double *loglik, double *score, double *kernel_ms) {
+        return HcDeviceScore(c, B, loglik, score, kernel_ms, bd);
+    };
 }
 
 }  // namespace fbn
@@ -186,10 +195,7 @@ static int HcRun(fbn_ci_ctx *c, const fbn_hc_options *options, const fbn_bd_scor
     if (int rc = fbn::HcCheckSamples(c->N)) return rc;
     auto r = std::unique_ptr<fbn_hc_result>(new (std::nothrow) fbn_hc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    fbn::HcScorer scorer = [c, bd](const fbn::HcBatch &B, double *loglik, double *score, double *kernel_ms) {
-        return fbn::HcDeviceScore(c, B, loglik, score, kernel_ms, bd);
-    };
-    if (int rc = fbn::HcSearch(c->nvars, c->dims.data(), *options, scorer, r.get())) return rc;
+    if (int rc = fbn::HcSearch(c->nvars, c->dims.data(), *options, fbn::HcDeviceScorer(c, bd), r.get())) return rc;
     c->last_ms = (float)r->info.kernel_ms;
     *out = r.release();
     return FBN_OK;

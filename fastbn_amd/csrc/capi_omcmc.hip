@@ -8,7 +8,6 @@
 // sized against the free device memory before anything is allocated and freed on return.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
 #include <memory>
 #include <new>
@@ -16,6 +15,7 @@
 
 #include "capi_state.h"
 #include "launchers.h"
+#include "learner_device.h"
 #include "order_mcmc.h"
 
 using fbn::SetError;
@@ -24,9 +24,6 @@ namespace fbn {
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
 struct DeviceLists {
     DevBuf ent, off;
 };
@@ -34,10 +31,7 @@ struct DeviceLists {
 // the lists through the device scorer, then up; extra_bytes: what the caller allocates beside them
 int UploadLists(fbn_ci_ctx *c, const fbn_exact_options &opt, int prior, const fbn_bd_score *bd, int64_t cap, size_t extra_bytes,
                 OmcmcLists *L, DeviceLists *D, fbn_exact_info *xi, double *upload_ms) {
-    HcScorer scorer = [c, bd](const HcBatch &B, double *loglik, double *score, double *kernel_ms) {
-        return HcDeviceScore(c, B, loglik, score, kernel_ms, bd);
-    };
-    if (int rc = OmcmcBuildLists(c->nvars, c->dims.data(), opt, prior, scorer, cap, L, xi)) return rc;
+    if (int rc = OmcmcBuildLists(c->nvars, c->dims.data(), opt, prior, HcDeviceScorer(c, bd), cap, L, xi)) return rc;
     const size_t ent_bytes = L->ent.size() * sizeof(OmcmcEntry), off_bytes = L->off.size() * sizeof(long long);
     size_t free_b = 0, total_b = 0;
     FBN_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -87,30 +81,29 @@ int OmcmcRunDevice(fbn_ci_ctx *c, const fbn_exact_options &opt, int prior, const
     info.steps_per_launch = c->omcmc_steps_per_launch > 0 ? c->omcmc_steps_per_launch : info.steps;
 
     hipStream_t s = c->stream;
-    CiSlot &S = c->slot[0];
-    const auto t0 = Clock::now();
-    if (c->timing) FBN_HIP(hipEventRecord(S.ev0, s));
-    for (int64_t t = 0; t < info.steps; t += info.steps_per_launch) {
-        a.t0 = t, a.t1 = std::min<int64_t>(info.steps, t + info.steps_per_launch);
-        const hipError_t e = fbn_omcmc_chain_launch(&a, s);
-        if (e != hipSuccess) return SetError(FBN_ERR_HIP, "order MCMC launch at step %lld: %s", (long long)t, hipGetErrorString(e));
-        ++info.launches;
-    }
-    if (c->timing) FBN_HIP(hipEventRecord(S.ev1, s));
-    std::vector<double> h_acc(acc_n);
-    std::vector<uint8_t> h_ord(ord_n);
+    std::vector<double> h_acc;  // sized once the launches are queued: the host fills them while the chains run
+    std::vector<uint8_t> h_ord;
     static_assert(sizeof(long long) == sizeof(int64_t), "accepted counts are copied as they are");
-    FBN_HIP(hipMemcpyAsync(h_acc.data(), acc.p, acc_n * 8, hipMemcpyDeviceToHost, s));
-    FBN_HIP(hipMemcpyAsync(h_ord.data(), orders.p, ord_n, hipMemcpyDeviceToHost, s));
-    FBN_HIP(hipMemcpyAsync(res->log_score.data(), trace.p, tr_n * 8, hipMemcpyDeviceToHost, s));
-    FBN_HIP(hipMemcpyAsync(res->accepted.data(), accepted.p, (size_t)m.chains * 8, hipMemcpyDeviceToHost, s));
-    FBN_HIP(hipStreamSynchronize(s));
-    if (c->timing) {
-        float f = 0.f;
-        FBN_HIP(hipEventElapsedTime(&f, S.ev0, S.ev1));
-        info.chain_kernel_ms = f;
-    }
-    info.chain_wall_ms = MsSince(t0);
+    rc = Phase(
+        c, &info.chain_kernel_ms, &info.chain_wall_ms,
+        [&]() -> int {
+            for (int64_t t = 0; t < info.steps; t += info.steps_per_launch) {
+                a.t0 = t, a.t1 = std::min<int64_t>(info.steps, t + info.steps_per_launch);
+                const hipError_t e = fbn_omcmc_chain_launch(&a, s);
+                if (e != hipSuccess) return SetError(FBN_ERR_HIP, "order MCMC launch at step %lld: %s", (long long)t, hipGetErrorString(e));
+                ++info.launches;
+            }
+            return FBN_OK;
+        },
+        [&]() -> int {
+            h_acc.resize(acc_n), h_ord.resize(ord_n);
+            FBN_HIP(hipMemcpyAsync(h_acc.data(), acc.p, acc_n * 8, hipMemcpyDeviceToHost, s));
+            FBN_HIP(hipMemcpyAsync(h_ord.data(), orders.p, ord_n, hipMemcpyDeviceToHost, s));
+            FBN_HIP(hipMemcpyAsync(res->log_score.data(), trace.p, tr_n * 8, hipMemcpyDeviceToHost, s));
+            FBN_HIP(hipMemcpyAsync(res->accepted.data(), accepted.p, (size_t)m.chains * 8, hipMemcpyDeviceToHost, s));
+            return FBN_OK;
+        });
+    if (rc) return rc;
     OmcmcFinish(n, m, h_acc.data(), h_ord.data(), res);
     info.wall_ms = MsSince(t_start);
     return FBN_OK;

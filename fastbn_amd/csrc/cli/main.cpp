@@ -54,6 +54,59 @@
 #include "PCStable.h"
 #include "fastbn.h"
 
+// What the score-based learners (-a 14, 17, 18, 20) share ahead of their entries: the discrete sample set and
+// --score / --iss as the entries take them.
+
+struct DiscreteSet {
+    int n = 0;
+    int64_t ns = 0;
+    std::vector<int32_t> dims;
+    std::vector<uint8_t> cols;
+};
+
+// -f2's CSV into its columns; false: fbn_last_error() says why
+static bool LoadDiscreteSet(const std::string &path, DiscreteSet *d) {
+    fbn_dataset *ds = nullptr;
+    if (fbn_dataset_load_csv(path.c_str(), &ds)) return false;
+    fbn_dataset_shape(ds, &d->n, &d->ns);
+    d->dims.resize((size_t)d->n);
+    d->cols.resize((size_t)d->n * (size_t)d->ns);
+    fbn_dataset_dims(ds, d->dims.data());
+    fbn_dataset_columns(ds, d->cols.data());
+    fbn_dataset_destroy(ds);
+    return true;
+}
+
+static bool IsGaussScore(const std::string &s) { return s == "bic-g" || s == "aic-g" || s == "loglik-g" || s == "bge"; }
+
+// the refusal of a learner that takes discrete data only
+static int RefuseGaussScore(const std::string &score_name, int algorithm) {
+    fprintf(stderr, "Error: --score %s scores continuous data, which -a %d does not learn from (hill climbing, -a 14, does)\n",
+            score_name.c_str(), algorithm);
+    return 1;
+}
+
+// A Bayesian Dirichlet score (BDeu with --iss, K2) has no penalty term and goes through the _bd entries; every
+// other name is a penalty per free parameter.  0, or 1 with the refusal printed.
+struct LearnerScore {
+    bool is_bd = false;
+    fbn_bd_score bd{};
+    double penalty = 0.0;
+};
+static int ParseLearnerScore(const std::string &score_name, bool iss_given, double iss, int64_t ns, LearnerScore *s) {
+    s->is_bd = score_name == "bde" || score_name == "k2";
+    if (iss_given && score_name != "bde") {
+        fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
+        return 1;
+    }
+    s->bd = fbn_bd_score{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+    if (!s->is_bd && fbn_hc_penalty(score_name.c_str(), ns, &s->penalty)) {
+        fprintf(stderr, "Error: %s\n", fbn_last_error());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     int algorithm = 2, num_threads = 1, group_size = 1, device = 0, depth = 1000, gpus = 1, propagation_length = 2;
     double tol = 0.0, damping = 0.0, eps = -1.0;
@@ -493,12 +546,8 @@ int main(int argc, char **argv) {
         };
         // the scores of continuous data (bic-g, aic-g, loglik-g: the Gaussian log-likelihood score; bge, with --iss as
         // alpha_mu) read -f2 as a CSV of reals, as -a 19 does, and go through the _gauss entries
-        const bool gauss = score_name == "bic-g" || score_name == "aic-g" || score_name == "loglik-g" || score_name == "bge";
-        if (gauss && exact) {
-            fprintf(stderr, "Error: --score %s scores continuous data, which -a 17 does not learn from (hill climbing, -a 14, does)\n",
-                    score_name.c_str());
-            return 1;
-        }
+        const bool gauss = IsGaussScore(score_name);
+        if (gauss && exact) return RefuseGaussScore(score_name, algorithm);
         int n = 0;
         int64_t ns = 0;
         fbn_hc_options opt{};
@@ -547,36 +596,26 @@ int main(int argc, char **argv) {
                 return die();
             }
         } else {
-            fbn_dataset *ds = nullptr;
-            if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
-            fbn_dataset_shape(ds, &n, &ns);
-            std::vector<int32_t> dims((size_t)n);
-            std::vector<uint8_t> cols((size_t)n * (size_t)ns);
-            fbn_dataset_dims(ds, dims.data());
-            fbn_dataset_columns(ds, cols.data());
-            fbn_dataset_destroy(ds);
-            // a Bayesian Dirichlet score (BDeu with --iss, K2) has no penalty term and goes through the _bd entries
-            const bool is_bd = score_name == "bde" || score_name == "k2";
-            if (iss_given && score_name != "bde") {
-                fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
-                return 1;
-            }
-            const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
-            if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &opt.penalty)) return die();
+            DiscreteSet D;
+            if (!LoadDiscreteSet(train_set_file, &D)) return die();
+            n = D.n, ns = D.ns;
+            LearnerScore sc;
+            if (ParseLearnerScore(score_name, iss_given, iss, ns, &sc)) return 1;
+            opt.penalty = sc.penalty;
             opt.max_parents = max_parents;
             opt.max_iter = -1;
             fbn_exact_options xopt{};
             xopt.penalty = opt.penalty;
             xopt.max_parents = max_parents;
             if (device < 0) {
-                if (is_bd ? (exact ? fbn_exact_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, &bd, &res)
-                                   : fbn_hc_run_bd_host(n, dims.data(), cols.data(), ns, &opt, &bd, &res))
-                          : (exact ? fbn_exact_run_host(n, dims.data(), cols.data(), ns, &xopt, &res)
-                                   : fbn_hc_run_host(n, dims.data(), cols.data(), ns, &opt, &res)))
+                if (sc.is_bd ? (exact ? fbn_exact_run_bd_host(n, D.dims.data(), D.cols.data(), ns, &xopt, &sc.bd, &res)
+                                   : fbn_hc_run_bd_host(n, D.dims.data(), D.cols.data(), ns, &opt, &sc.bd, &res))
+                          : (exact ? fbn_exact_run_host(n, D.dims.data(), D.cols.data(), ns, &xopt, &res)
+                                   : fbn_hc_run_host(n, D.dims.data(), D.cols.data(), ns, &opt, &res)))
                     return die();
             } else {
-                if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
-                if (is_bd ? (exact ? fbn_exact_run_bd(ctx, &xopt, &bd, &res) : fbn_hc_run_bd(ctx, &opt, &bd, &res))
+                if (fbn_ci_dataset_upload(D.cols.data(), n, ns, D.dims.data(), device, &ctx)) return die();
+                if (sc.is_bd ? (exact ? fbn_exact_run_bd(ctx, &xopt, &sc.bd, &res) : fbn_hc_run_bd(ctx, &opt, &sc.bd, &res))
                           : (exact ? fbn_exact_run(ctx, &xopt, &res) : fbn_hc_run(ctx, &opt, &res)))
                     return die();
             }
@@ -634,11 +673,7 @@ int main(int argc, char **argv) {
                   << "score = " << score_name << ", max parents = " << max_parents << ", prior = " << prior_name << std::endl
                   << "\tsample set: " << train_set_file << std::endl
                   << "===============================" << std::endl;
-        if (score_name == "bic-g" || score_name == "aic-g" || score_name == "loglik-g" || score_name == "bge") {
-            fprintf(stderr, "Error: --score %s scores continuous data, which -a %d does not learn from (hill climbing, -a 14, does)\n",
-                    score_name.c_str(), algorithm);
-            return 1;
-        }
+        if (IsGaussScore(score_name)) return RefuseGaussScore(score_name, algorithm);
         auto die = [] {
             fprintf(stderr, "Error: %s\n", fbn_last_error());
             return 1;
@@ -648,34 +683,24 @@ int main(int argc, char **argv) {
             return 1;
         }
         const int32_t prior = prior_name == "indegree";
-        fbn_dataset *ds = nullptr;
-        if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
-        int n = 0;
-        int64_t ns = 0;
-        fbn_dataset_shape(ds, &n, &ns);
-        std::vector<int32_t> dims((size_t)n);
-        std::vector<uint8_t> cols((size_t)n * (size_t)ns);
-        fbn_dataset_dims(ds, dims.data());
-        fbn_dataset_columns(ds, cols.data());
-        fbn_dataset_destroy(ds);
-        const bool is_bd = score_name == "bde" || score_name == "k2";
-        if (iss_given && score_name != "bde") {
-            fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
-            return 1;
-        }
-        const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+        DiscreteSet D;
+        if (!LoadDiscreteSet(train_set_file, &D)) return die();
+        const int n = D.n;
+        const int64_t ns = D.ns;
+        LearnerScore sc;
+        if (ParseLearnerScore(score_name, iss_given, iss, ns, &sc)) return 1;
         fbn_exact_options xopt{};
-        if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &xopt.penalty)) return die();
+        xopt.penalty = sc.penalty;
         xopt.max_parents = max_parents;
         fbn_bma_result *res = nullptr;
         fbn_ci_ctx *ctx = nullptr;
         if (device < 0) {
-            if (is_bd ? fbn_bma_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, prior, &bd, &res)
-                      : fbn_bma_run_host(n, dims.data(), cols.data(), ns, &xopt, prior, &res))
+            if (sc.is_bd ? fbn_bma_run_bd_host(n, D.dims.data(), D.cols.data(), ns, &xopt, prior, &sc.bd, &res)
+                      : fbn_bma_run_host(n, D.dims.data(), D.cols.data(), ns, &xopt, prior, &res))
                 return die();
         } else {
-            if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
-            if (is_bd ? fbn_bma_run_bd(ctx, &xopt, prior, &bd, &res) : fbn_bma_run(ctx, &xopt, prior, &res)) return die();
+            if (fbn_ci_dataset_upload(D.cols.data(), n, ns, D.dims.data(), device, &ctx)) return die();
+            if (sc.is_bd ? fbn_bma_run_bd(ctx, &xopt, prior, &sc.bd, &res) : fbn_bma_run(ctx, &xopt, prior, &res)) return die();
         }
         fbn_bma_info info;
         fbn_bma_result_info(res, &info);
@@ -721,11 +746,7 @@ int main(int argc, char **argv) {
                   << ", seed = " << seed << std::endl
                   << "\tsample set: " << train_set_file << std::endl
                   << "===============================" << std::endl;
-        if (score_name == "bic-g" || score_name == "aic-g" || score_name == "loglik-g" || score_name == "bge") {
-            fprintf(stderr, "Error: --score %s scores continuous data, which -a %d does not learn from (hill climbing, -a 14, does)\n",
-                    score_name.c_str(), algorithm);
-            return 1;
-        }
+        if (IsGaussScore(score_name)) return RefuseGaussScore(score_name, algorithm);
         auto die = [] {
             fprintf(stderr, "Error: %s\n", fbn_last_error());
             return 1;
@@ -739,35 +760,25 @@ int main(int argc, char **argv) {
             return 1;
         }
         const int32_t prior = prior_name == "indegree";
-        fbn_dataset *ds = nullptr;
-        if (fbn_dataset_load_csv(train_set_file.c_str(), &ds)) return die();
-        int n = 0;
-        int64_t ns = 0;
-        fbn_dataset_shape(ds, &n, &ns);
-        std::vector<int32_t> dims((size_t)n);
-        std::vector<uint8_t> cols((size_t)n * (size_t)ns);
-        fbn_dataset_dims(ds, dims.data());
-        fbn_dataset_columns(ds, cols.data());
-        fbn_dataset_destroy(ds);
-        const bool is_bd = score_name == "bde" || score_name == "k2";
-        if (iss_given && score_name != "bde") {
-            fprintf(stderr, "Error: --iss is the equivalent sample size of --score bde; the score is %s\n", score_name.c_str());
-            return 1;
-        }
-        const fbn_bd_score bd{score_name == "k2" ? FBN_SCORE_K2 : FBN_SCORE_BDE, 0, iss};
+        DiscreteSet D;
+        if (!LoadDiscreteSet(train_set_file, &D)) return die();
+        const int n = D.n;
+        const int64_t ns = D.ns;
+        LearnerScore sc;
+        if (ParseLearnerScore(score_name, iss_given, iss, ns, &sc)) return 1;
         fbn_exact_options xopt{};
-        if (!is_bd && fbn_hc_penalty(score_name.c_str(), ns, &xopt.penalty)) return die();
+        xopt.penalty = sc.penalty;
         xopt.max_parents = max_parents;
         const fbn_omcmc_options mopt{(int32_t)chains, (int32_t)samples, burn_in, thin, seed, 0, 0};
         fbn_omcmc_result *res = nullptr;
         fbn_ci_ctx *ctx = nullptr;
         if (device < 0) {
-            if (is_bd ? fbn_omcmc_run_bd_host(n, dims.data(), cols.data(), ns, &xopt, prior, &bd, &mopt, &res)
-                      : fbn_omcmc_run_host(n, dims.data(), cols.data(), ns, &xopt, prior, &mopt, &res))
+            if (sc.is_bd ? fbn_omcmc_run_bd_host(n, D.dims.data(), D.cols.data(), ns, &xopt, prior, &sc.bd, &mopt, &res)
+                      : fbn_omcmc_run_host(n, D.dims.data(), D.cols.data(), ns, &xopt, prior, &mopt, &res))
                 return die();
         } else {
-            if (fbn_ci_dataset_upload(cols.data(), n, ns, dims.data(), device, &ctx)) return die();
-            if (is_bd ? fbn_omcmc_run_bd(ctx, &xopt, prior, &bd, &mopt, &res) : fbn_omcmc_run(ctx, &xopt, prior, &mopt, &res)) return die();
+            if (fbn_ci_dataset_upload(D.cols.data(), n, ns, D.dims.data(), device, &ctx)) return die();
+            if (sc.is_bd ? fbn_omcmc_run_bd(ctx, &xopt, prior, &sc.bd, &mopt, &res) : fbn_omcmc_run(ctx, &xopt, prior, &mopt, &res)) return die();
         }
         fbn_omcmc_info info;
         fbn_omcmc_result_info(res, &info);

@@ -6,7 +6,6 @@
 // The reference has no score-based learner, so nothing here restates reference code; the method is Koivisto
 // & Sood's exact Bayesian structure discovery (JMLR 2004) with Koivisto's backward pass for all arcs at
 // once (UAI 2006).
-#include <chrono>
 #include <memory>
 #include <new>
 
@@ -16,11 +15,6 @@
 #include "hc_score.h"
 
 namespace fbn {
-
-namespace {
-using Clock = std::chrono::steady_clock;
-double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-}  // namespace
 
 int BmaCheck(int nvars, const int32_t *dims, const fbn_exact_options &opt, int prior) {
     if (prior != 0 && prior != 1) return SetError(FBN_ERR_ARG, "prior = %d: 0 (uniform) or 1 (indegree-uniform)", prior);
@@ -150,17 +144,11 @@ static int BmaRunHostEntry(int nvars, const int32_t *dims, const uint8_t *cols, 
                            const fbn_exact_options *options, int32_t prior, const fbn_bd_score *bd, fbn_bma_result **out) {
     if (!options || !out) return SetError(FBN_ERR_ARG, "null pointer");
     if (int rc = fbn::BmaCheck(nvars, dims, *options, prior)) return rc;
-    if (int rc = fbn::HcCheckSamples(nsamples)) return rc;
-    if (!cols) return SetError(FBN_ERR_ARG, "null column store");
-    for (int v = 0; v < nvars; ++v)
-        for (int64_t s = 0; s < nsamples; ++s)
-            if (cols[(size_t)v * nsamples + s] >= dims[v])
-                return SetError(FBN_ERR_ARG, "column store: variable %d holds a code >= its state count %d", v, dims[v]);
-    std::vector<double> L((size_t)nsamples + 1);
-    fbn_hc_fill_table(L.data(), nsamples);
     auto r = std::unique_ptr<fbn_bma_result>(new (std::nothrow) fbn_bma_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    if (int rc = fbn::BmaRunHost(nvars, dims, *options, prior, fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data(), bd), r.get()))
+    if (int rc = fbn::WithHostScorer(nvars, dims, cols, nsamples, bd, [&](const fbn::HcScorer &scorer) {
+            return fbn::BmaRunHost(nvars, dims, *options, prior, scorer, r.get());
+        }))
         return rc;
     *out = r.release();
     return FBN_OK;

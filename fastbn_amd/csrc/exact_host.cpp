@@ -6,7 +6,6 @@
 // nothing here restates reference code; the algorithm is Silander & Myllymaki's dynamic programme over
 // variable subsets (UAI 2006), with the definitions and tie rules of include/fastbn.h.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
 #include <memory>
@@ -19,9 +18,6 @@
 namespace fbn {
 
 namespace {
-
-using Clock = std::chrono::steady_clock;
-double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 constexpr int64_t kExactBatch = 1 << 15;  // families per scorer call
 
@@ -243,17 +239,11 @@ static int ExactRunHostEntry(int nvars, const int32_t *dims, const uint8_t *cols
                              const fbn_exact_options *options, const fbn_bd_score *bd, fbn_hc_result **out) {
     if (!options || !out) return SetError(FBN_ERR_ARG, "null pointer");
     if (int rc = fbn::ExactCheck(nvars, dims, *options)) return rc;
-    if (int rc = fbn::HcCheckSamples(nsamples)) return rc;
-    if (!cols) return SetError(FBN_ERR_ARG, "null column store");
-    for (int v = 0; v < nvars; ++v)
-        for (int64_t s = 0; s < nsamples; ++s)
-            if (cols[(size_t)v * nsamples + s] >= dims[v])
-                return SetError(FBN_ERR_ARG, "column store: variable %d holds a code >= its state count %d", v, dims[v]);
-    std::vector<double> L((size_t)nsamples + 1);
-    fbn_hc_fill_table(L.data(), nsamples);
     auto r = std::unique_ptr<fbn_hc_result>(new (std::nothrow) fbn_hc_result());
     if (!r) return SetError(FBN_ERR_NOMEM, "out of memory");
-    if (int rc = fbn::ExactRunHost(nvars, dims, *options, fbn::HcHostScorer(nvars, dims, cols, nsamples, L.data(), bd), r.get()))
+    if (int rc = fbn::WithHostScorer(nvars, dims, cols, nsamples, bd, [&](const fbn::HcScorer &scorer) {
+            return fbn::ExactRunHost(nvars, dims, *options, scorer, r.get());
+        }))
         return rc;
     *out = r.release();
     return FBN_OK;

@@ -4,6 +4,7 @@
 #ifndef FBN_HC_SEARCH_H
 #define FBN_HC_SEARCH_H
 
+#include <chrono>
 #include <cstdint>
 #include <functional>
 #include <vector>
@@ -11,6 +12,10 @@
 #include "../../include/fastbn.h"
 
 namespace fbn {
+
+// the wall clock of every learner's phase records (hill climbing, the lattice learners, order MCMC)
+using Clock = std::chrono::steady_clock;
+inline double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 // families [0, nfam): columns fam_cols[fam_off[f] .. fam_off[f+1]), the child first, its parents
 // ascending; pen[f] = the family's penalty term; cells[f] = its table size.  Writes loglik / score
@@ -43,9 +48,15 @@ int BdCheck(const fbn_bd_score *bd);
 // score = loglik - pen[f] (hc_score.h); else the Bayesian Dirichlet score (hc_bd.h), pen[f] unread
 HcScorer HcHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const double *L,
                       const fbn_bd_score *bd = nullptr);
+// the prologue of every host entry that scores: the sample count, the column store (not null, every code below
+// its variable's state count) and the scorer's table; run(scorer) under them, its return value passed on
+int WithHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const fbn_bd_score *bd,
+                   const std::function<int(const HcScorer &)> &run);
 // the device scorer over a CI context's resident column store (capi_hc.hip); bd as above
 int HcDeviceScore(fbn_ci_ctx *c, const HcBatch &B, double *loglik, double *score, double *kernel_ms,
                   const fbn_bd_score *bd = nullptr);
+// HcDeviceScore as a scorer; c and *bd outlive it
+HcScorer HcDeviceScorer(fbn_ci_ctx *c, const fbn_bd_score *bd);
 
 }  // namespace fbn
 

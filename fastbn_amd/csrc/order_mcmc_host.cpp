@@ -6,7 +6,6 @@
 // The reference has no score-based learner, so nothing here restates reference code; the method is Friedman &
 // Koller's MCMC over node orders (Machine Learning 2003).
 #include <algorithm>
-#include <chrono>
 #include <memory>
 #include <new>
 
@@ -18,9 +17,6 @@
 namespace fbn {
 
 namespace {
-
-using Clock = std::chrono::steady_clock;
-double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 // term_v of node v's list under pred: the maximum, the ranked slots, the butterfly, the logarithm
 double HostTerm(const OmcmcEntry *e, int64_t len, uint64_t pred) {
@@ -263,20 +259,6 @@ static int OmcmcRunHost(int n, const int32_t *dims, const fbn_exact_options &opt
     OmcmcFinish(n, m, acc.data(), orders.data(), res);
     res->info.wall_ms = MsSince(t_start);
     return FBN_OK;
-}
-
-// the host column store's checks and its scorer's table; fn(scorer) runs under them
-template <class Fn>
-static int WithHostScorer(int nvars, const int32_t *dims, const uint8_t *cols, int64_t nsamples, const fbn_bd_score *bd, Fn fn) {
-    if (int rc = HcCheckSamples(nsamples)) return rc;
-    if (!cols) return SetError(FBN_ERR_ARG, "null column store");
-    for (int v = 0; v < nvars; ++v)
-        for (int64_t s = 0; s < nsamples; ++s)
-            if (cols[(size_t)v * nsamples + s] >= dims[v])
-                return SetError(FBN_ERR_ARG, "column store: variable %d holds a code >= its state count %d", v, dims[v]);
-    std::vector<double> L((size_t)nsamples + 1);
-    fbn_hc_fill_table(L.data(), nsamples);
-    return fn(HcHostScorer(nvars, dims, cols, nsamples, L.data(), bd));
 }
 
 }  // namespace fbn

@@ -6,6 +6,7 @@ import hashlib
 import os
 
 import numpy as np
+import pytest
 
 import fastbn_amd as F
 
@@ -181,3 +182,31 @@ def synth12_dataset(N=1003, seed=8):
         synth.random_network(path=path, name="hc12", n_nodes=12, seed=seed, window=5, parent_probs=(0.5, 0.3, 0.2), dom=(2, 4))
         net = synth.read_xmlbif(path)
         return F.Dataset(columns=synth.forward_sample(net, N, seed), dims=np.array(net[1], np.int32))
+
+
+class HostStore:
+    """What a host entry reads of a Dataset: 3 binary variables over a column store that need not hold its samples."""
+
+    def __init__(self, columns, nsamples):
+        self.columns, self.dims = columns, np.array([2, 2, 2], np.int32)
+        self.num_vars, self.num_instance = 3, nsamples
+
+
+def host_prologue_refusals():
+    """[(source, code, message)]: the refusals of the prologue every scoring host entry runs after its own option
+    checks -- a null column store, a code at or above its state count, more than 2^24 samples (refused by the count
+    alone, ahead of any read: a 1-byte table stands in for the store)."""
+    bad = np.zeros((3, 8), np.uint8)
+    bad[1, 5] = 2
+    return [(HostStore(None, 8), ARG, "null column store"),
+            (HostStore(bad, 8), ARG, "column store: variable 1 holds a code >= its state count 2"),
+            (HostStore(np.zeros(1, np.uint8), (1 << 24) + 1), LIMIT,
+             "score table: 16777217 samples need 134217744 bytes (at most 2^24 samples)")]
+
+
+def assert_host_prologue_refusals(run):
+    """run(source) reaches a host entry; each refusal comes back with its code and text"""
+    for src, code, msg in host_prologue_refusals():
+        with pytest.raises(F.FastBNError) as e:
+            run(src)
+        assert e.value.code == code and msg in str(e.value), (msg, str(e.value))

@@ -140,3 +140,8 @@ def test_lse(a, b):
     # the cutoffs: an absent operand, and a difference past -37 (e^-37 < 2^-53), return the larger unchanged
     assert F.api._lse(a, -INF) == a and F.api._lse(-INF, a) == a and F.api._lse(-INF, -INF) == -INF
     assert F.api._lse(a, np.nextafter(a - 37.0, -INF)) == a
+
+
+@pytest.mark.parametrize("score", ["bic", "bde"])
+def test_column_store_refusals(score):
+    H.assert_host_prologue_refusals(lambda src: F.ArcPosterior(score=score).learn(src, host=True))

@@ -103,3 +103,8 @@ def test_more_than_26_variables_is_refused():
     with pytest.raises(F.FastBNError) as e:
         F.ExactSearch("bic").learn(ds, host=True)
     assert e.value.code == H.LIMIT and "bytes" in str(e.value)
+
+
+@pytest.mark.parametrize("score", ["bic", "bde"])
+def test_column_store_refusals(score):
+    H.assert_host_prologue_refusals(lambda src: F.ExactSearch(score=score).learn(src, host=True))

@@ -283,3 +283,9 @@ def test_exact_ties_go_to_the_lowest_operation():
     assert hc.trace[0][3] == sc[0] - sc[2]
     assert len(hc.trace) >= 2 and (0, 1, 2) not in [t[:3] for t in hc.trace]
     assert H.skeleton(hc.parents) in ({(0, 1), (0, 2)}, {(0, 1), (1, 2)})
+
+
+@pytest.mark.parametrize("score", ["bic", "bde"])
+def test_column_store_refusals(score):
+    H.assert_host_prologue_refusals(lambda src: F.HillClimbing(score=score).learn(src, host=True))
+    H.assert_host_prologue_refusals(lambda src: F.family_scores(src, [(0,)], 0.0, score=None if score == "bic" else score, host=True))

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import fastbn_amd as F
+import hc_data as H
 from hc_data import ARG, LIMIT
 
 U = 2.0 ** -53  # unit roundoff
@@ -121,3 +122,10 @@ def test_limits_and_arguments(n, kw, code):
     assert e.value.code == code and not hasattr(m, "arc_prob")
     if "max_families" in kw:  # 9 nodes of 1 + 8 + 28 + 56 candidates: the count is carried
         assert "837 entries" in str(e.value)
+
+
+@pytest.mark.parametrize("score", ["bic", "bde"])
+def test_column_store_refusals(score):
+    mc = F.OrderMCMC(score=score, chains=1, burn_in=0, samples=1, thin=1)
+    H.assert_host_prologue_refusals(lambda src: mc.learn(src, host=True))
+    H.assert_host_prologue_refusals(lambda src: mc.order_terms([[0, 1, 2]], src, host=True))
